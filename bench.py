@@ -7,7 +7,12 @@ minibatches of gather + fused PPO objective + backward + Adam, statistics pass).
 on the GPU; weights are random-init.  Multi-GPU (launched by torchrun, one rank per GPU): envs are sharded, 4096
 per rank (weak scaling), gradients and advantage statistics are all-reduced over RCCL/xGMI.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` — the
+wall-clock milliseconds of one timed iteration) and the run's configuration.  A plain run does nothing else: set-up, `--warmup`
+iterations, `--steps` timed iterations, the line.  `--dump-outputs DIR` writes what the last timed iteration computed as
+DIR/<name>.npy (dump_outputs).  `--full` adds the figures beside the headline, each measured after the timed region (its
+`--no-*` switch still skips it):
+  ppo_update_ms  — device time of one agent update (HIP events around it, inside the timed iterations)
   roofline       — dominant hot-path kernel = the minibatch gather that replays inside every captured train step (20 per
                    iteration): algorithmic bytes of exactly that launch / its graph-timed duration vs 8 TB/s HBM
                    roofline.at_scale — GAE, the PPO objective (std-vector form the preset runs), push, next_value,
@@ -15,6 +20,7 @@ Prints ONE JSON line on rank 0.  Extra objects:
                    approached (config 2 moves 1-13 MB per launch out of L2 / MALL)
   kernels        — the same accounting for every HIP kernel of the path at this workload's sizes
   cpu_baseline   — oracle/torch_ppo.py (reference-equivalent torch CPU path) timed on this box's host cores
+  config.gradient_allreduce, config.torch_generator_env_ms_per_step — the all-reduce of a multi-rank step, the env A/B
 
 `python bench.py --gpus N` without a launcher starts its own N ranks (torch.distributed.run, one process per GPU).
 """
@@ -43,6 +49,11 @@ def parse_args():
     parser.add_argument("--steps", type=int, default=50)   # >= 50 timed iterations ...
     parser.add_argument("--warmup", type=int, default=10)  # ... after >= 10 warm-up iterations
     parser.add_argument("--envs-per-gpu", type=int, default=NUM_ENVS)
+    parser.add_argument("--full", action="store_true",
+                        help="also measure every figure beside the headline (ppo_update_ms, roofline, kernels, gradient all-reduce, "
+                             "torch-generator env A/B, CPU baseline); the --no-* switches below apply to these")
+    parser.add_argument("--dump-outputs", metavar="DIR",
+                        help="write what the last timed iteration computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     parser.add_argument("--no-cpu-baseline", action="store_true")
     parser.add_argument("--no-kernel-pass", action="store_true")
     parser.add_argument("--no-scale-pass", action="store_true", help="skip the 1 048 576-env roofline-scale kernel pass")
@@ -245,6 +256,42 @@ def torch_generator_env_ms(args, device):
     return round(ms, 3)
 
 
+DUMP_ENV_COLUMNS = 1024  # env instances of the rollout buffer written by --dump-outputs (a fixed seeded sample when there are more)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: Path, trainer, observation, state) -> None:
+    """What a caller of the timed path holds after its last iteration, as ``directory/<name>.npy`` (float64 for 64-bit data,
+    float32 otherwise): the observation (and recurrent state) it returned, every parameter of the updated agent, every leaf of
+    the rollout buffer — that rollout's advantage, return, values, actions ... — at DUMP_ENV_COLUMNS env instances, and the
+    iteration's logged statistics without its wall-clock ("Perf/") figures.  Inputs are seeded: two builds run with the same
+    arguments can be compared array by array."""
+    import numpy as np
+
+    agent, buffer = trainer.agent, trainer.agent.buffer
+    arrays = {"observation": observation}
+    if isinstance(state, torch.Tensor):
+        arrays["state"] = state
+    arrays.update({f"param.{name}": param for name, param in agent.named_parameters()})
+    columns = None
+    if buffer.parallelism > DUMP_ENV_COLUMNS:
+        columns = torch.randperm(buffer.parallelism, generator=torch.Generator().manual_seed(0))[:DUMP_ENV_COLUMNS].sort().values
+    for key, leaf in buffer.storage.items():
+        arrays[f"buffer.{key}"] = leaf if columns is None else leaf[:, columns.to(leaf.device)]
+    arrays.update({f"info.{key}": torch.tensor(float(value), dtype=torch.float64)
+                   for key, value in trainer.last_info.items() if not key.startswith("Perf/")})
+    directory.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, tensor in arrays.items():
+        tensor = tensor.detach()
+        wide = tensor.dtype in (torch.float64, torch.int64, torch.int32)
+        array = tensor.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        total += array.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB at {name}")
+        np.save(directory / f"{name.replace('/', '.')}.npy", array)
+
+
 def run_gpu(args, rank, world):
     import cusrl_amd as cusrl
     from cusrl_amd import ops
@@ -284,7 +331,8 @@ def run_gpu(args, rank, world):
         update_events.append((start, end))
         return result
 
-    agent.update = timed_update
+    if args.full:
+        agent.update = timed_update
 
     def barrier():
         torch.cuda.synchronize()
@@ -307,14 +355,16 @@ def run_gpu(args, rank, world):
     trainer.flush()  # the last iteration's log (the trainer reads an iteration's log behind the next rollout's launch) is timed too
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), trainer, observation, state)
     update_ms = sum(s.elapsed_time(e) for s, e in update_events) / max(len(update_events), 1)
     # the dominant kernel replays inside hipGraphs (20 launches per iteration) where it cannot be bracketed from the
     # host: time the identical launch stand-alone from a graph right after the timed region
-    dominant = dominant_kernel(agent) if rank == 0 else None
+    dominant = dominant_kernel(agent) if args.full and rank == 0 else None
     # the gradient all-reduce of one optimizer step at this run's world size (a collective: EVERY rank times it), as the
     # step issues it: the C-ABI call captured in a hipGraph, or torch.distributed's eager call between two graphs
     allreduce_us = split_allreduce_us = None
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and agent.flat_gradients is not None:
+    if args.full and torch.distributed.is_available() and torch.distributed.is_initialized() and agent.flat_gradients is not None:
         flat = agent.flat_gradients.buffer
         scratch = torch.zeros_like(flat)
         comm = cusrl.utils.distributed.native_comm()
@@ -366,14 +416,14 @@ def run_gpu(args, rank, world):
         elapsed = float(t.item())
 
     env_ab_ms = None
-    if getattr(env, "fused", False) and world == 1 and not args.no_env_ab:
+    if args.full and getattr(env, "fused", False) and world == 1 and not args.no_env_ab:
         try:
             env_ab_ms = torch_generator_env_ms(args, device)
         except Exception as error:  # an A/B beside the headline must never cost the line itself
             print(f"bench: torch-generator env A/B skipped ({type(error).__name__}: {error})", file=sys.stderr)
 
     kernels = {}
-    if not args.no_kernel_pass and rank == 0:
+    if args.full and not args.no_kernel_pass and rank == 0:
         # every HIP kernel of the path stand-alone at this workload's sizes, replayed from a hipGraph between one
         # HIP-event pair (bracketing each eager launch with events costs a 10-40 us stream bubble per pair and would
         # dominate these 3-10 us kernels); scripts/kernel_bench.py also reports the roofline-scale size (1M envs)
@@ -385,7 +435,7 @@ def run_gpu(args, rank, world):
                              "achieved_GBps": round(nbytes / us / 1e3, 1), "frac_of_hbm_peak": round(nbytes / us / 1e3 / HBM_PEAK_GBS, 4)}
 
     scale = {}
-    if not args.no_scale_pass and rank == 0 and world == 1:
+    if args.full and not args.no_scale_pass and rank == 0 and world == 1:
         # the north-star bar "GAE + loss kernels >= 40 % of the HBM roofline" needs sizes where a launch outlives its
         # latency: the same kernels at 1 048 576 envs (24 M slots), graph-timed by scripts/kernel_bench.py
         sys.path.insert(0, str(ROOT / "scripts"))
@@ -404,7 +454,7 @@ def run_gpu(args, rank, world):
         torch.cuda.empty_cache()
 
     mfma = None
-    if not args.no_scale_pass and rank == 0 and world == 1:
+    if args.full and not args.no_scale_pass and rank == 0 and world == 1:
         try:
             mfma = mlp_forward_roofline(agent)
         except Exception as error:  # an extra beside the headline must never cost the line itself
@@ -412,7 +462,7 @@ def run_gpu(args, rank, world):
         torch.cuda.empty_cache()
 
     steps_per_iteration = args.envs_per_gpu * HORIZON * world
-    traffic, traffic_source = pmc_traffic(args.envs_per_gpu)
+    traffic, traffic_source = pmc_traffic(args.envs_per_gpu) if args.full else (None, None)
     profile = rocprof_gather(dominant["bytes_per_launch"]) if dominant and args.envs_per_gpu == NUM_ENVS else None
     dominant = dominant or {"achieved_GBps": 0.0, "bytes_per_launch": 0, "avg_us": 0.0, "rows": 0, "fields": [], "leaves": 0,
                             "packed_leaves": 0, "row_bytes": 0}
@@ -462,52 +512,55 @@ def run_gpu(args, rank, world):
             "autoreset": args.autoreset,
             "host_thread_cpus": pinned,
         },
-        "ppo_update_ms": round(update_ms, 3),
-        "roofline": {
-            "bound": "hbm",
-            "kernel": f"cusrl::gather_kernel — the minibatch gather (20 launches per iteration; since round 6 issued one step "
-                      f"AHEAD, at the tail of the previous step's critic branch inside the epoch's hipGraph): "
-                      f"{dominant['rows']} sampled slots x {dominant['leaves']} leaves the step reads ({', '.join(dominant['fields'])}; "
-                      f"{dominant['packed_leaves']} of them through the per-slot record — none while the sampled leaves fit L2 + "
-                      f"Infinity Cache, Buffer.record_threshold_bytes), {dominant['row_bytes']} B/slot read + written + 8 B index",
-            # `frac` / `achieved` are the REPRODUCIBLE figures: algorithmic bytes of the launch / its average duration in the
-            # committed rocprofv3 kernel trace of this very command (per-grid split, profiles/<round>/) / 8 TB/s.  The same
-            # launch timed live by this run (a hipGraph of 10 identical launches x 20 replays between one HIP-event pair,
-            # right after the timed region, on the graph's stream — the in-step launch cannot be bracketed from the host) is
-            # beside it as `frac_graph_timed`: the profiler adds ~1.5-2 us to a sub-10 us dispatch and the in-step launch shares
-            # the chip with the other branch, so the live figure is the higher of the two.  Without a committed profile of this
-            # kernel source `frac` falls back to the live figure and `frac_source` says so.
-            "timing": ("rocprofv3 --kernel-trace per-grid average of this command: " + profile["source"] if profile
-                       else "graph-timed live (no committed rocprofv3 profile matches this kernel source)"),
-            "frac_source": "rocprofv3" if profile else "graph_timed",
-            "achieved": (round(dominant["bytes_per_launch"] / profile["avg_us"] / 1e3, 1) if profile else dominant["achieved_GBps"]),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": (profile["frac"] if profile else round(dominant["achieved_GBps"] / HBM_PEAK_GBS, 4)),
-            "frac_graph_timed": round(dominant["achieved_GBps"] / HBM_PEAK_GBS, 4),
-            "achieved_graph_timed": dominant["achieved_GBps"],
-            "frac_rocprof": (profile or {}).get("frac"),
-            "rocprof": profile,
-            "traffic": traffic,
-            "traffic_source": traffic_source,
-            "bytes_per_launch": dominant["bytes_per_launch"],
-            "avg_us": (profile["avg_us"] if profile else dominant["avg_us"]),
-            "avg_us_graph_timed": dominant["avg_us"],
-            "launches_per_iteration": 20,
-            "note": "GAE stages its (reward, value, next_value, done) tuple in registers, not LDS: every element is used "
-                    "once by the lane that loaded it (DESIGN.md section 3)",
-            # the north-star criterion (GAE + loss >= 40 % of the HBM roofline) where a roofline can physically be shown:
-            # the same C-ABI launches at 1 048 576 envs x 24 steps, algorithmic bytes / graph-timed duration / 8 TB/s
-            "at_scale": {"envs": 1 << 20, "timing": "hipGraph of 10 launches between one HIP-event pair (scripts/kernel_bench.py)",
-                         "counters": "profiles/r04/pmc/pmc_summary.json, profiles/r05/pmc/pmc_summary.json (kernel sources unchanged since)",
-                         **scale},
-            # ... and flat, for consumers that keep scalars only
-            **{f"at_scale_{key}_frac": entry["frac"] for key, entry in scale.items()},
-            # the one kernel of the path bound by the matrix cores, not by bytes (round 6): the no-grad MLP pass
-            **({"mfma_kernel": mfma} if mfma else {}),
-        },
-        "kernels": kernels,
     }
+    if args.full:
+        result.update({
+            "ppo_update_ms": round(update_ms, 3),
+            "roofline": {
+                "bound": "hbm",
+                "kernel": f"cusrl::gather_kernel — the minibatch gather (20 launches per iteration; since round 6 issued one step "
+                          f"AHEAD, at the tail of the previous step's critic branch inside the epoch's hipGraph): "
+                          f"{dominant['rows']} sampled slots x {dominant['leaves']} leaves the step reads ({', '.join(dominant['fields'])}; "
+                          f"{dominant['packed_leaves']} of them through the per-slot record — none while the sampled leaves fit L2 + "
+                          f"Infinity Cache, Buffer.record_threshold_bytes), {dominant['row_bytes']} B/slot read + written + 8 B index",
+                # `frac` / `achieved` are the REPRODUCIBLE figures: algorithmic bytes of the launch / its average duration in the
+                # committed rocprofv3 kernel trace of this very command (per-grid split, profiles/<round>/) / 8 TB/s.  The same
+                # launch timed live by this run (a hipGraph of 10 identical launches x 20 replays between one HIP-event pair,
+                # right after the timed region, on the graph's stream — the in-step launch cannot be bracketed from the host) is
+                # beside it as `frac_graph_timed`: the profiler adds ~1.5-2 us to a sub-10 us dispatch and the in-step launch shares
+                # the chip with the other branch, so the live figure is the higher of the two.  Without a committed profile of this
+                # kernel source `frac` falls back to the live figure and `frac_source` says so.
+                "timing": ("rocprofv3 --kernel-trace per-grid average of this command: " + profile["source"] if profile
+                           else "graph-timed live (no committed rocprofv3 profile matches this kernel source)"),
+                "frac_source": "rocprofv3" if profile else "graph_timed",
+                "achieved": (round(dominant["bytes_per_launch"] / profile["avg_us"] / 1e3, 1) if profile else dominant["achieved_GBps"]),
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": (profile["frac"] if profile else round(dominant["achieved_GBps"] / HBM_PEAK_GBS, 4)),
+                "frac_graph_timed": round(dominant["achieved_GBps"] / HBM_PEAK_GBS, 4),
+                "achieved_graph_timed": dominant["achieved_GBps"],
+                "frac_rocprof": (profile or {}).get("frac"),
+                "rocprof": profile,
+                "traffic": traffic,
+                "traffic_source": traffic_source,
+                "bytes_per_launch": dominant["bytes_per_launch"],
+                "avg_us": (profile["avg_us"] if profile else dominant["avg_us"]),
+                "avg_us_graph_timed": dominant["avg_us"],
+                "launches_per_iteration": 20,
+                "note": "GAE stages its (reward, value, next_value, done) tuple in registers, not LDS: every element is used "
+                        "once by the lane that loaded it (DESIGN.md section 3)",
+                # the north-star criterion (GAE + loss >= 40 % of the HBM roofline) where a roofline can physically be shown:
+                # the same C-ABI launches at 1 048 576 envs x 24 steps, algorithmic bytes / graph-timed duration / 8 TB/s
+                "at_scale": {"envs": 1 << 20, "timing": "hipGraph of 10 launches between one HIP-event pair (scripts/kernel_bench.py)",
+                             "counters": "profiles/r04/pmc/pmc_summary.json, profiles/r05/pmc/pmc_summary.json (kernel sources unchanged since)",
+                             **scale},
+                # ... and flat, for consumers that keep scalars only
+                **{f"at_scale_{key}_frac": entry["frac"] for key, entry in scale.items()},
+                # the one kernel of the path bound by the matrix cores, not by bytes (round 6): the no-grad MLP pass
+                **({"mfma_kernel": mfma} if mfma else {}),
+            },
+            "kernels": kernels,
+        })
     trainer.environment.close()
     return result
 
@@ -615,7 +668,7 @@ def main():
         except OSError:
             pass
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = run_cpu_baseline(args)
             result["speedup_vs_cpu_baseline"] = round(result["value"] / result["cpu_baseline"]["value"], 2)
         print(json.dumps(result), flush=True)

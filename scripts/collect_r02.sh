@@ -6,15 +6,15 @@ O=$R/gpurun_out/r02
 mkdir -p "$O/configs"
 cd "$R"
 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tee "$O/pytest_gpu.txt"
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > "$O/bench_line.json"
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > "$O/bench_line.json"
 python -c "import json;d=json.load(open('$O/bench_line.json'));print('bench', d['value'], d['ms_per_step'], d['ppo_update_ms'], d['roofline']['avg_us'], d['roofline']['frac'], d.get('speedup_vs_cpu_baseline'))"
-for i in 1 2 3; do python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-pass --no-scale-pass 2>/dev/null | tail -1; done | python -c "
+for i in 1 2 3; do python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-pass --no-scale-pass 2>/dev/null | tail -1; done | python -c "
 import sys, json
 for line in sys.stdin:
     d = json.loads(line); print('repeat', d['value'], d['ms_per_step'], d['ppo_update_ms'])" | tee "$O/bench_repeats.txt"
 # one RCCL rank (torchrun): eager all-reduce between two graphs vs the C-ABI all-reduce captured inside the step graph
 for flag in "" "--native-collectives"; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 \
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 \
       --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-pass --no-scale-pass $flag 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('rccl-1-rank', d['config']['collectives'][:48], '|', d['value'], 'env-steps/s', d['ms_per_step'], 'ms/iteration, update', d['ppo_update_ms'], 'ms')"

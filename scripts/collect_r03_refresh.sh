@@ -13,9 +13,9 @@ cp gpurun_out/gradient_parity.json "$O/gradient_parity.json" 2>/dev/null
 bash scripts/gpu_pmc.sh r03_pmc > "$O/gpu_pmc.log" 2>&1
 tail -3 "$O/gpu_pmc.log"
 cp gpurun_out/r03_pmc/pmc_summary.json profiles/r03/pmc_summary.json   # (on the box's copy: the bench line below quotes it)
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > "$O/bench_line.json"
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > "$O/bench_line.json"
 python -c "import json;d=json.load(open('$O/bench_line.json'));print('bench', d['value'], d['ms_per_step'], d['ppo_update_ms'], d['roofline']['avg_us'], d['roofline']['frac'], d['roofline']['traffic'], d.get('speedup_vs_cpu_baseline'), d['cpu_baseline']['value'], d['cpu_baseline']['cores'])"
-for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-pass --no-scale-pass 2>/dev/null | tail -1 | python -c "
+for i in 1 2 3; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-pass --no-scale-pass 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('repeat', d['value'], d['ms_per_step'], d['ppo_update_ms'], d['config'].get('captured_env_steps'), d['config'].get('collectives'))"; done | tee "$O/bench_repeats.txt"
 python scripts/kernel_bench.py --envs 4096 1048576 --json "$O/kernel_bench_graph_timed.json" 2>/dev/null | grep -v amdgpu > "$O/kernel_bench_graph_timed.txt"

@@ -8,7 +8,7 @@ mkdir -p "$O/configs"
 cd "$R"
 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tee "$O/pytest_gpu.txt"
 cp gpurun_out/gradient_parity.json "$O/gradient_parity.json" 2>/dev/null
-python bench.py 2>/dev/null | tail -1 > "$O/bench_line.json"
+python bench.py --full 2>/dev/null | tail -1 > "$O/bench_line.json"
 python -c "import json;d=json.load(open('$O/bench_line.json'));print('bench', d['value'], d['ms_per_step'], d['ppo_update_ms'], d['roofline']['avg_us'], d['roofline']['frac'], {k: v['frac'] for k, v in d['roofline']['at_scale'].items() if isinstance(v, dict)}, d['cpu_baseline']['value'], d['cpu_baseline']['cores'])"
 brief() { python -c "
 import sys, json
@@ -16,14 +16,14 @@ for line in sys.stdin:
     if line.startswith('{'):
         d = json.loads(line); print('$1', d['value'], d['ms_per_step'], d['ppo_update_ms'], d['config'].get('captured_env_steps'), d['config'].get('epoch_graph_updates'), d['config'].get('collectives'), d['config'].get('gradient_allreduce'))"; }
 B="--no-cpu-baseline --no-kernel-pass --no-scale-pass"
-for i in 1 2 3; do python bench.py $B 2>/dev/null | tail -1; done | brief repeat | tee "$O/bench_repeats.txt"
+for i in 1 2 3; do python bench.py --full $B 2>/dev/null | tail -1; done | brief repeat | tee "$O/bench_repeats.txt"
 # interleaved A/B on this box of this round's switches
-for i in 1 2; do for v in 0 1; do CUSRL_FUSED_ENV=$v python bench.py $B --steps 80 --warmup 10 2>/dev/null | tail -1 | brief "CUSRL_FUSED_ENV=$v"; done; done | tee "$O/bench_fused_env_ab.txt"
-for i in 1 2; do for v in 0 1; do CUSRL_EPOCH_GRAPHS=$v python bench.py $B --steps 80 --warmup 10 2>/dev/null | tail -1 | brief "CUSRL_EPOCH_GRAPHS=$v"; done; done | tee "$O/bench_epoch_graphs_ab.txt"
-for i in 1 2; do for v in 0 1; do CUSRL_FUSE_EPILOGUE_PUSH=$v python bench.py $B --steps 80 --warmup 10 2>/dev/null | tail -1 | brief "CUSRL_FUSE_EPILOGUE_PUSH=$v"; done; done | tee "$O/bench_epilogue_push_ab.txt"
+for i in 1 2; do for v in 0 1; do CUSRL_FUSED_ENV=$v python bench.py --full $B --steps 80 --warmup 10 2>/dev/null | tail -1 | brief "CUSRL_FUSED_ENV=$v"; done; done | tee "$O/bench_fused_env_ab.txt"
+for i in 1 2; do for v in 0 1; do CUSRL_EPOCH_GRAPHS=$v python bench.py --full $B --steps 80 --warmup 10 2>/dev/null | tail -1 | brief "CUSRL_EPOCH_GRAPHS=$v"; done; done | tee "$O/bench_epoch_graphs_ab.txt"
+for i in 1 2; do for v in 0 1; do CUSRL_FUSE_EPILOGUE_PUSH=$v python bench.py --full $B --steps 80 --warmup 10 2>/dev/null | tail -1 | brief "CUSRL_FUSE_EPILOGUE_PUSH=$v"; done; done | tee "$O/bench_epilogue_push_ab.txt"
 # one RCCL rank (torchrun): C-ABI collectives captured inside the step graph (default) vs torch.distributed's eager all-reduce
 for flag in "" "--torch-collectives"; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 $B $flag 2>/dev/null | tail -1 | brief "rccl_one_rank$flag"
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 $B $flag 2>/dev/null | tail -1 | brief "rccl_one_rank$flag"
 done | tee "$O/bench_rccl_one_rank.txt"
 python scripts/kernel_bench.py --envs 4096 1048576 --json "$O/kernel_bench_graph_timed.json" 2>/dev/null | grep -v amdgpu > "$O/kernel_bench_graph_timed.txt"
 for N in 1048576 4194304; do python scripts/pre_update_chain.py --envs $N; CUSRL_GAE_POLICY=0 CUSRL_GAE_BLOCK=256 python scripts/pre_update_chain.py --envs $N; done 2>/dev/null | grep "^{" > "$O/pre_update_chain.jsonl"

@@ -21,31 +21,31 @@ tests)
   cp gpurun_out/gradient_parity.json "$O/gradient_parity.json" 2>/dev/null
   ;;
 bench)
-  python bench.py 2>/dev/null | tail -1 > "$O/bench_line.json"
+  python bench.py --full 2>/dev/null | tail -1 > "$O/bench_line.json"
   python -c "import json;d=json.load(open('$O/bench_line.json'));print('bench', d['value'], d['ms_per_step'], d['ppo_update_ms'], d['roofline']['avg_us'], d['roofline']['frac'], d['roofline'].get('frac_graph_timed'), {k: v['frac'] for k, v in d['roofline']['at_scale'].items() if isinstance(v, dict)}, d['cpu_baseline']['value'], d['cpu_baseline']['cores'], d['config'].get('torch_generator_env_ms_per_step'))"
-  for i in 1 2 3; do python bench.py $B 2>/dev/null | tail -1; done | brief repeat | tee "$O/bench_repeats.txt"
-  python bench.py --gpus 1 --steps 20 --warmup 5 $B 2>/dev/null | tail -1 | brief driver_flags | tee -a "$O/bench_repeats.txt"
-  python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$O/bench_line_driver_flags.json"
+  for i in 1 2 3; do python bench.py --full $B 2>/dev/null | tail -1; done | brief repeat | tee "$O/bench_repeats.txt"
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 $B 2>/dev/null | tail -1 | brief driver_flags | tee -a "$O/bench_repeats.txt"
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$O/bench_line_driver_flags.json"
   # the same box, the round-5 tree (git worktree of the round-5 head with its own build under build/r05_tree) interleaved with
   # this one: what the round moved, free of the +-5 % between the pool's boxes
   if [ -f build/r05_tree/bench.py ]; then
     for i in 1 2 3; do
       (cd build/r05_tree && python bench.py $B --steps 50 --warmup 10 2>/dev/null | tail -1) | brief "round5_tree"
-      python bench.py $B 2>/dev/null | tail -1 | brief "round6_tree"
+      python bench.py --full $B 2>/dev/null | tail -1 | brief "round6_tree"
     done | tee "$O/same_box_r05_vs_r06.txt"
   fi
   # the round's switches, one at a time against the default, interleaved
   for i in 1 2; do
-    python bench.py $B 2>/dev/null | tail -1 | brief "default"
-    CUSRL_PIPELINE_LOGS=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_PIPELINE_LOGS=0 (log read before the next rollout is launched)"
-    CUSRL_FUSED_INFERENCE=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_FUSED_INFERENCE=0 (library GEMM chain for the no-grad passes)"
-    CUSRL_TWO_WINDOW_STEP=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_TWO_WINDOW_STEP=0 (join + one Adam launch per step)"
-    CUSRL_EPOCH_GRAPHS=1 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_EPOCH_GRAPHS=1 (one graph per epoch)"
-    CUSRL_EPOCH_GRAPHS=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_EPOCH_GRAPHS=0 (one graph per step)"
-    CUSRL_SEPARATE_VALUE_TERM=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_SEPARATE_VALUE_TERM=0"
-    CUSRL_PREFETCH_GATHER=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_PREFETCH_GATHER=0"
-    CUSRL_INPUT_LAYER_KERNEL=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_INPUT_LAYER_KERNEL=0"
-    CUSRL_CONCURRENT_CRITIC=0 python bench.py $B 2>/dev/null | tail -1 | brief "CUSRL_CONCURRENT_CRITIC=0"
+    python bench.py --full $B 2>/dev/null | tail -1 | brief "default"
+    CUSRL_PIPELINE_LOGS=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_PIPELINE_LOGS=0 (log read before the next rollout is launched)"
+    CUSRL_FUSED_INFERENCE=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_FUSED_INFERENCE=0 (library GEMM chain for the no-grad passes)"
+    CUSRL_TWO_WINDOW_STEP=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_TWO_WINDOW_STEP=0 (join + one Adam launch per step)"
+    CUSRL_EPOCH_GRAPHS=1 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_EPOCH_GRAPHS=1 (one graph per epoch)"
+    CUSRL_EPOCH_GRAPHS=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_EPOCH_GRAPHS=0 (one graph per step)"
+    CUSRL_SEPARATE_VALUE_TERM=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_SEPARATE_VALUE_TERM=0"
+    CUSRL_PREFETCH_GATHER=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_PREFETCH_GATHER=0"
+    CUSRL_INPUT_LAYER_KERNEL=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_INPUT_LAYER_KERNEL=0"
+    CUSRL_CONCURRENT_CRITIC=0 python bench.py --full $B 2>/dev/null | tail -1 | brief "CUSRL_CONCURRENT_CRITIC=0"
   done | tee "$O/switches_ab.txt"
   bash scripts/gpu_r06_one_rank.sh > "$O/one_rank.log" 2>&1; cp gpurun_out/r06_one_rank/* "$O/" 2>/dev/null; tail -6 "$O/bench_one_rank.txt"
   python scripts/input_layer_bench.py 2>&1 | grep -v amdgpu.ids | tee "$O/input_layer_bench.txt"

@@ -6,11 +6,11 @@ cd /tmp && export TMPDIR=/tmp
 B="--no-cpu-baseline --no-kernel-pass --no-scale-pass --no-env-ab --steps 50 --warmup 10"
 brief() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['ms_per_step'], 'ms/it, update', d['ppo_update_ms'], 'ms,', round(d['value']/1e6,2), 'M env-steps/s;', d['config'].get('collectives'), d['config'].get('gradient_allreduce'))"; }
 for i in 1 2 3; do
-  python $R/bench.py $B 2>/dev/null | brief "single process :" | tee -a $OUT/bench_one_rank.txt
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 2951$i $R/bench.py --gpus 1 $B 2>/dev/null | tail -1 | brief "one RCCL rank  :" | tee -a $OUT/bench_one_rank.txt
+  python $R/bench.py --full $B 2>/dev/null | brief "single process :" | tee -a $OUT/bench_one_rank.txt
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 2951$i $R/bench.py --full --gpus 1 $B 2>/dev/null | tail -1 | brief "one RCCL rank  :" | tee -a $OUT/bench_one_rank.txt
 done
 rm -rf /tmp/one_rank_trace
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/one_rank_trace -o bench -- python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 1 --no-cpu-baseline --no-kernel-pass --no-scale-pass --no-env-ab --steps 6 --warmup 6 > /tmp/one_rank.log 2>&1 < /dev/null
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/one_rank_trace -o bench -- python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --full --gpus 1 --no-cpu-baseline --no-kernel-pass --no-scale-pass --no-env-ab --steps 6 --warmup 6 > /tmp/one_rank.log 2>&1 < /dev/null
 for T in $(find /tmp/one_rank_trace -name "*kernel_trace.csv"); do
   n=$(wc -l < $T); echo "$T $n"
   if [ $n -gt 1000 ]; then

@@ -9,6 +9,6 @@ B="--no-cpu-baseline --no-kernel-pass --no-scale-pass --no-env-ab"
 brief() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['ms_per_step'], 'ms/it, update', d['ppo_update_ms'], 'ms,', round(d['value']/1e6,2), 'M env-steps/s')"; }
 for i in 1 2 3; do
   for mode in update 1; do
-    CUSRL_EPOCH_GRAPHS=$mode python bench.py $B 2>$OUT/bench_err.txt | brief "CUSRL_EPOCH_GRAPHS=$mode :" | tee -a $OUT/step_ab6.txt
+    CUSRL_EPOCH_GRAPHS=$mode python bench.py --full $B 2>$OUT/bench_err.txt | brief "CUSRL_EPOCH_GRAPHS=$mode :" | tee -a $OUT/step_ab6.txt
   done
 done

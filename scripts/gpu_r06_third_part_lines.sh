@@ -9,10 +9,10 @@ import sys, json
 for line in sys.stdin:
     if line.startswith('{'):
         d = json.loads(line); print('$1', d['value'], d['ms_per_step'], d['ppo_update_ms'])"; }
-python bench.py 2>/dev/null | tail -1 > $O/bench_line.json
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_line.json
 python -c "import json;d=json.load(open('$O/bench_line.json'));print('bench', d['value'], d['ms_per_step'], d['ppo_update_ms'], d['roofline']['frac'], d['cpu_baseline']['value'])"
-for i in 1 2 3; do python bench.py $B 2>/dev/null | tail -1; done | brief repeat | tee $O/bench_repeats.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_line_driver_flags.json
+for i in 1 2 3; do python bench.py --full $B 2>/dev/null | tail -1; done | brief repeat | tee $O/bench_repeats.txt
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_line_driver_flags.json
 python -c "import json;d=json.load(open('$O/bench_line_driver_flags.json'));print('driver flags', d['value'], d['ms_per_step'], d['ppo_update_ms'])" | tee -a $O/bench_repeats.txt
 rm -rf gpurun_out/r06_one_rank; bash scripts/gpu_r06_one_rank.sh > $O/one_rank.log 2>&1; cp gpurun_out/r06_one_rank/* $O/; cat $O/bench_one_rank.txt | cut -c1-90
 bash scripts/gpu_profile.sh r06third/prof --steps 20 --warmup 6 > $O/gpu_profile.log 2>&1; tail -4 $O/gpu_profile.log | cut -c1-200

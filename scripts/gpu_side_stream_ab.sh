@@ -8,8 +8,8 @@ B="--no-cpu-baseline --no-kernel-pass --no-scale-pass --no-env-ab --steps 50 --w
 brief() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['ms_per_step'], 'ms/it, update', d['ppo_update_ms'], 'ms,', round(d['value']/1e6,2), 'M env-steps/s')"; }
 TR="python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1"
 for i in 1 2 3 4; do
-  CUSRL_SIDE_STREAM_PRIORITY=1 python $R/bench.py $B 2>/dev/null | brief "single process, high-priority draw stream   :" | tee -a $OUT/ab.txt
-  python $R/bench.py $B 2>/dev/null | brief "single process, normal-priority draw stream :" | tee -a $OUT/ab.txt
-  CUSRL_SIDE_STREAM_PRIORITY=1 $TR --master-port 2971$i $R/bench.py --gpus 1 $B 2>/dev/null | tail -1 | brief "one rank, high-priority draw stream         :" | tee -a $OUT/ab.txt
-  $TR --master-port 2972$i $R/bench.py --gpus 1 $B 2>/dev/null | tail -1 | brief "one rank, normal-priority draw stream       :" | tee -a $OUT/ab.txt
+  CUSRL_SIDE_STREAM_PRIORITY=1 python $R/bench.py --full $B 2>/dev/null | brief "single process, high-priority draw stream   :" | tee -a $OUT/ab.txt
+  python $R/bench.py --full $B 2>/dev/null | brief "single process, normal-priority draw stream :" | tee -a $OUT/ab.txt
+  CUSRL_SIDE_STREAM_PRIORITY=1 $TR --master-port 2971$i $R/bench.py --full --gpus 1 $B 2>/dev/null | tail -1 | brief "one rank, high-priority draw stream         :" | tee -a $OUT/ab.txt
+  $TR --master-port 2972$i $R/bench.py --full --gpus 1 $B 2>/dev/null | tail -1 | brief "one rank, normal-priority draw stream       :" | tee -a $OUT/ab.txt
 done
