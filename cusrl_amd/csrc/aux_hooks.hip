@@ -37,8 +37,20 @@ constexpr int kPrepMaxC = 128;
 constexpr int kPrepMaxBlocks = 64;
 constexpr int kPrepItems = 8;  // elements per thread and tensor
 
-// workspace layout (doubles): [P][2 tensors][C][2] partial sums, then the snapshot: mean[C], var[C], count
+// workspace layout (doubles): [P][2 tensors][C][2] partial sums, then the snapshot: mean[C], var[C], count, then the
+// pivots: agent[C], expert[C].  The sums are of x - pivot (row 0's agent / expert value of the channel, as in
+// masked_col_stats_kernel): no cancellation of E[x^2] - E[x]^2 when |mean| >> std.
 __device__ __forceinline__ int64_t prep_snapshot_offset(int P, int C) { return int64_t(P) * 2 * C * 2; }
+
+// row 0's value of channel c of the agent rows and of the expert rows
+__device__ __forceinline__ void prep_pivots(const float *__restrict__ state, const float *__restrict__ next_state,
+                                            const int32_t *__restrict__ columns, int K, const float *__restrict__ agent_raw,
+                                            const float *__restrict__ dataset, const int64_t *__restrict__ indices,
+                                            const float *__restrict__ expert_raw, int C, int c, double &pa, double &pe) {
+    const int k = c < K ? c : c - K;
+    pa = double(agent_raw ? agent_raw[c] : (c < K ? state : next_state)[columns ? columns[k] : k]);
+    pe = double(expert_raw ? expert_raw[c] : dataset[indices[0] * C + c]);
+}
 
 __global__ __launch_bounds__(kBlock) void amp_assemble_kernel(
     const float *__restrict__ state, const float *__restrict__ next_state, int state_pitch,
@@ -56,6 +68,8 @@ __global__ __launch_bounds__(kBlock) void amp_assemble_kernel(
         const int k = c < K ? c : c - K;
         const int col = agent_raw ? 0 : (columns ? columns[k] : k);
         const float *__restrict__ side = c < K ? state : next_state;
+        double pa, pe;
+        prep_pivots(state, next_state, columns, K, agent_raw, dataset, indices, expert_raw, C, c, pa, pe);
         // rounds of kPrepItems elements: every index, then every row element is requested before the first store (the
         // launch is a chain of dependent memory round trips: index -> dataset row -> store); out-of-range items are clamped
         for (int i0 = tid; i0 < E; i0 += stride * kPrepItems) {
@@ -81,8 +95,9 @@ __global__ __launch_bounds__(kBlock) void amp_assemble_kernel(
                 if (i < E) {
                     agent_out[i] = a[j];
                     expert_out[i] = e[j];
-                    sa += double(a[j]), qa += double(a[j]) * double(a[j]);
-                    se += double(e[j]), qe += double(e[j]) * double(e[j]);
+                    const double da = double(a[j]) - pa, de = double(e[j]) - pe;
+                    sa += da, qa += da * da;
+                    se += de, qe += de * de;
                 }
             }
         }
@@ -102,7 +117,11 @@ __global__ __launch_bounds__(kBlock) void amp_assemble_kernel(
     }
     if (blockIdx.x == 0) {  // the statistics every block of launch B merges into (nothing in THIS launch writes them)
         double *snap = work + prep_snapshot_offset(int(gridDim.x), C);
-        for (int c = threadIdx.x; c < C; c += kBlock) snap[c] = double(mean[c]), snap[C + c] = double(var[c]);
+        for (int c = threadIdx.x; c < C; c += kBlock) {
+            snap[c] = double(mean[c]), snap[C + c] = double(var[c]);
+            prep_pivots(state, next_state, columns, K, agent_raw, dataset, indices, expert_raw, C, c, snap[2 * C + 1 + c],
+                        snap[3 * C + 1 + c]);
+        }
         if (threadIdx.x == 0) snap[2 * C] = *count;
     }
 }
@@ -138,8 +157,8 @@ __global__ __launch_bounds__(kBlock) void amp_normalize_kernel(const double *__r
         for (int which = 0; which < 2; ++which) {
             double s = 0.0, q = 0.0;
             for (int g = 0; g < groups; ++g) s += fold[g * C + c][2 * which], q += fold[g * C + c][2 * which + 1];
-            const double n = double(rows), bm = s / n;
-            double bv = q / n - bm * bm;
+            const double n = double(rows), d = s / n, bm = snap[2 * C + 1 + which * C + c] + d;
+            double bv = q / n - d * d;
             if (bv < 0.0) bv = 0.0;
             const float batch_mean = float(bm), batch_var = float(bv);
             const double w_sum = running + n;
@@ -398,7 +417,7 @@ static int prep_blocks(int64_t elements) {
 
 extern "C" int64_t cusrl_amp_prepare_workspace(int64_t N, int64_t C) {
     if (N <= 0 || C <= 0) return 0;
-    return int64_t(prep_blocks(N * C)) * 2 * C * 2 + 2 * C + 1;  // doubles
+    return int64_t(prep_blocks(N * C)) * 2 * C * 2 + 4 * C + 1;  // doubles
 }
 
 extern "C" int cusrl_amp_prepare(const float *state, const float *next_state, int64_t state_pitch, const int32_t *columns,

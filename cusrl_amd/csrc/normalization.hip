@@ -8,6 +8,9 @@ namespace cusrl {
 constexpr int kRmsMaxBlocks = 256;
 
 // partials[block][c][{sum, sumsq}] for c < C, partials[block][C][0] = number of selected rows in this block's rows.
+// The sums are of x - x[0][c] (row 0's value of the channel, selected or not, the pivot every block reads): shifted sums
+// keep q / n - (s / n)^2 free of the cancellation of E[x^2] - E[x]^2 when |mean| >> std, and a constant channel exact.
+// C < kBlock: lanes keep one channel each (below); C >= kBlock: masked_col_stats_wide_kernel.
 __global__ __launch_bounds__(kBlock) void masked_col_stats_kernel(const float *__restrict__ x,
                                                                   const uint8_t *__restrict__ mask, int64_t rows, int C,
                                                                   double *__restrict__ partials) {
@@ -16,11 +19,12 @@ __global__ __launch_bounds__(kBlock) void masked_col_stats_kernel(const float *_
     const int64_t stride = threads / C * C;
     const int64_t tid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
     const int64_t E = rows * C;
+    const double pivot = double(x[tid % C]);  // rows >= 1 when this kernel runs
     double sum = 0.0, sumsq = 0.0, count = 0.0;
     for (int64_t i = tid < stride ? tid : E; i < E; i += stride) {
         const int64_t row = i / C;
         if (!mask || mask[row]) {
-            const double v = double(x[i]);
+            const double v = double(x[i]) - pivot;  // exact: the difference of two floats fits a double
             sum += v;
             sumsq += v * v;
             count += 1.0;
@@ -74,45 +78,80 @@ __global__ __launch_bounds__(kBlock) void masked_col_stats_kernel(const float *_
     }
 }
 
+// C >= kBlock: block b takes rows b, b + P, ... and its lanes walk the row in windows of kBlock adjacent channels
+// (coalesced), each lane summing one channel of the window over the block's rows; same partials layout and pivot.
+__global__ __launch_bounds__(kBlock) void masked_col_stats_wide_kernel(const float *__restrict__ x,
+                                                                       const uint8_t *__restrict__ mask, int64_t rows,
+                                                                       int C, double *__restrict__ partials) {
+    double *out = partials + int64_t(blockIdx.x) * (C + 1) * 2;
+    for (int c = threadIdx.x; c < C; c += kBlock) {
+        const double pivot = double(x[c]);
+        double sum = 0.0, sumsq = 0.0, count = 0.0;
+        for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+            if (!mask || mask[row]) {
+                const double v = double(x[row * C + c]) - pivot;
+                sum += v;
+                sumsq += v * v;
+                count += 1.0;
+            }
+        }
+        out[c * 2] = sum;
+        out[c * 2 + 1] = sumsq;
+        if (c == 0) {
+            out[C * 2] = count;
+            out[C * 2 + 1] = 0.0;
+        }
+    }
+}
+
 // One block folds the P block partials: the C + 1 columns (C channels + the row count) are spread over the whole block,
 // kBlock / (C + 1) lanes per column each taking every G-th partial, so the serial chain is P / G fp64 loads long instead
-// of P (P = 24 .. 256; as a single loop per channel this launch was 15 us inside every captured env step).
+// of P (P = 24 .. 256; as a single loop per channel this launch was 15 us inside every captured env step).  C >= kBlock:
+// windows of kBlock - 1 channels, each with the count column (re-folded in the same order, so the same n every window).
 __global__ __launch_bounds__(kBlock) void masked_stats_finalize_kernel(const double *__restrict__ partials, int P, int C,
+                                                                       const float *__restrict__ x,
                                                                        float *__restrict__ mean, float *__restrict__ var,
                                                                        double *__restrict__ count) {
     __shared__ double folded[kBlock][2];
-    const int columns = C + 1;            // C < kBlock (checked by the entry point)
-    const int groups = kBlock / columns;  // >= 1
+    const int width = C < kBlock ? C : kBlock - 1;  // channels per window
+    const int columns = width + 1;                  // + the count column
+    const int groups = kBlock / columns;            // >= 1
     const int column = threadIdx.x % columns, group = threadIdx.x / columns;
-    double s = 0.0, q = 0.0;
-    if (group < groups) {
-        for (int p = group; p < P; p += groups) {
-            const double2 v = reinterpret_cast<const double2 *>(partials)[int64_t(p) * columns + column];
-            s += v.x;
-            q += v.y;
+    for (int c0 = 0; c0 < C; c0 += width) {
+        const int w = C - c0 < width ? C - c0 : width;
+        const int source = column < width ? c0 + column : C;  // partial column this lane folds
+        double s = 0.0, q = 0.0;
+        if (group < groups && (column < w || column == width)) {
+            for (int p = group; p < P; p += groups) {
+                const double2 v = reinterpret_cast<const double2 *>(partials)[int64_t(p) * (C + 1) + source];
+                s += v.x;
+                q += v.y;
+            }
         }
-    }
-    folded[threadIdx.x][0] = s;
-    folded[threadIdx.x][1] = q;
-    __syncthreads();
-    if (threadIdx.x < C) {
-        double n = 0.0;
-        s = q = 0.0;
-        for (int g = 0; g < groups; ++g) {
-            s += folded[g * columns + threadIdx.x][0];
-            q += folded[g * columns + threadIdx.x][1];
-            n += folded[g * columns + C][0];
+        __syncthreads();  // the previous window's lanes have read `folded`
+        folded[threadIdx.x][0] = s;
+        folded[threadIdx.x][1] = q;
+        __syncthreads();
+        if (int(threadIdx.x) < w) {
+            const int c = c0 + threadIdx.x;
+            double n = 0.0;
+            s = q = 0.0;
+            for (int g = 0; g < groups; ++g) {
+                s += folded[g * columns + threadIdx.x][0];
+                q += folded[g * columns + threadIdx.x][1];
+                n += folded[g * columns + width][0];
+            }
+            if (n > 0.0) {
+                const double d = s / n;  // mean - pivot
+                const double v = q / n - d * d;  // population variance (correction = 0)
+                mean[c] = float(double(x[c]) + d);
+                var[c] = float(v < 0.0 ? 0.0 : v);
+            } else {
+                mean[c] = 0.0f;
+                var[c] = 1.0f;
+            }
+            if (c == 0) *count = n;
         }
-        if (n > 0.0) {
-            const double m = s / n;
-            const double v = q / n - m * m;  // population variance (correction = 0)
-            mean[threadIdx.x] = float(m);
-            var[threadIdx.x] = float(v < 0.0 ? 0.0 : v);
-        } else {
-            mean[threadIdx.x] = 0.0f;
-            var[threadIdx.x] = 1.0f;
-        }
-        if (threadIdx.x == 0) *count = n;
     }
 }
 
@@ -186,16 +225,20 @@ extern "C" int cusrl_masked_col_stats(const float *x, const uint8_t *mask, int64
                                       float *batch_mean, float *batch_var, double *batch_count, void *stream) {
     if (rows < 0 || C <= 0) return CUSRL_E_INVALID;
     if (!partials || !batch_mean || !batch_var || !batch_count || (rows > 0 && !x)) return CUSRL_E_INVALID;
-    if (C >= kBlock) return CUSRL_E_UNSUPPORTED;
+    if (C >= (int64_t(1) << 30)) return CUSRL_E_UNSUPPORTED;  // int channel offsets in the partials
     hipStream_t s = as_stream(stream);
     const int64_t P = rows == 0 ? 0 : cusrl_masked_stats_num_partials(rows, C);
     if (P > 0) {
-        hipLaunchKernelGGL(masked_col_stats_kernel, dim3(uint32_t(P)), dim3(kBlock), 0, s, x, mask, rows, int(C),
-                           partials);
+        if (C < kBlock)
+            hipLaunchKernelGGL(masked_col_stats_kernel, dim3(uint32_t(P)), dim3(kBlock), 0, s, x, mask, rows, int(C),
+                               partials);
+        else
+            hipLaunchKernelGGL(masked_col_stats_wide_kernel, dim3(uint32_t(P)), dim3(kBlock), 0, s, x, mask, rows,
+                               int(C), partials);
         if (int rc = launch_status()) return rc;
     }
-    hipLaunchKernelGGL(masked_stats_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(P), int(C), batch_mean,
-                       batch_var, batch_count);
+    hipLaunchKernelGGL(masked_stats_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(P), int(C), x,
+                       batch_mean, batch_var, batch_count);
     return launch_status();
 }
 

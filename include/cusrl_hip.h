@@ -586,7 +586,9 @@ int64_t cusrl_adam_step_normed_workspace_bytes(void);
  * cusrl/nn/utils/normalization.py:15-50 `mean_var_count` of x [rows, C] restricted to rows with mask != 0 (mask may
  * be NULL = all rows; replaces the host-synchronising boolean-mask select of hook/mdp/observation.py:206-208):
  * batch_mean[C], batch_var[C] (population variance, correction = 0), batch_count (device double[1]);
- * an empty selection yields mean 0, var 1, count 0 like the reference.
+ * an empty selection yields mean 0, var 1, count 0 like the reference.  Any C < 2^30 (C >= 256: a second partials
+ * kernel whose lanes walk a row in windows of 256 channels); the sums are shifted by row 0's value of each channel, so
+ * the variance does not cancel when |mean| >> std and a constant channel gives var 0 exactly.
  * partials: double[cusrl_masked_stats_num_partials(rows, C)][C + 1][2] workspace. */
 int cusrl_masked_col_stats(const float *x, const uint8_t *mask, int64_t rows, int64_t C, double *partials,
                            float *batch_mean, float *batch_var, double *batch_count, void *stream);

@@ -420,6 +420,23 @@ def reward_shaping(reward, scale=1.0, shift=0.0, lower=None, upper=None):
     return out.astype(np.float32)
 
 
+def masked_mean_var(x, mask=None):
+    """Mean, population variance and count of the rows of ``x [..., C]`` whose ``mask`` entry is nonzero, two-pass in
+    float64: ``mean_var_count`` (cusrl/nn/utils/normalization.py:15-50, ``torch.var_mean(correction=0)`` at :49) applied
+    to the ``observation[indices]`` select of cusrl/hook/mdp/observation.py:210-212.  An empty selection gives
+    (0, 1, 0) like normalization.py:41-44.  Returns ``(mean, var, count)``, float64 arrays and an int."""
+    x = np.asarray(x, np.float64)
+    x = x.reshape(-1, x.shape[-1])
+    if mask is not None:
+        x = x[np.asarray(mask).reshape(-1) != 0]
+    n = x.shape[0]
+    if n == 0:
+        return np.zeros(x.shape[1]), np.ones(x.shape[1]), 0
+    mean = x.sum(0) / n
+    d = x - mean
+    return mean, (d * d).sum(0) / n, n
+
+
 def running_mean_std_update(mean, var, count, batch, epsilon=1e-8, max_count=None):
     """One ``RunningMeanStd.update(batch)`` (cusrl/nn/layer/rms.py:140-167 with cusrl/nn/utils/normalization.py:15-50,80-93):
     population statistics of the batch rows, merged with weights count : rows; fp32 like the reference's tensors.
@@ -431,9 +448,20 @@ def running_mean_std_update(mean, var, count, batch, epsilon=1e-8, max_count=Non
     b64 = batch.astype(np.float64)
     batch_mean = b64.mean(0).astype(np.float32)
     batch_var = b64.var(0).astype(np.float32)  # torch.var_mean(correction=0)
+    return rms_merge(mean, var, None, count, batch_mean, batch_var, n, epsilon, max_count)
+
+
+def rms_merge(mean, var, std, count, batch_mean, batch_var, batch_count, epsilon=1e-8, max_count=None):
+    """The merge half of ``RunningMeanStd.update_from_stats`` (normalization.py:80-93 ``merge_mean_var_``, rms.py:163-167)
+    in the reference's fp32 operation order, from given batch statistics; a zero ``batch_count`` returns the state
+    unchanged.  Returns ``(mean, var, std, count)``."""
+    if batch_count == 0:
+        return mean, var, std, count
+    mean, var = np.asarray(mean, np.float32), np.asarray(var, np.float32)
+    batch_mean, batch_var, n = np.asarray(batch_mean, np.float32), np.asarray(batch_var, np.float32), batch_count
     w_sum = count + n
-    w_old, w_new = np.float32(count / w_sum), np.float32(n / w_sum)
-    delta = batch_mean - np.asarray(mean, np.float32)
+    w_new = np.float32(n / w_sum)
+    delta = batch_mean - mean
     new_mean = (mean + delta * w_new).astype(np.float32)
     new_var = (var + ((batch_var - var) * w_new + delta * delta * np.float32((count / w_sum) * (n / w_sum)))).astype(np.float32)
     total = count + n

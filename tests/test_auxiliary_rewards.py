@@ -199,6 +199,21 @@ def test_reward_shaping_restatement_matches_the_reference_hook_formula():
 def test_amp_prepare_kernel_vs_oracle(rows, state_dim, columns):
     """cusrl_amp_prepare — assembly, dataset rows, two statistics updates, two normalisations in ONE launch — against the
     numpy restatement over three consecutive steps (the running statistics carry over)."""
+    check_amp_prepare(rows, state_dim, columns)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows,state_dim,columns,offset,spread,max_count", [
+    (4096, 48, slice(6), 1e3, 1e-2, None),  # |mean| >> std: E[x^2] - E[x]^2 cancels in fp64 sums of raw values
+    (300, 16, [15, 2, 7], -2e4, 0.5, None),
+    (4096, 48, slice(6), 0.0, 1.0, 5000),  # the count saturates after the second update
+    (1000, 64, slice(64), 1e3, 1e-2, 1500),  # C = 128, the widest transition the fused kernel takes
+])
+def test_amp_prepare_kernel_vs_oracle_offset_data_and_max_count(rows, state_dim, columns, offset, spread, max_count):
+    check_amp_prepare(rows, state_dim, columns, offset, spread, max_count)
+
+
+def check_amp_prepare(rows, state_dim, columns, offset=0.0, spread=1.0, max_count=None):
     import oracle
     from cusrl_amd import ops
     from cusrl_amd.nn.rms import RunningMeanStd
@@ -207,17 +222,27 @@ def test_amp_prepare_kernel_vs_oracle(rows, state_dim, columns):
     rng = np.random.default_rng(rows)
     picked = np.arange(state_dim)[columns]
     C = 2 * len(picked)
-    dataset = rng.standard_normal((1000, C)).astype(np.float32) * 3 + 1
-    rms = RunningMeanStd(C).to(dev)
+    if offset == 0.0 and spread == 1.0:
+        dataset = rng.standard_normal((1000, C)).astype(np.float32) * 3 + 1
+    else:
+        dataset = (offset + spread * rng.standard_normal((1000, C))).astype(np.float32)
+    rms = RunningMeanStd(C, max_count=max_count).to(dev)
     mean, var, count = np.zeros(C, np.float32), np.ones(C, np.float32), 0
+    if offset != 0.0 or spread != 1.0:
+        # a normaliser that has already seen data of this kind: the batch variance is no longer swamped by the initial
+        # var = 1 (whose fp32 merge would round any batch variance ~1e-4 to a multiple of 6e-8)
+        mean, var, count = np.full(C, offset, np.float32), np.full(C, spread * spread, np.float32), 10000
+        rms.mean.copy_(torch.from_numpy(mean)), rms.var.copy_(torch.from_numpy(var))
+        rms.count = count
     prefix = len(picked) if np.array_equal(picked, np.arange(len(picked))) else None
     cols = None if prefix is not None else torch.as_tensor(picked, dtype=torch.int32, device=dev)
     for step in range(3):
-        state, nxt = rng.standard_normal((rows, state_dim)).astype(np.float32), rng.standard_normal((rows, state_dim)).astype(np.float32)
+        state, nxt = (offset + spread * rng.standard_normal((2, rows, state_dim))).astype(np.float32)
         picks = rng.integers(0, 1000, rows)
         agent, expert = ops.amp_prepare(rms, state=torch.from_numpy(state).to(dev), next_state=torch.from_numpy(nxt).to(dev), columns=cols,
                                         width=prefix, dataset=torch.from_numpy(dataset).to(dev), indices=torch.from_numpy(picks).to(dev))
-        ref_agent, ref_expert, mean, var, std, count = oracle.amp_prepare(state, nxt, picked, dataset, picks, mean, var, count)
+        ref_agent, ref_expert, mean, var, std, count = oracle.amp_prepare(state, nxt, picked, dataset, picks, mean, var, count,
+                                                                          max_count=max_count)
         np.testing.assert_allclose(agent.cpu().numpy(), ref_agent, rtol=1e-5, atol=2e-5)  # 1e-5 rel fp32
         np.testing.assert_allclose(expert.cpu().numpy(), ref_expert, rtol=1e-5, atol=2e-5)
         np.testing.assert_allclose(rms.mean.cpu().numpy(), mean, rtol=1e-5, atol=1e-6)
