@@ -287,7 +287,7 @@ class FusedPpoObjective:
             cached = composite._fusion_cache = (key, cls.mode(composite))
         if cached[1] is None:
             return None
-        context = cls(unit_grad=not agent.grad_scaler_enabled, owner=getattr(agent, "_deferred_loss_owner", None),
+        context = cls(unit_grad=not agent.grad_scaler_enabled, owner=agent.step_context.deferred_loss_owner,
                       split=cached[1] == "split")
         agent._fused_objective = context
         return context

@@ -233,17 +233,17 @@ class ValueLoss(Hook):
         memory, done = batch.get("critic_memory"), batch["done"]
         fused = FusedPpoObjective.current(self)
         # (split mode: a further hook may read `curr_value` on the main stream right behind this one — no second stream)
-        branch = getattr(self.agent, "_critic_stream", None) if fused is not None and not fused.split else None
+        branch = self.agent.step_context.critic_stream if fused is not None and not fused.split else None
         if branch is not None:
             # inside a minibatch step that is (being) captured: the critic's forward — and, because autograd replays
             # every node on the stream its forward ran on, its backward — goes to a second stream.  The two networks
             # share nothing until their losses are summed, so the captured graph gets two independent branches whose
             # latency-bound small kernels fill the gaps of the other branch's GEMM tails.
             main = torch.cuda.current_stream()
-            separate = getattr(self.agent, "separate_value_root", False) and fused.unit_grad
+            separate = self.agent.separate_value_root and fused.unit_grad
             if separate:  # (read on the main stream, in front of the fork: a lazy batch gathers a field where it is first touched)
                 ret, old_value = batch["return"], (batch["value"] if self.loss_clip is not None else None)
-            if not (separate and getattr(self.agent, "_batch_on_branch", False)):
+            if not (separate and self.agent.step_context.batch_on_branch):
                 branch.wait_stream(main)  # the gather of `state` was issued on `main`
             # (else: a step inside a whole-update graph whose predecessor left the streams unjoined — the critic's parameters were
             # stepped, and this step's rows gathered, on `branch` itself: it carries on without meeting the main stream)

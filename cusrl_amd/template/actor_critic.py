@@ -13,7 +13,8 @@ from __future__ import annotations
 
 import os
 
-from collections.abc import Iterable, Mapping
+from collections.abc import Callable, Iterable, Mapping, Sequence
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Any
 
@@ -27,9 +28,9 @@ from cusrl_amd.template.environment import EnvironmentSpec
 from cusrl_amd.template.hook import Hook, HookComposite
 from cusrl_amd.template.optimizer import OptimizerFactory, build_optimizer
 from cusrl_amd.utils.config import CONFIG
-from cusrl_amd.utils.distributed import FlatGradients, broadcast_parameters, reduce_gradients
+from cusrl_amd.utils.distributed import FlatGradients, UnjoinedStep, broadcast_parameters, reduce_gradients
 
-__all__ = ["ActorCritic", "ActorCriticFactory", "HookList"]
+__all__ = ["ActorCritic", "ActorCriticFactory", "HookList", "StepContext", "StepPlan", "plan_step"]
 
 
 def _hashable(value):
@@ -46,6 +47,92 @@ def _hashable(value):
             return frozen
         except TypeError:
             return repr(value)
+
+
+ONE_PASS, JOINED, UNJOINED, SPLIT = "one pass", "joined", "unjoined", "split"
+
+
+@dataclass(frozen=True)
+class StepPlan:
+    """How a minibatch step differentiates and steps its parameters (:func:`plan_step`).  ``mode``, for a step whose loss has a
+    summand of the critic's own, evaluated on the critic's stream (hook/on_policy/value.py):
+    ``ONE_PASS`` — the critic shares parameters: the streams join, one backward over every summand;
+    ``JOINED`` — the critic's summand differentiated on its stream, the others' on the main one, met once in front of ONE
+    assembly; ``UNJOINED`` — the same, but inside a whole-update graph (``StepContext.unjoined``) each window is assembled
+    and stepped (``FlatAdam``) where its backward ran, and the streams do not meet; ``SPLIT`` — a multi-rank job's per-network
+    split (``CONFIG.split_gradient_allreduce``): each window averaged as soon as it is assembled, with or without that summand."""
+
+    mode: str
+    critic_ids: tuple[int, ...] = ()  # the windows' parameters (indices into FlatGradients.params): the critic's ...
+    other_ids: tuple[int, ...] = ()  # ... and everybody else's
+    ranges: tuple[tuple[int, int], tuple[int, int]] | None = None  # UNJOINED: element ranges, the others' and the critic's
+    reduce_windows: tuple[tuple[int, int], ...] = ()  # SPLIT: element ranges averaged one by one, the critic's first
+
+
+def _stock_optim(hook: Hook) -> bool:
+    """Does ``hook`` leave the gradients alone between the backward and the step?  The stock clipping of the default group
+    does: it hands its coefficient to the flat Adam step (``FlatAdam.defer_clip``)."""
+    from cusrl_amd.hook.on_policy.gradient_clipping import GradientClipping
+
+    if type(hook).post_optim is not Hook.post_optim:
+        return False
+    return type(hook).pre_optim is Hook.pre_optim or (isinstance(hook, GradientClipping) and not hook.groups)
+
+
+def plan_step(critic_ids: Sequence[int] | None, offsets: Sequence[int], size: int, *, multi_rank: bool = False,
+              split_allreduce: bool = False, native_comm: bool = False, branch_stream: bool = False, flat_adam: bool = False,
+              hooks: Iterable[Hook] = (), two_window: bool = True) -> StepPlan:
+    """The :class:`StepPlan` of a flat gradient buffer whose parameters start at element ``offsets`` (``size`` in all).
+    ``critic_ids``: the critic's parameters, None when it shares one with the actor or a hook; ``native_comm``: the C-ABI
+    communicator; ``branch_stream``: the critic's stream exists (``compile=True``); ``hooks``: the active hooks;
+    ``two_window``: the ``CUSRL_TWO_WINDOW_STEP`` switch.
+
+    The split route needs the critic's parameters in one run.  A step may stay unjoined when each network's parameters form
+    one run, no hook but the stock clipping comes between backward and step (a ``pre_optim`` could read the window on the
+    other stream) and, with several ranks, the all-reduce can be captured where it belongs: ONE collective over the whole
+    buffer through the C-ABI communicator, behind both assemblies (``reduce_gradients``)."""
+    if not critic_ids:
+        return StepPlan(ONE_PASS)
+    critic = tuple(critic_ids)
+    others = tuple(i for i in range(len(offsets)) if i not in set(critic))
+
+    def spans(ids):  # element ranges of the runs of consecutive parameters in `ids` (alignment padding included)
+        runs = []
+        for i in ids:
+            if runs and i == runs[-1][-1] + 1:
+                runs[-1].append(i)
+            else:
+                runs.append([i])
+        return [(offsets[run[0]], offsets[run[-1] + 1] if run[-1] + 1 < len(offsets) else size) for run in runs]
+
+    critic_spans, other_spans = spans(critic), spans(others)
+    if multi_rank and split_allreduce and branch_stream and others and len(critic_spans) == 1:
+        return StepPlan(SPLIT, critic, others, reduce_windows=tuple(critic_spans + other_spans))
+    if (two_window and flat_adam and len(critic_spans) == len(other_spans) == 1
+            and not (multi_rank and (split_allreduce or not native_comm)) and all(_stock_optim(hook) for hook in hooks)):
+        return StepPlan(UNJOINED, critic, others, ranges=(other_spans[0], critic_spans[0]))
+    return StepPlan(JOINED, critic, others)
+
+
+@dataclass
+class StepContext:
+    """What the captured step body being issued (template/graphs.py) tells the hooks and ``ActorCritic._backward``.  Every
+    field holds its default outside of one; :meth:`set` installs values for the duration of a body."""
+
+    critic_stream: torch.cuda.Stream | None = None  # the critic's forward, value term and backward run there (ValueLoss)
+    deferred_loss_owner: Any = None  # the fused objective runs without its finalize launch (ops.DeferredLoss)
+    branch_tail: Callable[[], None] | None = None  # issued once, at the tail of the critic's branch (the next step's gather)
+    unjoined: list[UnjoinedStep] | None = None  # a step may leave its streams unjoined and files its record here (None: it joins)
+    batch_on_branch: bool = False  # the step's rows were gathered on the critic's stream, which need not meet the main one
+
+    @contextmanager
+    def set(self, **fields):
+        saved = {name: getattr(self, name) for name in fields}
+        self.__dict__.update(fields)
+        try:
+            yield self
+        finally:
+            self.__dict__.update(saved)
 
 
 class HookList(list):
@@ -151,11 +238,7 @@ class ActorCritic(Agent):
         self._graphed_act = None
         self._graphed_steps: dict[tuple, Any] = {}
         self._graphed_epochs = None
-        self._branch_tail = None  # a callable GraphedEpochs wants issued at the tail of the running step's critic branch
-        # set by GraphedEpochs around the step bodies of a whole-update / whole-epoch capture: a step may leave its two streams
-        # unjoined (they meet behind the LAST body); `_batch_on_branch`: the running step's rows were gathered on the critic's stream
-        self._unjoined_steps = False
-        self._batch_on_branch = False
+        self.step_context = StepContext()
         self._while_waiting = None  # host work to issue while a pre_update hook waits for the device (run_while_waiting)
         self._minibatches_done = None  # event behind the last minibatch step of the previous update (its index rows may be redrawn)
         self._graph_key_reads = 0
@@ -181,8 +264,6 @@ class ActorCritic(Agent):
             self.defer_loss_finalize = os.environ.get("CUSRL_DEFER_LOSS_FINALIZE", "1") != "0"
             self._graphed_act = GraphedAct(self)
         self.flat_gradients: FlatGradients | None = None
-        self._split_plan = False  # per-network split of the backward: not looked at yet (None = does not apply)
-        self._networks = False  # critic / other parameter windows: not looked at yet (None = they share parameters)
         self._unit_grads: dict[tuple, torch.Tensor] = {}
         # the value term of the stock composition as its own launch + root on the critic's branch of a captured step (A/B switch)
         self._separate_value_term = os.environ.get("CUSRL_SEPARATE_VALUE_TERM", "1") != "0"
@@ -427,7 +508,7 @@ class ActorCritic(Agent):
         """Gradients of ``loss`` into ``p.grad``.  With the flat gradient buffer the per-parameter gradients — and the
         unsummed slabs of the split-batch weight-gradient GEMMs — are written into it by ONE kernel (no memset, no 13
         accumulate launches, no per-layer sum(0)); otherwise this is the
-        reference's ``scaled_loss.backward()`` (actor_critic.py:311-312)."""
+        reference's ``scaled_loss.backward()`` (actor_critic.py:311-312).  The form of the step: :func:`plan_step`."""
         flat = self.flat_gradients
         roots = list(loss) if isinstance(loss, (list, tuple)) else [loss]  # several roots = the summands of the loss
         if len(roots) > 1:  # a constant summand (a hook returning a plain number) changes no gradient
@@ -438,145 +519,101 @@ class ActorCritic(Agent):
                 total = total + term
             self.grad_scaler.scale(total).backward()
             return
+
+        def differentiate(roots, units, ids, retain=False):
+            with collect_split_weight_grads() as slabs:
+                grads = torch.autograd.grad(roots, [flat.params[i] for i in ids], grad_outputs=units, allow_unused=True,
+                                            retain_graph=retain)
+            return grads, slabs
+
         units = [self._unit_gradient(term) for term in roots]
-        plan = self._split_backward_plan()
+        plan = self.step_plan()
         # a summand evaluated on the critic's stream (hook/on_policy/value.py: the value term of the stock composition)
         branch_root = getattr(loss, "branch", None)
-        networks = self._network_windows() if branch_root is not None else None
-        if branch_root is not None and (networks is None or len(roots) != len(loss)):
+        if branch_root is not None and (plan.mode == ONE_PASS or len(roots) != len(loss)):
             # not differentiable network by network (shared parameters, or a summand was dropped above): join first
             torch.cuda.current_stream().wait_stream(branch_root[1])
             branch_root = None
-        if plan is None and branch_root is not None:
-            # The critic's backward where its forward and its loss ran, the other summands' on the main stream, both issued from
-            # here back to back: neither pass waits for the other (the engine would order a one-pass backward behind the stream
-            # this call is made from), the two streams meet ONCE, in front of the assembly.
-            value_root, branch = branch_root
-            critic_ids, other_ids = networks
-            position = next(i for i, term in enumerate(roots) if term is value_root)
-            others = [term for i, term in enumerate(roots) if i != position]
-            other_units = [unit for i, unit in enumerate(units) if i != position]
-            ranges = self._two_window_ranges() if self._unjoined_steps else None
-            if ranges is not None:
-                # Round 6, inside a whole-update / whole-epoch graph: each network's window of the flat buffer is assembled on the
-                # stream its backward ran on, and the streams do NOT meet — the optimizer steps the two windows where they are
-                # (FlatAdam.step: each behind the other window's assembly, the clipping coefficient needs both).  The rows of the
-                # NEXT minibatch step are gathered in front of the critic's assembly, so the one event the main stream waits for
-                # covers them too.
-                main = torch.cuda.current_stream()
-                flat.absent = []
-                # (several ranks: the rows would be of the un-averaged gradients — reduce_gradients averages the buffer behind
-                # both assemblies, the step launches measure its norm themselves)
-                from cusrl_amd.utils.config import configure_distributed
-
-                multi_rank = configure_distributed()
-                with torch.cuda.stream(branch):
-                    with collect_split_weight_grads() as critic_slabs:
-                        critic_grads = torch.autograd.grad([value_root], [flat.params[i] for i in critic_ids],
-                                                           grad_outputs=[units[position]], allow_unused=True)
-                    tail, self._branch_tail = self._branch_tail, None
-                    if tail is not None:
-                        tail()
-                    branch_sumsq = flat.assemble(critic_grads, critic_slabs, subset=critic_ids, want_sumsq=not multi_rank)
-                    branch_assembled = torch.cuda.Event()
-                    branch_assembled.record(branch)
-                with collect_split_weight_grads() as split_slabs:
-                    other_grads = torch.autograd.grad(others, [flat.params[i] for i in other_ids], grad_outputs=other_units,
-                                                      allow_unused=True)
-                main_sumsq = flat.assemble(other_grads, split_slabs, subset=other_ids, want_sumsq=not multi_rank)
-                main_assembled = torch.cuda.Event()
-                main_assembled.record(main)
-                main_range, branch_range = ranges
-                # (the rows in parameter order: summed as ONE assembly's rows would be — the same norm to the bit)
-                sumsq = (main_sumsq, branch_sumsq) if main_range[0] < branch_range[0] else (branch_sumsq, main_sumsq)
-                flat.split_tail = {"branch": branch, "branch_assembled": branch_assembled, "main_assembled": main_assembled,
-                                   "sumsq": sumsq, "main_range": main_range, "branch_range": branch_range, "reduce": multi_rank}
-                return
-            with torch.cuda.stream(branch):
-                with collect_split_weight_grads() as critic_slabs:
-                    critic_grads = torch.autograd.grad([value_root], [flat.params[i] for i in critic_ids],
-                                                       grad_outputs=[units[position]], allow_unused=True)
-                # the critic's branch ends before the actor's: work that depends on neither — the gather of the NEXT minibatch
-                # step's rows (template/graphs.py GraphedEpochs) — rides at its tail
-                tail, self._branch_tail = self._branch_tail, None
-                if tail is not None:
-                    tail()
-            with collect_split_weight_grads() as split_slabs:
-                other_grads = torch.autograd.grad(others, [flat.params[i] for i in other_ids], grad_outputs=other_units,
-                                                  allow_unused=True)
-            torch.cuda.current_stream().wait_stream(branch)  # the step's one join
-            grads: list = [None] * len(flat.params)
-            for i, grad in zip(critic_ids, critic_grads):
-                grads[i] = grad
-            for i, grad in zip(other_ids, other_grads):
-                grads[i] = grad
-            split_slabs.update(critic_slabs)
-            flat.assemble(grads, split_slabs)
+        if branch_root is None and plan.mode != SPLIT:
+            flat.assemble(*differentiate(roots, units, range(len(flat.params))))
             return
-        if plan is None:
-            with collect_split_weight_grads() as split_slabs:
-                grads = torch.autograd.grad(roots, flat.params, grad_outputs=units, allow_unused=True)
-            flat.assemble(grads, split_slabs)
-            return
-        # Per-network split (CONFIG.split_gradient_allreduce; cusrl/utils/distributed.py:145-172 reduces once, behind the
-        # whole backward): the critic first — its window is assembled and averaged on the branch stream through the second
-        # communicator while the actor's backward, issued right behind, runs on the main stream.  Same autograd nodes, same
-        # kernels, same operands as the one-pass backward; the loss node they share is evaluated by both passes.
+        # The critic's backward on the branch stream, the others' on the main stream, both issued from here back to back: neither
+        # waits for the other (the engine would order a one-pass backward behind the stream this call is made from).  Same
+        # autograd nodes, kernels and operands as the one-pass backward; a loss node both passes share is evaluated by both.
+        # The streams meet once, in front of ONE assembly (JOINED); or not at all, each window assembled and then stepped where
+        # its backward ran (UNJOINED, FlatAdam.step); or each window is averaged over the ranks as soon as it is assembled, the
+        # critic's through the second communicator on the branch stream (SPLIT; cusrl/utils/distributed.py:145-172 reduces
+        # once, behind the whole backward).
         from cusrl_amd.utils import distributed
+        from cusrl_amd.utils.config import configure_distributed
 
-        critic_ids, other_ids, windows = plan
-        main, branch = torch.cuda.current_stream(), self._branch_stream
-        # collectives inside the backward need a route that may be enqueued here: eager, or capturable (the C ABI)
-        inline = not torch.cuda.is_current_stream_capturing() or distributed.native_comm() is not None
-        flat.absent, flat.split_windows = [], windows
-        # The critic's pass and its window's assembly run where the critic's autograd nodes run: on the branch stream when the
-        # step evaluated the critic there (GraphedTrainStep._critic_branch), else on the main stream — gradients are consumed on
-        # the stream whose allocator pool they came from.  Only the all-reduce, which touches nothing but the persistent flat
-        # buffer, always goes to the branch stream.
-        on_branch = getattr(self, "_critic_backward_stream", None) is branch
+        main, branch, context = torch.cuda.current_stream(), self._branch_stream, self.step_context
+        split = plan.mode == SPLIT
+        unjoined = plan.mode == UNJOINED and context.unjoined is not None
+        multi_rank = configure_distributed()
+        want_sumsq = unjoined and not multi_rank  # (several ranks: the step launches measure the averaged norm themselves)
         critic_roots, critic_units, other_roots, other_units = roots, units, roots, units
         if branch_root is not None:  # the value term is a root of its own (evaluated on `branch`): each pass takes its summands
             position = next(i for i, term in enumerate(roots) if term is branch_root[0])
             critic_roots, critic_units = [roots[position]], [units[position]]
             other_roots = [term for i, term in enumerate(roots) if i != position]
             other_units = [unit for i, unit in enumerate(units) if i != position]
-            on_branch = True
-
-        def critic_pass():
-            with collect_split_weight_grads() as slabs:
-                grads = torch.autograd.grad(critic_roots, [flat.params[i] for i in critic_ids], grad_outputs=critic_units,
-                                            allow_unused=True, retain_graph=branch_root is None)
-            flat.assemble(grads, slabs, subset=critic_ids)
-
-        # Two collectives in flight on two streams need two communicators: without the second one (it could not be created, or
-        # the route is torch.distributed's) the critic's window is averaged on the MAIN stream behind the join below — one
-        # communicator is only ever used from one stream at a time.
-        on_branch_comm = inline and distributed.branch_comm() is not None
-
-        def critic_reduce():
+        # (else — the split route — the critic's pass runs where its autograd nodes run: gradients are consumed on the stream
+        # whose allocator pool they came from)
+        on_branch = branch_root is not None or context.critic_stream is branch
+        flat.absent = []
+        if split and on_branch:
+            branch.wait_stream(main)
+        with torch.cuda.stream(branch if on_branch else main):
+            critic_grads, critic_slabs = differentiate(critic_roots, critic_units, plan.critic_ids, retain=branch_root is None)
+            if not split:
+                # the critic's branch ends before the actor's: work that depends on neither — the gather of the NEXT minibatch
+                # step's rows (template/graphs.py GraphedEpochs) — rides at its tail
+                tail, context.branch_tail = context.branch_tail, None
+                if tail is not None:
+                    tail()
+            if split or unjoined:
+                branch_sumsq = flat.assemble(critic_grads, critic_slabs, subset=plan.critic_ids, want_sumsq=want_sumsq)
+            if unjoined:
+                branch_assembled = torch.cuda.Event()
+                branch_assembled.record(branch)
+        if split:
+            # two collectives in flight on two streams need two communicators: without the second one (it could not be created,
+            # or the route is torch.distributed's, which cannot be captured) the critic's window is averaged on the MAIN stream
+            # behind the join below — one communicator is only ever used from one stream at a time
+            inline = not torch.cuda.is_current_stream_capturing() or distributed.native_comm() is not None
+            on_branch_comm = inline and distributed.branch_comm() is not None
+            windows = tuple(flat.buffer[lo:hi] for lo, hi in plan.reduce_windows)
+            if not on_branch:
+                branch.wait_stream(main)
             if on_branch_comm:
-                distributed.branch_comm().allreduce_mean_(windows[0])
-
-        if on_branch:
-            branch.wait_stream(main)
-            with torch.cuda.stream(branch):
-                critic_pass()
-                critic_reduce()
-        else:
-            critic_pass()
-            branch.wait_stream(main)
-            with torch.cuda.stream(branch):
-                critic_reduce()
-        with collect_split_weight_grads() as slabs:
-            grads = torch.autograd.grad(other_roots, [flat.params[i] for i in other_ids], grad_outputs=other_units, allow_unused=True)
-        flat.assemble(grads, slabs, subset=other_ids)
+                with torch.cuda.stream(branch):
+                    distributed.branch_comm().allreduce_mean_(windows[0])
+        other_grads, other_slabs = differentiate(other_roots, other_units, plan.other_ids)
+        if not (split or unjoined):
+            main.wait_stream(branch)  # the step's one join
+            grads: list = [None] * len(flat.params)
+            for i, grad in zip(plan.critic_ids + plan.other_ids, critic_grads + other_grads):
+                grads[i] = grad
+            other_slabs.update(critic_slabs)
+            flat.assemble(grads, other_slabs)
+            return
+        main_sumsq = flat.assemble(other_grads, other_slabs, subset=plan.other_ids, want_sumsq=want_sumsq)
+        if unjoined:
+            main_assembled = torch.cuda.Event()
+            main_assembled.record(main)
+            main_range, branch_range = plan.ranges
+            sumsq = (main_sumsq, branch_sumsq) if main_range < branch_range else (branch_sumsq, main_sumsq)  # parameter order
+            flat.unjoined = UnjoinedStep(branch, branch_assembled, main_assembled, main_range, branch_range, sumsq, multi_rank)
+            context.unjoined.append(flat.unjoined)
+            return
         if inline:
             for window in windows[1:]:
                 distributed.reduce_mean_(window)
         main.wait_stream(branch)
         if inline and not on_branch_comm:
             distributed.reduce_mean_(windows[0])
-        flat.reduced = inline
+        flat.unaveraged_windows = () if inline else windows
 
     def _unit_gradient(self, term: torch.Tensor) -> torch.Tensor:
         """The persistent, registered ones-scalar of ``term``'s dtype and device (no ones_like per step; custom backwards
@@ -587,96 +624,34 @@ class ActorCritic(Agent):
             unit = self._unit_grads[key] = register_unit_gradient(torch.ones((), dtype=term.dtype, device=term.device))
         return unit
 
-    def _network_windows(self):
-        """``(critic parameter indices, the others' indices)`` of the flat gradient buffer when the critic shares no parameter
-        with anything else the optimizer steps (then a summand that reaches the critic alone can be differentiated on its own),
-        else None.  Computed once."""
-        if self._networks is not False:
-            return self._networks
-        self._networks = None
+    def step_plan(self) -> StepPlan:
+        """:func:`plan_step` for this agent as it stands: computed again at every backward (and capture), so that a hook
+        activated since, a changed clipping group or a changed collective route selects its form."""
+        from cusrl_amd.utils import distributed
+        from cusrl_amd.utils.config import CONFIG, configure_distributed
+
         flat = self.flat_gradients
         if flat is None:
-            return None
+            return StepPlan(ONE_PASS)
         critic = {id(p) for p in self.critic.parameters()}
         outside = {id(p) for p in self.actor.parameters()} | {id(p) for p in self.hook.parameters()}
-        critic_ids = [i for i, p in enumerate(flat.params) if id(p) in critic]
-        if critic_ids and not (critic & outside):
-            self._networks = (critic_ids, [i for i, p in enumerate(flat.params) if id(p) not in critic])
-        return self._networks
+        multi_rank = configure_distributed()
+        return plan_step(
+            None if critic & outside else [i for i, p in enumerate(flat.params) if id(p) in critic], flat.offsets,
+            flat.buffer.numel(), multi_rank=multi_rank, split_allreduce=CONFIG.split_gradient_allreduce,
+            native_comm=multi_rank and distributed.native_comm() is not None,
+            branch_stream=getattr(self, "_branch_stream", None) is not None, flat_adam=self.flat_optimizer is not None,
+            hooks=[hook for hook in self.hook if hook._active], two_window=os.environ.get("CUSRL_TWO_WINDOW_STEP", "1") != "0")
 
-    def _two_window_ranges(self):
-        """``(element range of the others' window, of the critic's window)`` of the flat buffers when a minibatch step may leave
-        its two streams unjoined (``_backward`` / ``FlatAdam.step``): one process, the flat Adam step, critic and others each one
-        run of consecutive parameters, nobody but the stock gradient clipping between backward and step (a ``pre_optim`` of
-        another hook could read gradients of the window that lives on the other stream); else None.  Computed once."""
-        cached = getattr(self, "_two_windows", False)
-        if cached is not False:
-            return cached
-        self._two_windows = None
-        from cusrl_amd.hook.on_policy.gradient_clipping import GradientClipping
-        from cusrl_amd.template.hook import Hook
-        from cusrl_amd.utils.config import configure_distributed
-
-        networks, flat = self._network_windows(), self.flat_gradients
-        if networks is None or flat is None or self.flat_optimizer is None:
-            return None
-        if configure_distributed():
-            # several ranks: the step stays unjoined when the all-reduce can be captured where it belongs — ONE collective over
-            # the whole buffer through the C-ABI communicator, on the main stream behind both assemblies (reduce_gradients) —
-            # and the step launches measure the averaged gradients' norm themselves (cusrl_adam_step_normed)
-            from cusrl_amd.utils import distributed
-            from cusrl_amd.utils.config import CONFIG
-
-            if CONFIG.split_gradient_allreduce or distributed.native_comm() is None:
-                return None
-        if os.environ.get("CUSRL_TWO_WINDOW_STEP", "1") == "0":  # A/B switch
-            return None
-        for hook in self.hook:
-            stock = type(hook).pre_optim is Hook.pre_optim and type(hook).post_optim is Hook.post_optim
-            if hook._active and not stock and not (isinstance(hook, GradientClipping) and not hook.groups
-                                                   and type(hook).post_optim is Hook.post_optim):
-                return None
-        try:
-            self._two_windows = (flat.element_range(networks[1]), flat.element_range(networks[0]))
-        except ValueError:
-            self._two_windows = None
-        return self._two_windows
+    @property
+    def _split_plan(self) -> bool:
+        """Does the per-network split of the backward apply (read by bench.py and the distributed tests)?"""
+        return self.step_plan().mode == SPLIT
 
     @property
     def separate_value_root(self) -> bool:
         """May ``ValueLoss`` evaluate its term by its own launch on the critic's stream (a root of its own in ``_backward``)?"""
-        return self._separate_value_term and self._network_windows() is not None
-
-    def _split_backward_plan(self):
-        """``(critic parameter indices, the others' indices, [critic window, other windows ...])`` of the flat gradient buffer
-        when the per-network split of the backward applies — a multi-rank job with ``CONFIG.split_gradient_allreduce``, a
-        GPU agent with a branch stream, critic parameters forming one run of the buffer — else None.  Computed once."""
-        if self._split_plan is not False:
-            return self._split_plan
-        self._split_plan = None
-        from cusrl_amd.utils.config import CONFIG, configure_distributed
-
-        flat = self.flat_gradients
-        if (flat is None or not CONFIG.split_gradient_allreduce or not configure_distributed() or self.device.type != "cuda"
-                or getattr(self, "_branch_stream", None) is None):
-            return None
-        critic = {id(p) for p in self.critic.parameters()}
-        if critic & {id(p) for p in self.actor.parameters()}:
-            return None  # shared parameters: one pass
-        critic_ids = [i for i, p in enumerate(flat.params) if id(p) in critic]
-        other_ids = [i for i, p in enumerate(flat.params) if id(p) not in critic]
-        if not critic_ids or not other_ids or critic_ids != list(range(critic_ids[0], critic_ids[-1] + 1)):
-            return None
-        runs, run = [], [other_ids[0]]
-        for i in other_ids[1:]:
-            if i == run[-1] + 1:
-                run.append(i)
-            else:
-                runs.append(run)
-                run = [i]
-        runs.append(run)
-        self._split_plan = (critic_ids, other_ids, [flat.window(critic_ids)] + [flat.window(r) for r in runs])
-        return self._split_plan
+        return self._separate_value_term and self.step_plan().mode != ONE_PASS
 
     def _train_step(self, metadata: dict[str, Any], batch: dict[str, Any]):
         self.actor.clear_intermediate_repr()

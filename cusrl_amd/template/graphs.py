@@ -329,20 +329,15 @@ class GraphedTrainStep:
         agent.actor.clear_intermediate_repr()
         agent.critic.clear_intermediate_repr()
         agent.hook.pre_objective(self.metadata, batch)
-        agent._critic_stream = agent._branch_stream if self._critic_branch() else None
-        agent._critic_backward_stream = agent._critic_stream  # (where the critic's autograd nodes will run: _backward's split route)
-        agent._deferred_loss_owner = self if agent.defer_loss_finalize else None
-        try:
+        with agent.step_context.set(critic_stream=agent._branch_stream if self._critic_branch() else None,
+                                    deferred_loss_owner=self if agent.defer_loss_finalize else None):
             with agent.autocast():
                 objectives = agent.hook.objective(self.metadata, batch)
-        finally:
-            agent._critic_stream = None
-            agent._deferred_loss_owner = None
-        if objectives is not None:
-            loss = objectives.terms() if agent.flat_gradients is not None else objectives.loss()
-            agent._zero_grad()
-            agent._backward(loss)
-            agent.grad_scaler.unscale_(agent.optimizer)
+            if objectives is not None:
+                loss = objectives.terms() if agent.flat_gradients is not None else objectives.loss()
+                agent._zero_grad()
+                agent._backward(loss)
+                agent.grad_scaler.unscale_(agent.optimizer)
         self.carry = {"batch": batch, "objectives": objectives}
 
     def _phase_b(self):
@@ -555,9 +550,12 @@ class GraphedEpochs:
         store = self.stores.setdefault((parity, indices.numel(), step.temporal, names), {})
         return buffer.gather(indices, step.temporal, fields=names, out=store)
 
-    def _body(self, row):
+    def _body(self, row) -> list:
+        """Issues the steps of ``row``; returns the records of the steps that left their streams unjoined, which the capture
+        keeps referenced until it has ended (``UnjoinedStep``: their squared-norm rows are read across streams)."""
         agent = self.agent
         main, side = torch.cuda.current_stream(), self.gather_stream
+        records: list = []
         ahead_of_step = self.prefetch in ("side", "tail")
         # (the persistent batch tensors exist by now: `_allocate` ran outside the capture)
         ahead = self._gather(row[0][0], row[0][2], 0) if ahead_of_step else None
@@ -568,6 +566,7 @@ class GraphedEpochs:
             step.metadata = TrackedMetadata(metadata, agent._metadata_reads)
             step.preloaded = ahead
             following: list = []
+            fetch = None
             if ahead_of_step and k + 1 < len(row):
                 # the next step's rows depend on the buffer and the permutation only
                 fetch = lambda k=k: following.append(self._gather(row[k + 1][0], row[k + 1][2], (k + 1) % 2))  # noqa: E731
@@ -575,24 +574,24 @@ class GraphedEpochs:
                     side.wait_stream(main)
                     with torch.cuda.stream(side):
                         fetch()
-                else:  # at the tail of this step's critic branch (ActorCritic._backward calls it there, on that stream)
-                    agent._branch_tail = fetch
+                    fetch = None
             optimizer = agent.flat_optimizer
             two_window_before = optimizer.two_window_steps if optimizer is not None else 0
-            agent._unjoined_steps = self.prefetch == "tail"  # (the step may leave its streams unjoined: ActorCritic._backward)
-            agent._batch_on_branch = on_branch
+            # (fetch: at the tail of this step's critic branch — ActorCritic._backward calls it there, on that stream; the step
+            # may leave its streams unjoined, they meet behind the LAST body)
             try:
-                step._whole_step()
+                with agent.step_context.set(branch_tail=fetch, unjoined=records if self.prefetch == "tail" else None,
+                                            batch_on_branch=on_branch) as context:
+                    step._whole_step()
+                    pending = context.branch_tail
             finally:
                 step.static_indices, step.metadata, step.preloaded = saved
-                pending, agent._branch_tail = agent._branch_tail, None
-                agent._unjoined_steps = agent._batch_on_branch = False
             step.carry = {}
             unjoined = optimizer is not None and optimizer.two_window_steps != two_window_before
-            if agent.flat_gradients is not None and agent.flat_gradients.split_tail is not None:
+            if agent.flat_gradients is not None and agent.flat_gradients.unjoined is not None:
                 # (a backward left its streams unjoined and nobody stepped the optimizer: meet here)
-                main.wait_stream(agent.flat_gradients.split_tail["branch"])
-                agent.flat_gradients.split_tail, unjoined = None, False
+                main.wait_stream(agent.flat_gradients.unjoined.branch)
+                agent.flat_gradients.unjoined, unjoined = None, False
             if pending is not None:
                 pending()  # no critic branch in this composition: behind the step, on its stream
             elif side is not None and following:
@@ -604,6 +603,7 @@ class GraphedEpochs:
             branch_open = unjoined
         if branch_open:
             main.wait_stream(agent._branch_stream)  # the streams of the last body meet before the capture ends
+        return records
 
     def _allocate(self, rows):
         """The persistent batch tensors of both parities, created OUTSIDE the capture (one throw-away gather per set: an

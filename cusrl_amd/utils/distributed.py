@@ -16,6 +16,7 @@ from __future__ import annotations
 import os
 from contextlib import contextmanager
 from collections.abc import Iterable, Sequence
+from dataclasses import dataclass
 from typing import Any, TypeVar
 
 import numpy as np
@@ -26,6 +27,7 @@ from cusrl_amd.utils.config import CONFIG, configure_distributed
 __all__ = [
     "FlatGradients",
     "RcclComm",
+    "UnjoinedStep",
     "native_comm",
     "average_dict",
     "barrier",
@@ -544,6 +546,32 @@ def reduce_mean_var_(mean: torch.Tensor, var: torch.Tensor) -> tuple[torch.Tenso
     return mean, var
 
 
+@dataclass(eq=False)
+class UnjoinedStep:
+    """A backward that assembled the critic's window of the flat buffer on the critic's stream and the others' window on the
+    main stream WITHOUT joining them (``ActorCritic._backward``): what the two-window step of ``FlatAdam`` needs.
+
+    ``sumsq`` holds the squared-norm rows of both assemblies in parameter order (summed as ONE assembly's rows would be: the
+    same norm to the bit), or ``(None, None)`` with several ranks, where the step launches measure the averaged buffer's norm
+    themselves.  Each row is read by the other stream's step launch: the record is kept alive until the capture of its graph
+    has ended (``GraphedEpochs._body``), so the private pool never hands a row to a later allocation of the same graph.  Any
+    later write of a row belongs to a later graph launch on the same stream, which starts behind the end of this graph."""
+
+    branch: torch.cuda.Stream
+    branch_assembled: torch.cuda.Event
+    main_assembled: torch.cuda.Event  # what the critic's step launch waits for: the others' assembly, or the all-reduce behind it
+    main_range: tuple[int, int]  # element ranges of the two windows
+    branch_range: tuple[int, int]
+    sumsq: tuple[torch.Tensor | None, torch.Tensor | None]
+    multi_rank: bool  # the buffer has to be averaged over the ranks between the backward and the step (reduce_gradients)
+    averaged: bool = False
+
+    def average(self, event: torch.cuda.Event) -> None:
+        """``reduce_gradients`` averaged the buffer on the main stream behind both assemblies (it waited for the critic's):
+        the critic's step launch waits for ``event`` instead of the others' assembly."""
+        self.main_assembled, self.averaged = event, True
+
+
 class FlatGradients:
     """One contiguous fp32 buffer that every parameter's ``.grad`` aliases.
 
@@ -565,12 +593,11 @@ class FlatGradients:
         self.buffer = torch.zeros(total, dtype=torch.float32, device=device)
         self.views = []
         self.absent: list[int] = []
-        # the per-network split of the backward (ActorCritic._backward): the windows it reduces, and whether it already did
-        self.split_windows: list[torch.Tensor] | None = None
-        self.reduced = False
-        # a backward that assembled the critic's window on the critic's stream and the others' on the main stream WITHOUT joining
-        # them (ActorCritic._backward, round 6): events, squared-norm rows and element ranges for the two-window optimizer step
-        self.split_tail: dict | None = None
+        # the per-network split of the backward (ActorCritic._backward): the windows it left for reduce_gradients to average one
+        # by one (() = it averaged them itself)
+        self.unaveraged_windows: tuple[torch.Tensor, ...] | None = None
+        # a backward that left its two windows assembled on two streams, unjoined (ActorCritic._backward): FlatAdam.step takes it
+        self.unjoined: UnjoinedStep | None = None
         self._sumsq: torch.Tensor | None = None
         self._sumsq_version = -1
         for p, offset in zip(self.params, self.offsets):
@@ -646,13 +673,6 @@ class FlatGradients:
         self._sumsq_version = self.buffer._version
         return sumsq
 
-    def element_range(self, indices: Sequence[int]) -> tuple[int, int]:
-        """``(first, end)`` element offsets of the run of consecutive parameters ``indices`` (padding included)."""
-        first, last = indices[0], indices[-1]
-        if list(indices) != list(range(first, last + 1)):
-            raise ValueError("a gradient window is a run of consecutive parameters")
-        return self.offsets[first], (self.offsets[last + 1] if last + 1 < len(self.offsets) else self.buffer.numel())
-
     def window(self, indices: Sequence[int]) -> torch.Tensor:
         """The contiguous stretch of the buffer that holds the (consecutive) parameters ``indices``, padding included."""
         first, last = indices[0], indices[-1]
@@ -674,24 +694,21 @@ def reduce_gradients(optimizer: torch.optim.Optimizer, flat: FlatGradients | Non
         return
     if flat is not None and flat.intact():
         flat._sumsq = None  # the averaged gradients have another norm
-        tail = flat.split_tail
-        if tail is not None and tail.get("reduce"):
+        step = flat.unjoined
+        if step is not None and step.multi_rank and not step.averaged:
             # An unjoined step (ActorCritic._backward): the critic's window was assembled on the critic's stream, the others' on
             # this one.  ONE collective over the whole buffer, here, behind the critic's assembly; the critic's step launch waits
             # for it through the event its stream would have waited for anyway (FlatAdam.step: `main_assembled`) — the step still
             # has two cross-stream edges and no join.
             main = torch.cuda.current_stream()
-            main.wait_event(tail["branch_assembled"])
+            main.wait_event(step.branch_assembled)
             reduce_mean_(flat.buffer)
             averaged = torch.cuda.Event()
             averaged.record(main)
-            tail.update(main_assembled=averaged, main_joined=True, reduced=True, reduce=False)
+            step.average(averaged)
             return
-        if flat.reduced:  # the split route already averaged both windows inside the backward
-            flat.reduced = False
-            return
-        windows = flat.split_windows
-        if CONFIG.split_gradient_allreduce and windows:
+        windows, flat.unaveraged_windows = flat.unaveraged_windows, None
+        if windows is not None:
             # the split route where the collectives cannot be issued inside the backward (a captured phase on a route that
             # cannot be captured: torch.distributed's collectives): the same windows, one after the other, here
             for window in windows:

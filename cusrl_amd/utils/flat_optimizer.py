@@ -64,7 +64,7 @@ class FlatAdam:
         self.lr = torch.zeros(1, dtype=torch.float32, device=device)
         self._lr_value: float | None = None
         self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
-        # the two-window step (ActorCritic._backward left the streams unjoined, FlatGradients.split_tail): the critic's window is
+        # the two-window step (ActorCritic._backward left the streams unjoined, FlatGradients.unjoined): the critic's window is
         # stepped on the critic's stream with a counter and a ticket of its own; every launch keeps the two counters equal
         self.branch_step_count = torch.zeros(1, dtype=torch.float32, device=device)
         self.branch_ticket = torch.zeros(1, dtype=torch.int32, device=device)
@@ -111,14 +111,14 @@ class FlatAdam:
         """Take over gradient clipping: launches only the squared-norm partials now; the coefficient is applied by
         the next :meth:`step`.  Returns the device scalar that will hold the pre-clip norm after that step."""
         norm = torch.empty(1, dtype=torch.float32, device=self.lr.device)  # one per step: metrics keep a reference
-        tail = self.gradients.split_tail
-        if tail is not None and tail.get("reduce"):
-            raise RuntimeError("FlatAdam: the windows of an unjoined multi-rank step reached the clipping without having been "
-                               "averaged over the ranks (reduce_gradients comes between the backward and pre_optim)")
-        if tail is not None:
+        unjoined = self.gradients.unjoined
+        if unjoined is not None:
+            if unjoined.multi_rank and not unjoined.averaged:
+                raise RuntimeError("FlatAdam: the windows of an unjoined multi-rank step reached the clipping without having been "
+                                   "averaged over the ranks (reduce_gradients comes between the backward and pre_optim)")
             # two unjoined window assemblies: their rows, in parameter order (summed as one array by both launches) — or, when
             # the gradients were averaged over the ranks behind the assemblies, the norm each step launch measures itself
-            self._pending_clip = (_OWN_NORM if tail.get("reduced") else tail["sumsq"], max_norm, norm)
+            self._pending_clip = (_OWN_NORM if unjoined.averaged else unjoined.sumsq, max_norm, norm)
             return norm[0]
         partials = self.gradients.take_sumsq()  # left behind by the gradient assembly when nothing touched them since
         if partials is None:
@@ -170,15 +170,15 @@ class FlatAdam:
         slot = tap.slot_of(norm) if tap is not None else None
         hyper = dict(betas=group["betas"], eps=group["eps"], weight_decay=group["weight_decay"], decoupled=decoupled,
                      maximize=bool(group.get("maximize", False)), max_norm=max_norm)
-        tail, self.gradients.split_tail = self.gradients.split_tail, None
-        if tail is not None and not kept:
+        unjoined, self.gradients.unjoined = self.gradients.unjoined, None
+        if unjoined is not None and not kept:
             # The backward left the critic's window assembled on the critic's stream and the others' on this one, unjoined: each
             # window is stepped where its gradients are, behind the OTHER window's assembly (an event edge — the clipping
             # coefficient needs both windows' rows).  No join, no fork: the critic's next forward follows its own step on its own
             # stream, and a stream only ever waits for the other's assembly — a fork / join pair per minibatch step costs
             # ~18 us on this stack, two late-bound event edges ~11 (scripts/probe_graph_fork.py).
-            main, branch = torch.cuda.current_stream(), tail["branch"]
-            (lo, hi), (blo, bhi) = tail["main_range"], tail["branch_range"]
+            main, branch = torch.cuda.current_stream(), unjoined.branch
+            (lo, hi), (blo, bhi) = unjoined.main_range, unjoined.branch_range
             if partials is _OWN_NORM:
                 # several ranks (reduce_gradients averaged the whole buffer on this stream, behind the critic's assembly): both
                 # launches measure the norm of the WHOLE averaged buffer themselves — same split, same norm to the bit
@@ -191,13 +191,13 @@ class FlatAdam:
 
             def critic_window():
                 with torch.cuda.stream(branch):
-                    branch.wait_event(tail["main_assembled"])
+                    branch.wait_event(unjoined.main_assembled)
                     step_branch(self.param_buffer[blo:bhi], self.gradients.buffer[blo:bhi], self.exp_avg[blo:bhi],
                                 self.exp_avg_sq[blo:bhi], self.branch_step_count, self.lr, self.branch_ticket, **hyper)
 
             def main_window():
-                if not tail.get("main_joined"):  # (the all-reduce of a multi-rank step already waited for the critic's assembly)
-                    main.wait_event(tail["branch_assembled"])
+                if not unjoined.averaged:  # (the all-reduce of a multi-rank step already waited for the critic's assembly)
+                    main.wait_event(unjoined.branch_assembled)
                 step_main(self.param_buffer[lo:hi], self.gradients.buffer[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
                           self.step_count, self.lr, self.ticket, norm_out=norm, norm_accumulator=slot, **hyper)
 
@@ -205,7 +205,7 @@ class FlatAdam:
             # front of them (it follows a node's first edge): behind the all-reduce of a multi-rank step that must be the main
             # stream's — the longer chain, the actor's — so that its step launch follows the collective without a queue hop.
             # (a single process: measured neutral, profiles/r06/experiments/step_order_single_process_ab.txt — left as it was)
-            main_first = (tail.get("reduced") and os.environ.get("CUSRL_NORMED_MAIN_FIRST", "1") != "0"
+            main_first = (unjoined.averaged and os.environ.get("CUSRL_NORMED_MAIN_FIRST", "1") != "0"
                           or os.environ.get("CUSRL_STEP_MAIN_FIRST") == "1")
             if main_first:
                 main_window(), critic_window()
@@ -213,8 +213,8 @@ class FlatAdam:
                 critic_window(), main_window()
             self.two_window_steps += 1
             return loss
-        if tail is not None:  # (parameters without a gradient are put back below: one launch over everything, behind a join)
-            torch.cuda.current_stream().wait_stream(tail["branch"])
+        if unjoined is not None:  # (parameters without a gradient are put back below: one launch over everything, behind a join)
+            torch.cuda.current_stream().wait_stream(unjoined.branch)
         if partials is _OWN_NORM:
             ops.adam_step_normed(self.param_buffer, self.gradients.buffer, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr,
                                  self.ticket, norm_grad=self.gradients.buffer, workspace=self._norm_workspaces[0], norm_out=norm,

@@ -914,6 +914,85 @@ def test_recurrent_step_gemm_rows_are_bucketed_to_256_and_capped_by_the_batch():
     assert _gemm_rows(7, 7) == 7 and _gemm_rows(100, 100) == 100
 
 
+def test_step_plan_decision_table():
+    """template/actor_critic.py::plan_step — the form of a minibatch step from plain inputs: each mode from its inputs, and
+    each disqualifier of the unjoined and of the split form."""
+    from cusrl_amd.hook.on_policy.gradient_clipping import GradientClipping
+    from cusrl_amd.template.actor_critic import JOINED, ONE_PASS, SPLIT, UNJOINED, plan_step
+    from cusrl_amd.template.hook import Hook
+
+    offsets, size = [0, 8, 16, 24, 32, 40], 48  # six parameters; the critic's are the last two unless said otherwise
+    plan = lambda critic=(4, 5), **kw: plan_step(critic, offsets, size, **{"flat_adam": True, **kw})  # noqa: E731
+
+    class OwnPreOptim(Hook):
+        def pre_optim(self, optimizer):
+            pass
+
+    class OwnPostOptim(Hook):
+        def post_optim(self):
+            pass
+
+    class ClippingWithPostOptim(GradientClipping):
+        def post_optim(self):
+            pass
+
+    assert plan(None).mode == ONE_PASS and plan(()).mode == ONE_PASS  # the critic shares parameters (or has none)
+    unjoined = plan()
+    assert unjoined.mode == UNJOINED and unjoined.critic_ids == (4, 5) and unjoined.other_ids == (0, 1, 2, 3)
+    assert unjoined.ranges == ((0, 32), (32, 48)) and unjoined.reduce_windows == ()
+    assert plan(hooks=[Hook(), GradientClipping()]).mode == UNJOINED  # the stock clipping defers to the flat Adam step
+    assert plan((0, 1)).ranges == ((16, 48), (0, 16))
+    joined = [plan(flat_adam=False), plan(two_window=False), plan((1, 4)), plan((2, 3)), plan(hooks=[OwnPreOptim()]),
+              plan(hooks=[OwnPostOptim()]), plan(hooks=[GradientClipping(groups={"actor": 1.0})]),
+              plan(hooks=[ClippingWithPostOptim()]), plan(multi_rank=True), plan(multi_rank=True, native_comm=True, split_allreduce=True)]
+    assert all(p.mode == JOINED and p.ranges is None for p in joined), [p.mode for p in joined]
+    assert joined[3].critic_ids == (2, 3) and joined[3].other_ids == (0, 1, 4, 5)
+    assert plan(multi_rank=True, native_comm=True).mode == UNJOINED  # one collective over the whole buffer, captured
+    assert plan(split_allreduce=True, branch_stream=True).mode == UNJOINED  # (a single process has nothing to split)
+    split = plan((2, 3), multi_rank=True, split_allreduce=True, branch_stream=True, flat_adam=False, hooks=[OwnPreOptim()])
+    assert split.mode == SPLIT and split.reduce_windows == ((16, 32), (0, 16), (32, 48)) and split.ranges is None
+    assert plan(multi_rank=True, split_allreduce=True, branch_stream=True).reduce_windows == ((32, 48), (0, 32))
+    assert plan((1, 4), multi_rank=True, split_allreduce=True, branch_stream=True).mode == JOINED  # the critic in two runs
+    assert plan(multi_rank=True, split_allreduce=True).mode == JOINED  # no branch stream
+    assert plan(tuple(range(6)), multi_rank=True, split_allreduce=True, branch_stream=True).mode == JOINED  # nobody else
+
+
+def test_step_plan_follows_a_hook_activated_after_the_first_plan():
+    """ActorCritic.step_plan is computed from the agent as it stands: a hook with its own ``pre_optim`` that becomes active
+    after a step was planned unjoined makes the next plan a joined one (it could read the window on the other stream)."""
+    from cusrl_amd.template.actor_critic import JOINED, UNJOINED
+    from cusrl_amd.template.hook import Hook
+
+    class ReadsGradients(Hook):
+        def pre_optim(self, optimizer):
+            pass
+
+    factory = cusrl.preset.PpoAgentFactory(device="cpu").to_underlying()
+    factory.register_hook(ReadsGradients())
+    agent = factory(cusrl.EnvironmentSpec(48, 12, num_instances=4, device="cpu"))
+    (hook,) = [hook for hook in agent.hook if isinstance(hook, ReadsGradients)]
+    hook.active_(False)
+    agent.flat_optimizer = object()  # (a CPU agent steps torch's Adam: stand in for the flat Adam step of a GPU agent)
+    assert agent.step_plan().mode == UNJOINED and agent.separate_value_root and not agent._split_plan
+    hook.active_(True)
+    assert agent.step_plan().mode == JOINED and agent.separate_value_root
+
+
+def test_step_context_restores_its_fields_on_exit():
+    """ActorCritic.step_context: what a captured step body installs is put back when the body ends, also on an exception."""
+    from cusrl_amd.template.actor_critic import StepContext
+
+    context = StepContext()
+    with context.set(batch_on_branch=True, unjoined=[]):
+        with context.set(critic_stream="branch", branch_tail=print) as inner:
+            assert inner is context and context.critic_stream == "branch" and context.batch_on_branch
+            context.branch_tail = None  # consumed inside the body
+        assert context.critic_stream is None and context.branch_tail is None and context.unjoined == []
+    with pytest.raises(RuntimeError), context.set(deferred_loss_owner="step"):
+        raise RuntimeError
+    assert context == StepContext()
+
+
 def test_critic_stream_branch_default_is_chosen_per_composition(monkeypatch):
     """GraphedTrainStep._critic_branch: forced by ``agent.concurrent_critic``; unset, the branch only where it measured
     faster — the stock fused composition at >= 4096-row minibatches (profiles/r05/stream_ab.txt); launch-bound small
