@@ -13,9 +13,11 @@ from pathlib import Path
 
 # (CUSRL_HIP_LIBRARY: another build of the same library — A/B runs of compile-time variants, profiles/r05/loss_variants_ab.txt)
 LIB_PATH = Path(os.environ.get("CUSRL_HIP_LIBRARY") or Path(__file__).resolve().parent / "libcusrl_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_FIELDS = 24
 MAX_PACKED = 16
+MAX_MIRROR_FIELDS = 24
+MAX_SYMMETRIZE_CHANNELS = 4096
 
 
 class Field(Structure):
@@ -34,6 +36,13 @@ class GradPiece(Structure):
     """``cusrl_grad_piece_t`` — one parameter's slot of the flat gradient buffer and what to sum into it."""
 
     _fields_ = [("src", c_void_p), ("offset", c_int64), ("numel", c_int64), ("splits", c_int64), ("row_stride", c_int64)]
+
+
+class MirrorField(Structure):
+    """``cusrl_mirror_field_t`` — one field of a ``cusrl_mirror_rows`` launch (a copy, or the mirror through a table)."""
+
+    _fields_ = [("src", c_void_p), ("src_stride", c_int64), ("dst", c_void_p), ("dst_stride", c_int64), ("dst_offset", c_int64),
+                ("table", c_void_p), ("width", ctypes.c_int32), ("src_width", ctypes.c_int32)]
 
 
 class NativeError(RuntimeError):
@@ -159,6 +168,11 @@ _SIGNATURES = {
     "cusrl_sequence_blocks": (c_int64, [c_int64]),
     "cusrl_sequence_layout": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
     "cusrl_gather_memory": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P]),
+    "cusrl_mirror_rows": (c_int, [POINTER(MirrorField), c_int, c_int64, _P]),
+    "cusrl_mirror_rows_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, _P]),
+    "cusrl_mirror_mse_fwd_bwd": (c_int, [_P, _P, _P, _P, c_int, _P, c_int64, c_int64, c_double, _P, _P, _P, _P, _P, _P, _P]),
+    "cusrl_mirror_mse_num_partials": (c_int64, [c_int64]),
+    "cusrl_symmetrize_mean_var": (c_int, [_P, _P, _P, c_int64, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

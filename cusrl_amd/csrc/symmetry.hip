@@ -1,0 +1,268 @@
+// Mirror symmetry (cusrl/hook/auxiliary/symmetry.py, cusrl/hook/mdp/observation.py:213-217) as single launches:
+//   cusrl_mirror_rows          MirrorDef.__call__ over several fields at once, into strided / offset destinations: the
+//                              [R, 2, C] rows of SymmetricDataAugmentation (original half copied, mirrored half through the
+//                              table) and the repeated narrow leaves in ONE launch
+//   cusrl_mirror_rows_bwd      its gradient, through the inverse table (fixed-order sums per input column)
+//   cusrl_mirror_mse_fwd_bwd   MirrorSymmetryLoss: both weighted terms and the gradients wrt both actor outputs in one pass
+//   cusrl_symmetrize_mean_var  the symmetric running-statistics update of ObservationNormalization, in place
+// Table (int32, built once on the host, cusrl_amd/hook/auxiliary/symmetry.py): [C_out] forward codes, [C_in + 1] offsets,
+// [C_out] inverse codes.  A code is a column index with bit 31 set when the value is negated.  A negation is a sign flip
+// (exact, signed zeros included), which is what `x * -1` is for every non-NaN x.
+#include "common.hpp"
+
+namespace cusrl {
+
+constexpr uint32_t kFlipBit = 0x80000000u;
+constexpr int kMirrorTile = 4096;  // elements per block of the row kernels (whole rows; a wider row takes a block alone)
+constexpr int kMirrorMaxBlocks = 1024;
+
+__device__ __forceinline__ float apply_code(float v, uint32_t code) { return (code & kFlipBit) ? -v : v; }
+__device__ __forceinline__ int code_column(uint32_t code) { return int(code & ~kFlipBit); }
+
+struct MirrorTable {
+    cusrl_mirror_field_t f[CUSRL_MAX_MIRROR_FIELDS];
+};
+
+__host__ __device__ inline int64_t mirror_rows_per_block(int64_t width) { return width >= kMirrorTile ? 1 : kMirrorTile / width; }
+
+// blockIdx.y = field, blockIdx.x = a tile of whole rows.  Thread t of the tile writes element t (coalesced stores); its load
+// is a gather inside the same row, which the row's cache lines serve.
+__global__ __launch_bounds__(kBlock) void mirror_rows_kernel(MirrorTable table, int64_t rows) {
+    const cusrl_mirror_field_t &f = table.f[blockIdx.y];
+    const int64_t width = f.width, rpb = mirror_rows_per_block(width);
+    const int64_t row0 = int64_t(blockIdx.x) * rpb;
+    if (row0 >= rows) return;
+    const int64_t nrows = rows - row0 < rpb ? rows - row0 : rpb;
+    const uint32_t n = uint32_t(nrows * width), w = uint32_t(width);
+    const uint32_t *codes = reinterpret_cast<const uint32_t *>(f.table);
+    for (uint32_t e = threadIdx.x; e < n; e += kBlock) {
+        const uint32_t r = e / w, c = e - r * w;
+        const int64_t row = row0 + r;
+        const float *src = f.src + row * f.src_stride;
+        float v;
+        if (codes) {
+            const uint32_t code = codes[c];
+            v = apply_code(src[code_column(code)], code);
+        } else {
+            v = src[c];
+        }
+        f.dst[row * f.dst_stride + f.dst_offset + c] = v;
+    }
+}
+
+// grad_in[r, i] = sum over the output columns j that read column i, in increasing j, of sign_j * grad_out[r, j]
+__global__ __launch_bounds__(kBlock) void mirror_rows_bwd_kernel(const float *__restrict__ grad_out, int64_t go_stride,
+                                                                 float *__restrict__ grad_in, int64_t gi_stride,
+                                                                 const uint32_t *__restrict__ table, int c_in, int c_out,
+                                                                 int64_t rows) {
+    const int64_t rpb = mirror_rows_per_block(c_in), row0 = int64_t(blockIdx.x) * rpb;
+    if (row0 >= rows) return;
+    const int64_t nrows = rows - row0 < rpb ? rows - row0 : rpb;
+    const uint32_t n = uint32_t(nrows * c_in), w = uint32_t(c_in);
+    const uint32_t *offsets = table + c_out, *inverse = table + c_out + c_in + 1;
+    for (uint32_t e = threadIdx.x; e < n; e += kBlock) {
+        const uint32_t r = e / w, i = e - r * w;
+        const int64_t row = row0 + r;
+        const float *g = grad_out + row * go_stride;
+        float acc = 0.0f;
+        for (uint32_t k = offsets[i]; k < offsets[i + 1]; ++k) {
+            const uint32_t code = inverse[k];
+            acc += apply_code(g[code_column(code)], code);
+        }
+        grad_in[row * gi_stride + i] = acc;
+    }
+}
+
+// torch.sign: the gradient of abs (0 at 0, NaN stays NaN)
+__device__ __forceinline__ float sign_of(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : x); }
+
+// One pass over [B, A]: element (b, j) adds its squared differences to the fp64 partials and writes d mu[b, j] and
+// d sigma[b, j]; as (b, i) it writes d mu~[b, i] and d sigma~[b, i], re-deriving the differences of the output columns that
+// read column i (from the same row, in cache) in increasing j.  A std vector ([A], repeat_std) is one row, done by block 0.
+__global__ __launch_bounds__(kBlock) void mirror_mse_kernel(const float *__restrict__ mu, const float *__restrict__ mu_m,
+                                                            const float *__restrict__ sigma, const float *__restrict__ sigma_m,
+                                                            int std_vector, const uint32_t *__restrict__ table, int64_t B,
+                                                            int A, float g_mean, float g_std, float *__restrict__ d_mu,
+                                                            float *__restrict__ d_mu_m, float *__restrict__ d_sigma,
+                                                            float *__restrict__ d_sigma_m, double *__restrict__ partials,
+                                                            double loss_mean_scale, double loss_std_scale,
+                                                            float *__restrict__ loss_out) {
+    __shared__ double scratch[kWavesPerBlock];
+    const uint32_t *offsets = table + A, *inverse = table + 2 * A + 1;
+    const int64_t n = B * A, stride = int64_t(gridDim.x) * kBlock;
+    const bool std_matrix = sigma != nullptr && !std_vector;
+    double acc_mean = 0.0, acc_std = 0.0;
+    for (int64_t e = int64_t(blockIdx.x) * kBlock + threadIdx.x; e < n; e += stride) {
+        const int64_t b = e / A;
+        const int j = int(e - b * A);
+        const float *m = mu + b * A, *mm = mu_m + b * A;
+        const uint32_t code = table[j];
+        const float d = m[j] - apply_code(mm[code_column(code)], code);
+        acc_mean += double(d * d);
+        d_mu[e] = g_mean * d;
+        float acc = 0.0f;
+        for (uint32_t k = offsets[j]; k < offsets[j + 1]; ++k) {
+            const uint32_t c = inverse[k];
+            const int jj = code_column(c);
+            const float dd = m[jj] - apply_code(mm[j], c);
+            acc += apply_code(-(g_mean * dd), c);
+        }
+        d_mu_m[e] = acc;
+        if (std_matrix) {
+            const float *s = sigma + b * A, *sm = sigma_m + b * A;
+            const float t = s[j] - fabsf(sm[code_column(code)]);
+            acc_std += double(t * t);
+            d_sigma[e] = g_std * t;
+            float a2 = 0.0f;
+            for (uint32_t k = offsets[j]; k < offsets[j + 1]; ++k) {
+                const int jj = code_column(inverse[k]);
+                a2 += -(g_std * (s[jj] - fabsf(sm[j])));
+            }
+            d_sigma_m[e] = a2 * sign_of(sm[j]);
+        }
+    }
+    if (sigma != nullptr && std_vector && blockIdx.x == 0) {
+        for (int j = threadIdx.x; j < A; j += kBlock) {
+            const uint32_t code = table[j];
+            const float t = sigma[j] - fabsf(sigma_m[code_column(code)]);
+            acc_std += double(t * t);
+            d_sigma[j] = g_std * t;
+            float a2 = 0.0f;
+            for (uint32_t k = offsets[j]; k < offsets[j + 1]; ++k) {
+                const int jj = code_column(inverse[k]);
+                a2 += -(g_std * (sigma[jj] - fabsf(sigma_m[j])));
+            }
+            d_sigma_m[j] = a2 * sign_of(sigma_m[j]);
+        }
+    }
+    const double total_mean = block_sum(acc_mean, scratch);
+    const double total_std = block_sum(acc_std, scratch);
+    if (threadIdx.x == 0) {
+        if (gridDim.x == 1) {
+            loss_out[0] = float(total_mean * loss_mean_scale);
+            loss_out[1] = float(total_std * loss_std_scale);
+        } else {
+            partials[2 * blockIdx.x] = total_mean;
+            partials[2 * blockIdx.x + 1] = total_std;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void mirror_mse_finalize_kernel(const double *__restrict__ partials, int blocks,
+                                                                     double loss_mean_scale, double loss_std_scale,
+                                                                     float *__restrict__ loss_out) {
+    __shared__ double scratch[kWavesPerBlock];
+    double acc_mean = 0.0, acc_std = 0.0;
+    for (int b = threadIdx.x; b < blocks; b += kBlock) {
+        acc_mean += partials[2 * b];
+        acc_std += partials[2 * b + 1];
+    }
+    const double total_mean = block_sum(acc_mean, scratch);
+    const double total_std = block_sum(acc_std, scratch);
+    if (threadIdx.x == 0) {
+        loss_out[0] = float(total_mean * loss_mean_scale);
+        loss_out[1] = float(total_std * loss_std_scale);
+    }
+}
+
+// observation.py:213-217 in fp32, one rounding per operation and in the reference's order:
+//   mm = M(mean); mv = |M(var)|; var = (var + mv) / 2 + (mean - mm)^2 / 4; mean = (mean + mm) / 2
+// Every new value reads other columns of the old ones: all of them are staged in LDS before any is stored.
+__global__ __launch_bounds__(kBlock) void symmetrize_mean_var_kernel(float *__restrict__ mean, float *__restrict__ var,
+                                                                     const uint32_t *__restrict__ table, int C) {
+    extern __shared__ float staged[];  // [2 C]: new mean, new var
+    for (int j = threadIdx.x; j < C; j += kBlock) {
+        const uint32_t code = table[j];
+        const int i = code_column(code);
+        const float m = mean[j], v = var[j];
+        const float mm = apply_code(mean[i], code), mv = fabsf(apply_code(var[i], code));
+        const float diff = __fsub_rn(m, mm);
+        staged[j + C] = __fadd_rn(__fmul_rn(__fadd_rn(v, mv), 0.5f), __fmul_rn(__fmul_rn(diff, diff), 0.25f));
+        staged[j] = __fmul_rn(__fadd_rn(m, mm), 0.5f);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < C; j += kBlock) {
+        mean[j] = staged[j];
+        var[j] = staged[j + C];
+    }
+}
+
+}  // namespace cusrl
+
+using namespace cusrl;
+
+extern "C" int cusrl_mirror_rows(const cusrl_mirror_field_t *fields, int n_fields, int64_t rows, void *stream) {
+    if (!fields || n_fields <= 0 || rows < 0) return CUSRL_E_INVALID;
+    if (n_fields > CUSRL_MAX_MIRROR_FIELDS) return CUSRL_E_TOO_MANY;
+    MirrorTable table{};
+    int64_t blocks = 0;
+    for (int i = 0; i < n_fields; ++i) {
+        const cusrl_mirror_field_t &f = fields[i];
+        if (f.width <= 0 || f.src_width <= 0) return CUSRL_E_INVALID;
+        if (rows > 0 && (!f.src || !f.dst)) return CUSRL_E_INVALID;  // (an empty tensor may have no storage)
+        if (f.src_stride < f.src_width || f.dst_offset < 0 || f.dst_stride < f.dst_offset + f.width) return CUSRL_E_INVALID;
+        if (!f.table && f.width != f.src_width) return CUSRL_E_INVALID;  // a copy keeps the width
+        if (rows > 1 && f.src_stride > (int64_t(1) << 40)) return CUSRL_E_UNSUPPORTED;
+        table.f[i] = f;
+        const int64_t need = ceil_div(rows, mirror_rows_per_block(f.width));
+        if (need > blocks) blocks = need;
+    }
+    if (rows == 0) return 0;
+    if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
+    hipLaunchKernelGGL(mirror_rows_kernel, dim3(uint32_t(blocks), uint32_t(n_fields)), dim3(kBlock), 0, as_stream(stream),
+                       table, rows);
+    return launch_status();
+}
+
+extern "C" int cusrl_mirror_rows_bwd(const float *grad_out, int64_t go_stride, float *grad_in, int64_t gi_stride,
+                                     const int32_t *table, int64_t c_in, int64_t c_out, int64_t rows, void *stream) {
+    if (!table || c_in <= 0 || c_out <= 0 || rows < 0) return CUSRL_E_INVALID;
+    if (rows > 0 && (!grad_out || !grad_in)) return CUSRL_E_INVALID;  // (an empty tensor may have no storage)
+    if (go_stride < c_out || gi_stride < c_in) return CUSRL_E_INVALID;
+    if (c_in > INT32_MAX / 2 || c_out > INT32_MAX / 2) return CUSRL_E_UNSUPPORTED;
+    if (rows == 0) return 0;
+    const int64_t blocks = ceil_div(rows, mirror_rows_per_block(c_in));
+    if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
+    hipLaunchKernelGGL(mirror_rows_bwd_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), grad_out, go_stride,
+                       grad_in, gi_stride, reinterpret_cast<const uint32_t *>(table), int(c_in), int(c_out), rows);
+    return launch_status();
+}
+
+extern "C" int64_t cusrl_mirror_mse_num_partials(int64_t n) {
+    if (n <= 0) return 0;
+    if (n <= int64_t(kBlock) * 64) return 1;  // one block finalises itself
+    const int64_t want = ceil_div(n, int64_t(kBlock) * 8);
+    return want > kMirrorMaxBlocks ? kMirrorMaxBlocks : want;
+}
+
+extern "C" int cusrl_mirror_mse_fwd_bwd(const float *mu, const float *mu_m, const float *sigma, const float *sigma_m,
+                                        int std_vector, const int32_t *table, int64_t B, int64_t A, double weight,
+                                        float *loss_out, float *d_mu, float *d_mu_m, float *d_sigma, float *d_sigma_m,
+                                        double *partials, void *stream) {
+    if (B <= 0 || A <= 0 || weight < 0.0) return CUSRL_E_INVALID;
+    if (!mu || !mu_m || !table || !loss_out || !d_mu || !d_mu_m || !partials) return CUSRL_E_INVALID;
+    if ((sigma == nullptr) != (sigma_m == nullptr)) return CUSRL_E_INVALID;
+    if (sigma && (!d_sigma || !d_sigma_m)) return CUSRL_E_INVALID;
+    if (A > 65536 || B > (int64_t(1) << 40) / A) return CUSRL_E_UNSUPPORTED;
+    const int64_t n = B * A, blocks = cusrl_mirror_mse_num_partials(n);
+    const double std_count = sigma ? double(std_vector ? A : n) : 1.0;
+    const float g_mean = float(2.0 * weight / double(n)), g_std = float(2.0 * weight / std_count);
+    const double mean_scale = weight / double(n), std_scale = weight / std_count;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(mirror_mse_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, mu, mu_m, sigma, sigma_m, std_vector,
+                       reinterpret_cast<const uint32_t *>(table), B, int(A), g_mean, g_std, d_mu, d_mu_m, d_sigma, d_sigma_m,
+                       partials, mean_scale, std_scale, loss_out);
+    if (int rc = launch_status()) return rc;
+    if (blocks == 1) return 0;
+    hipLaunchKernelGGL(mirror_mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), mean_scale, std_scale,
+                       loss_out);
+    return launch_status();
+}
+
+extern "C" int cusrl_symmetrize_mean_var(float *mean, float *var, const int32_t *table, int64_t C, void *stream) {
+    if (!mean || !var || !table || C <= 0) return CUSRL_E_INVALID;
+    if (C > CUSRL_MAX_SYMMETRIZE_CHANNELS) return CUSRL_E_UNSUPPORTED;
+    hipLaunchKernelGGL(symmetrize_mean_var_kernel, dim3(1), dim3(kBlock), size_t(2 * C) * sizeof(float), as_stream(stream),
+                       mean, var, reinterpret_cast<const uint32_t *>(table), int(C));
+    return launch_status();
+}

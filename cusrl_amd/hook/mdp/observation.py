@@ -4,7 +4,10 @@
 normalised, clamped value, keeping the raw tensors under ``original_*`` (they become extra buffer leaves and ride
 the same push / gather launches).  On MI355X an update is masked column statistics + merge + normalise = three HIP
 launches with the sample count kept on the device; the reference's ``observation[last_done]`` boolean-mask select
-(observation.py:206-208), which synchronises with the host every step, becomes the kernel's row mask.
+(observation.py:206-208), which synchronises with the host every step, becomes the kernel's row mask.  With
+``mirror_observation`` / ``mirror_state`` in the spec the batch statistics are made symmetric before the merge
+(observation.py:213-217): one more launch (``cusrl_symmetrize_mean_var``) for a ``MirrorDef``; any other mirror callable is
+evaluated as given on the ``[C]`` statistics.
 """
 
 from __future__ import annotations
@@ -13,10 +16,32 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from cusrl_amd import ops
+from cusrl_amd.hook.auxiliary.symmetry import MirrorDef
 from cusrl_amd.nn.rms import RunningMeanStd, mean_var_count
 from cusrl_amd.template.hook import Hook
+from cusrl_amd.utils.misc import host_form
 
 __all__ = ["ObservationNormalization"]
+
+
+def _symmetric(stats, mirror):
+    """observation.py:213-217: the batch statistics of the mirrored data merged with the original's, before the merge into
+    the running statistics (and before any cross-rank merge)."""
+    mean, var, count = stats
+    if mirror is None:
+        return stats
+    if isinstance(mirror, MirrorDef) and mean.is_cuda:
+        mean, var = mean.float().contiguous(), var.float().contiguous()
+        ops.symmetrize_mean_var_(mean, var, mirror.device_table(mean.device, mean.numel()))
+        return mean, var, count
+    if not mean.is_cuda:  # (a user-supplied mirror callable on the device is evaluated as given)
+        host_form("ObservationNormalization (symmetric statistics)")
+    mirrored_mean = mirror(mean)
+    mirrored_var = abs(mirror(var))
+    var = (var + mirrored_var) / 2 + (mean - mirrored_mean) ** 2 / 4
+    mean = (mean + mirrored_mean) / 2
+    return mean, var, count
 
 
 class ObservationNormalization(Hook):
@@ -32,6 +57,8 @@ class ObservationNormalization(Hook):
         self.observation_rms: RunningMeanStd
         self.state_rms: RunningMeanStd | None = None
         self._observation_is_subset_of_state = None
+        self._mirror_observation = None
+        self._mirror_state = None
         self._last_done: Tensor | None = None
 
     def freeze(self):
@@ -40,8 +67,16 @@ class ObservationNormalization(Hook):
 
     def init(self):
         spec = self.agent.environment_spec
-        if spec.mirror_observation is not None or spec.mirror_state is not None:
-            raise NotImplementedError("symmetry-aware statistics (mirror_*) are out of scope (SURVEY.md §2 row 15)")
+        self._mirror_observation = spec.mirror_observation
+        self._mirror_state = spec.mirror_state
+        device = getattr(self.agent, "device", None)
+        if device is not None and torch.device(device).type == "cuda":  # tables uploaded now, outside any capture
+            mirrors = [(self._mirror_observation, self.agent.observation_dim)]
+            if self.agent.has_state:  # (without a state the agent's state_dim is the observation's; a state mirror is unused)
+                mirrors.append((self._mirror_state, self.agent.state_dim))
+            for mirror, dim in mirrors:
+                if isinstance(mirror, MirrorDef):
+                    mirror.device_table(device, dim)
         subset = spec.observation_is_subset_of_state
         if subset is not None:
             if not self.agent.has_state:
@@ -108,11 +143,12 @@ class ObservationNormalization(Hook):
             return
         synchronize = not self.defer_synchronization
         if state is not None:
-            self.state_rms.update_from_stats(*mean_var_count(state, mask), synchronize=synchronize)
+            self.state_rms.update_from_stats(*_symmetric(mean_var_count(state, mask), self._mirror_state), synchronize=synchronize)
         if self._observation_is_subset_of_state is not None:
             self._copy_observation_stats_from_state()
         else:
-            self.observation_rms.update_from_stats(*mean_var_count(observation, mask), synchronize=synchronize)
+            self.observation_rms.update_from_stats(*_symmetric(mean_var_count(observation, mask), self._mirror_observation),
+                                                   synchronize=synchronize)
 
     def _copy_observation_stats_from_state(self):
         index = self._observation_is_subset_of_state

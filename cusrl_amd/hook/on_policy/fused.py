@@ -244,7 +244,7 @@ class FusedPpoObjective:
         one-hot categorical policy on a GPU, and no other active hook that defines ``objective``;  ``"split"``: the same
         with further ``objective`` hooks (they get differentiable policy terms from ``cusrl_policy_terms_fwd``);
         ``None``: the hooks evaluate their terms one by one."""
-        from cusrl_amd.hook.auxiliary import AdversarialMotionPrior, RandomNetworkDistillation
+        from cusrl_amd.hook.auxiliary import AdversarialMotionPrior, RandomNetworkDistillation, SymmetricDataAugmentation
         from cusrl_amd.hook.mdp.observation import ObservationNormalization
         from cusrl_amd.hook.on_policy.advantage import AdvantageNormalization, AdvantageReduction
         from cusrl_amd.hook.on_policy.common import OnPolicyPreparation
@@ -260,8 +260,9 @@ class FusedPpoObjective:
             return None
         terms = (ValueLoss, OnPolicyPreparation, PpoSurrogateLoss, EntropyLoss)
         # hooks whose objective neither reads nor differentiates the policy terms: they keep fusion available
+        # (SymmetricDataAugmentation only rewrites the batch in front of the term hooks: the stock terms stay one launch)
         passive = (GeneralizedAdvantageEstimation, AdvantageNormalization, AdvantageReduction, ObservationNormalization,
-                   RandomNetworkDistillation, AdversarialMotionPrior, MiniBatchWiseLRSchedule)
+                   RandomNetworkDistillation, AdversarialMotionPrior, MiniBatchWiseLRSchedule, SymmetricDataAugmentation)
         order, extra = [], False
         for hook in composite:
             if not hook.active:

@@ -25,10 +25,12 @@
 extern "C" {
 #endif
 
-#define CUSRL_ABI_VERSION 6
+#define CUSRL_ABI_VERSION 7
 #define CUSRL_MAX_FIELDS 24 /* leaves per push / gather launch; larger tables are split by the host */
 #define CUSRL_MAX_PACKED 16 /* 1-8 byte entries of the per-slot record (cusrl_pack_rows); wide fields count as leaves */
 #define CUSRL_MAX_RECORD_BYTES 1024
+#define CUSRL_MAX_MIRROR_FIELDS 24 /* fields per cusrl_mirror_rows launch */
+#define CUSRL_MAX_SYMMETRIZE_CHANNELS 4096 /* channels of cusrl_symmetrize_mean_var (one workgroup, LDS-staged) */
 
 #define CUSRL_E_INVALID (-1)     /* NULL pointer, negative size, inconsistent arguments */
 #define CUSRL_E_TOO_MANY (-2)    /* n_fields > CUSRL_MAX_FIELDS */
@@ -697,6 +699,60 @@ int cusrl_sumsq_fwd_bwd(const float *x, int64_t n, double loss_scale, double gra
  * target 1): loss_out[0] = weight * mean BCE-with-logits = (BCE(D(agent), 0) + BCE(D(expert), 1)) / 2 * loss_weight
  * (amp.py:143-147), d_logit = weight * (sigmoid(logit) - target) / (2 rows).  One launch instead of ~10 torch ops. */
 int cusrl_bce_pair_fwd_bwd(const float *logit, int64_t rows, float weight, float *loss_out, float *d_logit, void *stream);
+
+
+/* ---- Mirror symmetry — cusrl/hook/auxiliary/symmetry.py:30-62,155-356, cusrl/hook/mdp/observation.py:213-217 (ABI 7) ----
+ * A mirror table (int32, device) describes MirrorDef(destination_indices, flipped_indices), out[j] = in[dest[j]] * (-1 if j is
+ * flipped else 1), out width C_out = len(dest), in width C_in:
+ *   table[0 .. C_out)                      code of output column j: dest[j] | (flipped ? 1u << 31 : 0)
+ *   table[C_out .. C_out + C_in + 1)       offsets into the inverse list, per input column (CSR)
+ *   table[C_out + C_in + 1 .. 2 C_out + C_in + 1)  inverse list: the codes (output column | flip bit) that read input column i,
+ *                                          in increasing output column
+ * A negation is a sign flip: bit-exact against `x * -1` for every non-NaN x, signed zeros included.
+ *
+ * One field of cusrl_mirror_rows: rows r in [0, rows) of src [R, src_width] (row stride src_stride elements) go to
+ * dst[r * dst_stride + dst_offset + j], j in [0, width): a copy (table == NULL, width == src_width) or the mirror through
+ * `table` (width = C_out, src_width = C_in).  dst_stride / dst_offset let one launch write the [R, 2, C] rows of
+ * SymmetricDataAugmentation (original half copied, mirrored half through the table) and the repeated narrow leaves
+ * ([R, 2, 1] advantage: two copies).  Bytes moved: rows * 4 (src_width read + width written) per field. */
+typedef struct {
+    const float *src;
+    int64_t src_stride;
+    float *dst;
+    int64_t dst_stride;
+    int64_t dst_offset;
+    const int32_t *table;
+    int32_t width;
+    int32_t src_width;
+} cusrl_mirror_field_t;
+
+/* All fields in ONE launch (`fields` is a HOST array, passed by value to the kernel).  rows == 0 launches nothing. */
+int cusrl_mirror_rows(const cusrl_mirror_field_t *fields, int n_fields, int64_t rows, void *stream);
+
+/* Gradient of the mirror: grad_in[r, i] = sum over the output columns j that read i, in increasing j, of
+ * sign_j * grad_out[r, j] (fp32, fixed order: a non-bijective map gives the same bits every time); a column nobody reads gets 0.
+ * grad_out [rows, C_out] (row stride go_stride), grad_in [rows, C_in] (row stride gi_stride). */
+int cusrl_mirror_rows_bwd(const float *grad_out, int64_t go_stride, float *grad_in, int64_t gi_stride, const int32_t *table,
+                          int64_t c_in, int64_t c_out, int64_t rows, void *stream);
+
+/* MirrorSymmetryLoss.objective (symmetry.py:204-231) forward AND backward in one pass, C_in == C_out == A:
+ *   loss_out[0] = weight * mean((mu - M(mu_m))^2) over [B, A]
+ *   loss_out[1] = weight * mean((sigma - |M(sigma_m)|)^2) when sigma != NULL (else 0)
+ * mu = the current action mean, mu_m = the mean the actor gives for the mirrored observations, both [B, A] contiguous.
+ * sigma / sigma_m: [B, A], or with std_vector != 0 the [A] vector the actor repeats over the rows (the term is then the
+ * mean over A, which is the mean of the repeated matrix).  Gradients of loss_out[0] + loss_out[1]: d_mu, d_mu_m [B, A]
+ * (d_mu_m already taken back through the mirror, fixed-order sums), d_sigma, d_sigma_m (the shape of sigma; abs' gradient is
+ * torch.sign, 0 at 0).  fp64 block partials; partials: double[2 * cusrl_mirror_mse_num_partials(B * A)].  Beyond one
+ * block a one-block finalize follows.  Nothing is read back to the host. */
+int cusrl_mirror_mse_fwd_bwd(const float *mu, const float *mu_m, const float *sigma, const float *sigma_m, int std_vector,
+                             const int32_t *table, int64_t B, int64_t A, double weight, float *loss_out, float *d_mu,
+                             float *d_mu_m, float *d_sigma, float *d_sigma_m, double *partials, void *stream);
+int64_t cusrl_mirror_mse_num_partials(int64_t n);
+
+/* The symmetric statistics of ObservationNormalization._update_rms_impl (observation.py:213-217), in place on fp32 mean / var
+ * [C] (C_in == C_out == C <= CUSRL_MAX_SYMMETRIZE_CHANNELS), one rounding per operation in the reference's order:
+ *   var = (var + |M(var)|) / 2 + (mean - M(mean))^2 / 4,  then  mean = (mean + M(mean)) / 2.  One workgroup. */
+int cusrl_symmetrize_mean_var(float *mean, float *var, const int32_t *table, int64_t C, void *stream);
 
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
