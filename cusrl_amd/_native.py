@@ -7,12 +7,13 @@ The library is the product: there is no CPU or eager fallback.  If it has not be
 from __future__ import annotations
 
 import ctypes
-import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 from pathlib import Path
 
-# (CUSRL_HIP_LIBRARY: another build of the same library — A/B runs of compile-time variants, profiles/r05/loss_variants_ab.txt)
-LIB_PATH = Path(os.environ.get("CUSRL_HIP_LIBRARY") or Path(__file__).resolve().parent / "libcusrl_hip.so")
+from cusrl_amd.utils import switches
+
+# (another build of the same library: A/B runs of compile-time variants, profiles/r05/loss_variants_ab.txt)
+LIB_PATH = Path(switches.read("HIP_LIBRARY") or Path(__file__).resolve().parent / "libcusrl_hip.so")
 ABI_VERSION = 7
 MAX_FIELDS = 24
 MAX_PACKED = 16
@@ -202,15 +203,11 @@ def lib() -> ctypes.CDLL:
 
 # The A/B scripts of rounds 2-5 drive the kernels' launch-shape / cache-policy overrides through CUSRL_* environment variables.
 # The library no longer reads the environment in its launch entry points (cusrl_set_option, ABI 6): the HOST translates them,
-# once, when it loads the library.  {environment variable: (option, {text: value})}; None = the integer as it stands.
+# once, when it loads the library.  {switch: (option,)} — the option's name first, as before; utils/switches.py maps each one's
+# text to the option's value.
 _ENVIRONMENT_OPTIONS = {
-    "CUSRL_GAE_POLICY": ("gae_policy", {"0": 1, "5": 6, "7": 8}),
-    "CUSRL_GAE_BLOCK": ("gae_block", None),
-    "CUSRL_LOSS_POLICY": ("loss_policy", {"0": 1, "1": 2}),
-    "CUSRL_PUSH_POLICY": ("push_policy", {"0": 1, "3": 2}),
-    "CUSRL_COLSUM_ROWS": ("colsum_rows", None),
-    "CUSRL_HEAD_ROWS": ("head_rows", None),
-    "CUSRL_GRU_BIAS_ROWS": ("gru_bias_rows", None),
+    "GAE_POLICY": ("gae_policy",), "GAE_BLOCK": ("gae_block",), "LOSS_POLICY": ("loss_policy",), "PUSH_POLICY": ("push_policy",),
+    "COLSUM_ROWS": ("colsum_rows",), "HEAD_ROWS": ("head_rows",), "GRU_BIAS_ROWS": ("gru_bias_rows",),
 }
 
 
@@ -226,16 +223,10 @@ def get_option(key: str) -> int:
 
 
 def _options_from_environment() -> None:
-    for variable, (key, mapping) in _ENVIRONMENT_OPTIONS.items():
-        text = os.environ.get(variable)
-        if text is None or text == "":
-            continue
-        try:
-            value = mapping[text] if mapping is not None else int(text)
-        except (KeyError, ValueError):
-            continue  # (an unknown value meant "the kernel's own rule" to the library, too)
-        if _lib.cusrl_set_option(key.encode(), value) != 0:
-            continue
+    for switch, (option,) in _ENVIRONMENT_OPTIONS.items():
+        value = switches.read(switch)
+        if value is not None:
+            _lib.cusrl_set_option(option.encode(), value)  # (a value the library refuses leaves the kernel's own rule, too)
 
 
 # Launch census: how often each C-ABI entry point was called through ``check`` (every ``ops`` function reports its

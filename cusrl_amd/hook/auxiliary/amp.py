@@ -6,7 +6,6 @@ running statistics stay torch / RunningMeanStd; the style-reward epilogue is one
 
 from __future__ import annotations
 
-import os
 
 import numpy as np
 import torch
@@ -14,6 +13,7 @@ from torch import Tensor, nn
 
 from cusrl_amd.nn.rms import RunningMeanStd
 from cusrl_amd.template.hook import Hook
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.misc import get_first, host_form
 
 __all__ = ["AdversarialMotionPrior", "GradientPenaltyLoss"]
@@ -172,9 +172,9 @@ class _ReluDiscriminatorObjective(torch.autograd.Function):
 class AdversarialMotionPrior(Hook):
     objective_draws_random = True  # torch.randint for the discriminator batch
     step_draws_random = True  # torch.randint for the step's expert transitions (post_step; the reference's amp.py:161)
-    # Extension: a Linear / ReLU discriminator takes the closed-form objective above (CUSRL_AMP_CLOSED_FORM=0 or this
+    # Extension: a Linear / ReLU discriminator takes the closed-form objective above (the switch off or this
     # attribute restore the autograd double backward, which any other discriminator keeps anyway).
-    closed_form_objective: bool = os.environ.get("CUSRL_AMP_CLOSED_FORM", "1") != "0"
+    closed_form_objective: bool = switches.read("AMP_CLOSED_FORM")
 
     def __init__(self, discriminator_factory, dataset_source=None, state_indices=None, batch_size: int | None = 512,
                  reward_scale: float = 1.0, loss_weight: float = 1.0, grad_penalty_weight: float = 5.0):

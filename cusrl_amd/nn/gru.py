@@ -20,12 +20,11 @@ kernels also take device-side ``lengths`` for an unsorted batch).
 
 from __future__ import annotations
 
-import os
-
 import torch
 from torch import Tensor
 
 from cusrl_amd import ops
+from cusrl_amd.utils import switches
 
 __all__ = ["gru_forward", "gru_supported", "lstm_forward", "rnn_forward"]
 
@@ -365,7 +364,7 @@ def _plan(lengths: Tensor | None, input: Tensor) -> _LengthPlan | None:
 
 def gru_supported(module: torch.nn.RNNBase, input) -> bool:
     """fp32 device tensors through a plain (uni-directional, time-major, dropout-free at this call) ``nn.GRU`` / ``nn.LSTM``."""
-    if os.environ.get("CUSRL_FUSED_RNN", "1") == "0":  # escape hatch / A-B switch: MIOpen's RNN for everything
+    if not switches.read("FUSED_RNN"):  # escape hatch / A-B switch: MIOpen's RNN for everything
         return False
     return (isinstance(input, Tensor) and input.is_cuda and input.dtype == torch.float32 and input.dim() == 3
             and not module.bidirectional and not module.batch_first and getattr(module, "proj_size", 0) == 0

@@ -5,7 +5,6 @@ what is hand-written here is the backward's non-GEMM work (ReLU masks, bias colu
 
 from __future__ import annotations
 
-import os
 from collections.abc import Iterable, Sequence
 from contextlib import contextmanager
 from dataclasses import dataclass
@@ -15,6 +14,7 @@ import torch
 from torch import nn
 from torch.nn.functional import linear
 
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.nest import iterate_nested
 
 __all__ = ["Linear", "LinearFp32", "fused_inference_layers", "linear_act", "Mlp", "Module", "ModuleFactory", "disable_autocast",
@@ -41,12 +41,12 @@ _plain_linear_depth = 0
 # Rows from which a differentiated fp32 linear layer on the GPU takes ``_WideBatchLinear``: EVERY batch size since round 5.  Up
 # to round 4 batches below 4096 rows went through torch's ``addmm`` backward, whose bias gradient is an ATen ``sum`` — a
 # global reduce_kernel with a semaphore zeroed by a memset node once the batch has >= ~1024 rows, and a captured step
-# containing those is not replayed reliably by this stack.  ``CUSRL_WIDE_LINEAR_MIN_ROWS`` restores
+# containing those is not replayed reliably by this stack.  The switch restores
 # a threshold for A/B runs and for the defect's reproduction (scripts/debug_amp_identity.py).
-_WIDE_MIN_ROWS = int(os.environ.get("CUSRL_WIDE_LINEAR_MIN_ROWS", "1"))
-# The first layer's backward as one launch (round 6, ops.input_layer_backward); CUSRL_INPUT_LAYER_KERNEL=0: the mask + column-sum
+_WIDE_MIN_ROWS = switches.read("WIDE_LINEAR_MIN_ROWS")
+# The first layer's backward as one launch (round 6, ops.input_layer_backward); off: the mask + column-sum
 # pass followed by the split-batch weight-gradient GEMM of rounds 2-5 (A/B switch)
-_INPUT_LAYER_KERNEL = os.environ.get("CUSRL_INPUT_LAYER_KERNEL", "1") != "0"
+_INPUT_LAYER_KERNEL = switches.read("INPUT_LAYER_KERNEL")
 
 
 # Backward shortcuts for a UNIT incoming gradient.  The loss summands of a step are differentiated as separate roots with a
@@ -280,9 +280,9 @@ class LinearFp32(nn.Linear):
             return linear(input.float(), self.weight.float(), None if self.bias is None else self.bias.float())
 
 
-# The no-grad pass of backbone + head as ONE launch (round 6, ops.mlp2_forward; CUSRL_FUSED_INFERENCE=0: the library GEMM chain,
+# The no-grad pass of backbone + head as ONE launch (round 6, ops.mlp2_forward; off: the library GEMM chain,
 # A/B switch).  Acting on 4096 envs is three launch-bound GEMMs + the sampling launch: 24 of the 37 us a captured env step takes.
-_FUSED_INFERENCE = os.environ.get("CUSRL_FUSED_INFERENCE", "1") != "0"
+_FUSED_INFERENCE = switches.read("FUSED_INFERENCE")
 
 
 def fused_inference_layers(backbone, head: nn.Linear, input, memory=None):

@@ -11,12 +11,12 @@ stream on a GPU buffer (indices are then uploaded, 8 B per sample).  The gather 
 
 from __future__ import annotations
 
-import os
 from collections.abc import Sequence
 
 import torch
 
 from cusrl_amd.template.buffer import Buffer, Sampler
+from cusrl_amd.utils import switches
 
 __all__ = ["AutoMiniBatchSampler", "DrawnEpochs", "MiniBatchSampler", "TemporalMiniBatchSampler"]
 
@@ -99,7 +99,7 @@ class MiniBatchSampler(Sampler):
         self.hot_fields: set[str] = set()
         # prefetch (extension, default): a device permutation for the next epoch is drawn on a second stream while the
         # current epoch's minibatches run (same generator stream of values; see iter_indices)
-        self.prefetch = prefetch and os.environ.get("CUSRL_PREFETCH_PERMUTATIONS", "1") != "0"
+        self.prefetch = prefetch and switches.read("PREFETCH_PERMUTATIONS")
         # Device permutations are drawn into PERSISTENT index buffers (two, alternating when drawing ahead): every
         # minibatch's index slice then lives at an address that repeats from update to update, and a captured minibatch
         # step can read it in place instead of through a copy into a static buffer (`persistent_indices`, template/graphs.py).

@@ -11,8 +11,6 @@ Differences that matter on MI355X (semantics unchanged):
 
 from __future__ import annotations
 
-import os
-
 from collections.abc import Callable, Iterable, Mapping, Sequence
 from contextlib import contextmanager
 from dataclasses import dataclass
@@ -27,6 +25,7 @@ from cusrl_amd.template.buffer import Buffer, Sampler
 from cusrl_amd.template.environment import EnvironmentSpec
 from cusrl_amd.template.hook import Hook, HookComposite
 from cusrl_amd.template.optimizer import OptimizerFactory, build_optimizer
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.config import CONFIG
 from cusrl_amd.utils.distributed import FlatGradients, UnjoinedStep, broadcast_parameters, reduce_gradients
 
@@ -256,17 +255,16 @@ class ActorCritic(Agent):
             self._graph_pool = torch.cuda.graph_pool_handle()
             # second branch of the captured minibatch step (critic forward / backward, hook/on_policy/value.py)
             self._branch_stream = torch.cuda.Stream(device=self.device)
-            # True / False force it; None (default, CUSRL_CONCURRENT_CRITIC unset) = per composition, where it measured faster
+            # True / False force it; None (default, the switch unset) = per composition, where it measured faster
             # (GraphedTrainStep._critic_branch)
-            forced = os.environ.get("CUSRL_CONCURRENT_CRITIC")
-            self.concurrent_critic = None if forced is None else forced != "0"
+            self.concurrent_critic = switches.read("CONCURRENT_CRITIC")
             # captured minibatch steps run the fused objective without its one-block finalize launch (ops.DeferredLoss)
-            self.defer_loss_finalize = os.environ.get("CUSRL_DEFER_LOSS_FINALIZE", "1") != "0"
+            self.defer_loss_finalize = switches.read("DEFER_LOSS_FINALIZE")
             self._graphed_act = GraphedAct(self)
         self.flat_gradients: FlatGradients | None = None
         self._unit_grads: dict[tuple, torch.Tensor] = {}
         # the value term of the stock composition as its own launch + root on the critic's branch of a captured step (A/B switch)
-        self._separate_value_term = os.environ.get("CUSRL_SEPARATE_VALUE_TERM", "1") != "0"
+        self._separate_value_term = switches.read("SEPARATE_VALUE_TERM")
         if isinstance(self.optimizer, torch.optim.Optimizer) and not self.grad_scaler_enabled:
             self.flat_gradients = FlatGradients(self.optimizer)
         self.flat_optimizer = None
@@ -641,7 +639,7 @@ class ActorCritic(Agent):
             flat.buffer.numel(), multi_rank=multi_rank, split_allreduce=CONFIG.split_gradient_allreduce,
             native_comm=multi_rank and distributed.native_comm() is not None,
             branch_stream=getattr(self, "_branch_stream", None) is not None, flat_adam=self.flat_optimizer is not None,
-            hooks=[hook for hook in self.hook if hook._active], two_window=os.environ.get("CUSRL_TWO_WINDOW_STEP", "1") != "0")
+            hooks=[hook for hook in self.hook if hook._active], two_window=switches.read("TWO_WINDOW_STEP"))
 
     @property
     def _split_plan(self) -> bool:

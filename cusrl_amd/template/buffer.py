@@ -15,13 +15,13 @@ env axis is unit-stride for C = 1 leaves (reward, value, flags) and rows are C*4
 
 from __future__ import annotations
 
-import os
 from collections.abc import Callable, Iterator, Mapping, MutableMapping, Sequence
 from typing import Any
 
 import torch
 
 from cusrl_amd import ops
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.config import device as resolve_device
 from cusrl_amd.utils.nest import get_schema, iterate_nested, reconstruct_nested
 
@@ -222,7 +222,7 @@ class Buffer(MutableMapping):
         # the record pays when sampled rows miss the caches (a random row costs whole 128-byte lines out of HBM); while the
         # packed leaves fit L2 + Infinity Cache the plain per-leaf gather is faster and needs no pack launch at all
         # (config 2: 25 MB, 5.5 vs 6.7 us per minibatch; measured break-even between 64 and 256 MB)
-        self.record_threshold_bytes = int(os.environ.get("CUSRL_RECORD_THRESHOLD_BYTES", 128 << 20))
+        self.record_threshold_bytes = switches.read("RECORD_THRESHOLD_BYTES")
         self._pack = None
         self._pack_hot = None
         self._hot_fields: set[str] = set()

@@ -37,11 +37,11 @@ simply does not opt in (``rollout_capture_safe``).  ``compile=False`` (the defau
 from __future__ import annotations
 
 import gc
-import os
 from typing import Any
 
 import torch
 
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.metrics import MetricTap
 
 __all__ = ["GraphedAct", "GraphedEpochs", "GraphedRegion", "GraphedRolloutStep", "GraphedTrainStep", "capture_signature",
@@ -180,7 +180,7 @@ class _Capture:
         # not capture-safe invalidates OUR capture.  The capturing thread's own discipline is what matters here.
         from cusrl_amd.utils import distributed
 
-        mode = os.environ.get("CUSRL_CAPTURE_ERROR_MODE") or ("thread_local" if distributed.enabled() else "global")
+        mode = switches.read("CAPTURE_ERROR_MODE") or ("thread_local" if distributed.enabled() else "global")
         try:
             with torch.cuda.graph(graph, stream=stream, pool=pool, capture_error_mode=mode):
                 result = fn()
@@ -205,7 +205,7 @@ class _Capture:
         from cusrl_amd import ops
 
         self.census = ops.graph_census(graph)
-        if self.census["memset"] and os.environ.get("CUSRL_GRAPH_MEMSETS", "replace") != "keep":
+        if self.census["memset"] and switches.read("GRAPH_MEMSETS") != "keep":
             # This stack does not replay memset nodes reliably (scripts/probe_aten_reduce_capture.py) and
             # ATen's split reductions — any `.sum()` / `.mean()` over >= ~1024 rows a hook issues — zero their semaphores
             # with one: every memset node becomes a fill-kernel node with the same edges before the graph is instantiated.
@@ -425,8 +425,7 @@ def epoch_graphs_mode() -> str:
     one join per step and the gather off the critical path the device needs less time per step than the HOST needs to issue one
     (the replay of a two-branch 22-node graph costs the host ~80 us, the Python around it as much again:
     profiles/r06/experiments/), and what the device gained was lost to replays that arrive late."""
-    value = os.environ.get("CUSRL_EPOCH_GRAPHS", "update")
-    return {"0": "off", "1": "epoch", "epoch": "epoch"}.get(value, "update")
+    return switches.read("EPOCH_GRAPHS")
 
 
 def epoch_graphs_enabled() -> bool:
@@ -458,10 +457,10 @@ class GraphedEpochs:
         self.mode = epoch_graphs_mode()
         self.enabled = self.mode != "off"
         self.replays = 0
-        # the gather of the next step's rows ahead of that step.  CUSRL_PREFETCH_GATHER: "tail" (default) — at the tail of the
+        # the gather of the next step's rows ahead of that step: "tail" (default) — at the tail of the
         # running step's critic branch, which ends before the actor's (no third stream; compositions without the branch issue it
         # behind the step); "side" — forked to a stream of its own at the start of the running step; "0" — inside the step
-        self.prefetch = os.environ.get("CUSRL_PREFETCH_GATHER", "tail")
+        self.prefetch = switches.read("PREFETCH_GATHER")
         self.gather_stream = torch.cuda.Stream(device=agent.device) if self.prefetch == "side" else None
         self.stores: dict[tuple, dict[str, torch.Tensor]] = {}
 
@@ -774,12 +773,12 @@ class GraphedRolloutStep:
         # ... and, once every step of a rollout has its graph, the WHOLE rollout as one graph (run_rollout)
         self.rollouts: dict[tuple, dict] = {}
         self.rollout_replays = 0
-        self.whole_rollouts = os.environ.get("CUSRL_WHOLE_ROLLOUT_GRAPH", "1") != "0"
-        self.fuse_epilogue_push = os.environ.get("CUSRL_FUSE_EPILOGUE_PUSH", "1") != "0"  # A/B switch
+        self.whole_rollouts = switches.read("WHOLE_ROLLOUT_GRAPH")
+        self.fuse_epilogue_push = switches.read("FUSE_EPILOGUE_PUSH")
         # the exploration noise of a whole rollout drawn AHEAD of it (an env that leaves torch's generator alone: the T draws are
         # the generator's only consumers inside the rollout — issued before its launch, on a side stream, they run while the
-        # previous update does, and the captured env step is one launch shorter); CUSRL_PREDRAW_NOISE=0: drawn inside the step
-        self.predraw_noise = os.environ.get("CUSRL_PREDRAW_NOISE", "1") != "0"
+        # previous update does, and the captured env step is one launch shorter); off: drawn inside the step
+        self.predraw_noise = switches.read("PREDRAW_NOISE")
         self._noise: torch.Tensor | None = None
         self._noise_stream: torch.cuda.Stream | None = None
         self._noise_ready: torch.cuda.Event | None = None

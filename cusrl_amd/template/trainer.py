@@ -4,7 +4,6 @@ dumps, trial folders and console boxes of the reference are out of scope (SURVEY
 
 from __future__ import annotations
 
-import os
 from collections.abc import Callable, Iterable, Mapping
 from typing import Any
 
@@ -12,7 +11,7 @@ import torch
 
 from cusrl_amd.template.agent import Agent, AgentFactory
 from cusrl_amd.template.environment import Environment, get_done_indices, update_observation_and_state
-from cusrl_amd.utils import distributed
+from cusrl_amd.utils import distributed, switches
 from cusrl_amd.utils.timing import Timer
 
 __all__ = ["EnvironmentStats", "Trainer", "TrainerHook"]
@@ -283,10 +282,11 @@ class Trainer:
         self._last_info: dict[str, float] = {}
         self._pending_log: tuple | None = None
         # the log of an iteration is read, averaged and written AFTER the next rollout has been launched (A/B switch)
-        self.pipeline_logs = os.environ.get("CUSRL_PIPELINE_LOGS", "1") != "0"
+        pipeline = switches.read("PIPELINE_LOGS")
+        self.pipeline_logs = pipeline != "off"
         # "late" (A/B; measured 0.12 ms SLOWER): the pending log is written behind the update's launches instead of between the
         # rollout's launch and the update's — the host then issues the next rollout while the update still runs
-        self._late_flush = os.environ.get("CUSRL_PIPELINE_LOGS") == "late"
+        self._late_flush = pipeline == "late"
         self.host_thread_cpus: list[int] = []
         if pin_host_thread and self.agent.device.type == "cuda":  # extension: NUMA-local placement of the driving thread
             from cusrl_amd.utils.affinity import pin_host_thread as pin
@@ -304,7 +304,7 @@ class Trainer:
         self._epilogue_ok: bool | None = None
         self._graphed_rollout = None
         self._rollout_split: tuple[float, float] | None = None
-        self.capture_rollout = os.environ.get("CUSRL_CAPTURE_ROLLOUT", "1") != "0"  # A/B switch of the captured env step
+        self.capture_rollout = switches.read("CAPTURE_ROLLOUT")  # A/B switch of the captured env step
 
     def run_training_loop(self):
         """Checkpoints as the reference does (trainer.py:280-294): once before the loop, every ``checkpoint_interval``
@@ -351,7 +351,7 @@ class Trainer:
         with timer.record("agent"):
             agent_info = agent.update()
         self.stats.close_frame(frame)  # (no-op when the update's staged read took the statistics along)
-        self.flush()  # (a log still pending here: `CUSRL_PIPELINE_LOGS=late` — written behind this iteration's launches, A/B)
+        self.flush()  # (a log still pending here: the "late" flush — written behind this iteration's launches, A/B)
         self._pending_log = (agent_info, frame, timer.detach(), self.iteration)
         if not pipelined:
             self.flush()

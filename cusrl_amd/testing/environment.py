@@ -8,11 +8,11 @@ reset returning fresh N(0, 1) rows — everything generated on the env's device 
 
 from __future__ import annotations
 
-import os
 
 import torch
 
 from cusrl_amd.template.environment import Environment
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.config import device as resolve_device
 
 __all__ = ["DummyTorchEnvironment", "SyntheticEnvironment"]
@@ -32,12 +32,12 @@ class SyntheticEnvironment(Environment):
         # host synchronisation and replay whole env steps from hipGraphs (template/environment.py `capturable`)
         self.capturable = bool(capturable) and self.device.type == "cuda"
         self._flag_probs = torch.tensor([terminate_prob, truncate_prob], dtype=torch.float32, device=self.device).view(2, 1, 1)
-        # fused (default on a GPU, CUSRL_FUSED_ENV=0 / fused=False for the torch-generator form): a whole step — observation,
+        # fused (default on a GPU, the switch off / fused=False for the torch-generator form): a whole step — observation,
         # reward, both flags and the rows for the resets — from ONE HIP launch (`cusrl_synthetic_env_step`: Philox keyed on a
         # seed drawn from torch's generator here and a device-resident step counter) instead of five generator launches; the
         # same distributions, another random stream.  No privileged state in this form.
         if fused is None:
-            fused = os.environ.get("CUSRL_FUSED_ENV", "1") != "0"
+            fused = switches.read("FUSED_ENV")
         self.fused = bool(fused) and self.device.type == "cuda" and state_dim is None
         # (the fused step and the reset rows it leaves behind come from the env's own Philox stream: nothing is drawn from torch's
         # generator while the trainer drives the env — template/environment.py `generator_free`)

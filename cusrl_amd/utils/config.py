@@ -12,6 +12,8 @@ import os
 
 import torch
 
+from cusrl_amd.utils import switches
+
 __all__ = ["CONFIG", "configure_distributed", "device", "is_autocast_available"]
 
 
@@ -28,29 +30,29 @@ class _Config:
         # Test-only: every rank of the job drives cuda:0 and the process group is gloo (RCCL refuses two ranks on one
         # device; gloo stages device tensors through the host).  Lets a 1-GPU box run the whole multi-rank agent path —
         # parameter broadcast, per-step gradient averaging, merged advantage statistics, rank-averaged logs — end to end.
-        self.share_gpu = self.distributed and env.get("CUSRL_SHARE_GPU", "0") == "1"
+        self.share_gpu = self.distributed and switches.read("SHARE_GPU")
         self._device = torch.device((f"cuda:{0 if self.share_gpu else self.local_rank}") if self.cuda else "cpu")
         # Collectives of the hot path through the C ABI (cusrl_allreduce_mean / cusrl_allgather / cusrl_broadcast on a
         # communicator owned by libcusrl_hip.so) instead of torch.distributed: they are enqueued on the step's stream,
         # so with compile=True the gradient all-reduce is captured INSIDE the minibatch step's hipGraph.  This is the
         # DEFAULT route of an RCCL job (utils/distributed.py native_comm: the communicator is created over the existing
         # process group and checked against it once; a failure is logged and the job falls back to torch.distributed's
-        # collectives).  CUSRL_NATIVE_COLLECTIVES=0 (or CONFIG.native_collectives = False before the agent is built)
+        # collectives).  Switching it off (or CONFIG.native_collectives = False before the agent is built)
         # forces the torch.distributed route: eager all-reduce between two graphs per minibatch step.
-        self.native_collectives = env.get("CUSRL_NATIVE_COLLECTIVES", "1") != "0"
+        self.native_collectives = switches.read("NATIVE_COLLECTIVES")
         # Per-network split of the gradient all-reduce (cusrl/utils/distributed.py:145-172 is ONE all-reduce behind the whole
         # backward): the critic's parameters are differentiated first, their window of the flat buffer is assembled and
         # averaged on the branch stream through a second communicator WHILE the actor's backward runs; the actor's window
         # follows on the main stream.  Same kernels, same operands: bit-identical parameters (tests/test_distributed_*).
         # Off by default — whether two half-size collectives overlapped with backward beat one full-size collective behind
         # it on 8 xGMI-connected ranks has never been measured (no multi-GPU box in any round); bench.py prints both routes'
-        # durations so that the first such session is one A/B.  CUSRL_SPLIT_ALLREDUCE=1 or CONFIG.split_gradient_allreduce.
-        self.split_gradient_allreduce = env.get("CUSRL_SPLIT_ALLREDUCE", "0") == "1"
+        # durations so that the first such session is one A/B.
+        self.split_gradient_allreduce = switches.read("SPLIT_ALLREDUCE")
         # Building an agent on a GPU loads the measured rocBLAS / hipBLASLt kernel selection through PyTorch TunableOp
         # (utils/tuning.py) — a PROCESS-WIDE setting: other torch code in the process gets the same kernel choice for
-        # the GEMM shapes listed in the file.  CONFIG.tuned_gemms = False before the first agent is built (or
-        # CUSRL_TUNED_GEMMS=0) leaves torch untouched.
-        self.tuned_gemms = env.get("CUSRL_TUNED_GEMMS", "1") != "0"
+        # the GEMM shapes listed in the file.  CONFIG.tuned_gemms = False before the first agent is built (or the switch
+        # set to 0) leaves torch untouched.
+        self.tuned_gemms = switches.read("TUNED_GEMMS") is not False
 
     @property
     def device(self) -> torch.device:

@@ -13,7 +13,6 @@ SURVEY.md §5), so the design goal is the fewest, copy-free collectives:
 
 from __future__ import annotations
 
-import os
 from contextlib import contextmanager
 from collections.abc import Iterable, Sequence
 from dataclasses import dataclass
@@ -22,6 +21,7 @@ from typing import Any, TypeVar
 import numpy as np
 import torch
 
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.config import CONFIG, configure_distributed
 
 __all__ = [
@@ -253,16 +253,16 @@ def establish_native_comm(factory, device, rank: int, world: int, capture_probe=
     Returns ``(comm, "")`` or ``(None, reason)`` — the same outcome on every rank.  A communicator that may have a
     half-issued collective in flight is aborted (``cusrl_comm_abort``), never destroyed (destroy waits for its kernels).
     ``CUSRL_COMM_FAULT = "<stage>:<rank>"`` injects a failure (tests of exactly this protocol)."""
-    fault_stage, _, fault_rank = os.environ.get("CUSRL_COMM_FAULT", "").partition(":")
+    fault_stage, _, fault_rank = switches.read("COMM_FAULT").partition(":")
 
-    def faulty(stage: str) -> bool:
-        return fault_stage == stage and fault_rank != "" and int(fault_rank) == rank
+    def inject(stage: str) -> None:
+        if fault_stage == stage and fault_rank != "" and int(fault_rank) == rank:
+            raise RuntimeError("injected fault (CUSRL_COMM_FAULT)")
 
     # ---- stage 1: creation
     comm, problem = None, ""
     try:
-        if faulty("create"):
-            raise RuntimeError("injected fault (CUSRL_COMM_FAULT)")
+        inject("create")
         comm = factory()
     except Exception as error:
         problem = f"{type(error).__name__}: {error}"
@@ -275,8 +275,7 @@ def establish_native_comm(factory, device, rank: int, world: int, capture_probe=
     probe, expect = base * (rank + 1), base * ((world + 1) / 2)  # mean over ranks of (rank + 1)
     side = torch.cuda.Stream(device=device) if device.type == "cuda" else None
     try:
-        if faulty("probe"):
-            raise RuntimeError("injected fault (CUSRL_COMM_FAULT)")
+        inject("probe")
         if side is not None:
             side.wait_stream(torch.cuda.current_stream(device))
             with torch.cuda.stream(side):
@@ -305,8 +304,7 @@ def establish_native_comm(factory, device, rank: int, world: int, capture_probe=
     if capture_probe is not None:
         captured = None
         try:
-            if faulty("capture"):
-                raise RuntimeError("injected fault (CUSRL_COMM_FAULT)")
+            inject("capture")
             captured = capture_probe(comm, rank, world)
         except Exception as error:
             problem = f"cusrl_allreduce_mean inside a hipGraph: {type(error).__name__}: {error}"
@@ -315,8 +313,7 @@ def establish_native_comm(factory, device, rank: int, world: int, capture_probe=
             return None, problem or "another rank could not capture the all-reduce"
         graph, probe, expect, side = captured
         try:
-            if faulty("replay"):
-                raise RuntimeError("injected fault (CUSRL_COMM_FAULT)")
+            inject("replay")
             if side is not None:
                 side.wait_stream(torch.cuda.current_stream(device))
                 with torch.cuda.stream(side):

@@ -17,11 +17,11 @@ fused-adam), and the learning rate is read from device memory so hipGraph replay
 from __future__ import annotations
 
 import functools
-import os
 
 import torch
 
 from cusrl_amd import ops
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.distributed import FlatGradients
 
 __all__ = ["FlatAdam"]
@@ -205,8 +205,7 @@ class FlatAdam:
             # front of them (it follows a node's first edge): behind the all-reduce of a multi-rank step that must be the main
             # stream's — the longer chain, the actor's — so that its step launch follows the collective without a queue hop.
             # (a single process: measured neutral, profiles/r06/experiments/step_order_single_process_ab.txt — left as it was)
-            main_first = (unjoined.averaged and os.environ.get("CUSRL_NORMED_MAIN_FIRST", "1") != "0"
-                          or os.environ.get("CUSRL_STEP_MAIN_FIRST") == "1")
+            main_first = (unjoined.averaged and switches.read("NORMED_MAIN_FIRST") or switches.read("STEP_MAIN_FIRST"))
             if main_first:
                 main_window(), critic_window()
             else:

@@ -11,6 +11,7 @@ from typing import Any
 import numpy as np
 import torch
 
+from cusrl_amd.utils import switches
 from cusrl_amd.utils.config import CONFIG
 
 __all__ = ["MISSING", "camel_to_snake", "get_first", "host_form", "set_global_seed"]
@@ -40,7 +41,7 @@ def host_form(what: str) -> None:
     an MI355X every hook takes its HIP entry point, and a CPU tensor reaching one of these places raises — unless the
     process opted in with ``CUSRL_HOST_FORMS=1``, which only the repository's own test infrastructure does (the host-logic
     tests and the gloo workers run in processes without a GPU and exercise the hooks' bookkeeping there)."""
-    if os.environ.get("CUSRL_HOST_FORMS") != "1":
+    if not switches.read("HOST_FORMS"):
         raise RuntimeError(
             f"cusrl_amd: {what} received CPU tensors; the rollout + PPO-update hot path only runs as HIP kernels on an MI355X "
             "(no CPU fallback by design).  Test infrastructure without a GPU sets CUSRL_HOST_FORMS=1.")

@@ -12,11 +12,12 @@ everything on one stream, cusrl/template/actor_critic.py:296-320.)
 
 from __future__ import annotations
 
-import os
 import time
 from collections.abc import Sequence
 
 import torch
+
+from cusrl_amd.utils import switches
 
 __all__ = ["runs_beside", "side_stream"]
 
@@ -57,12 +58,12 @@ def side_stream(device: torch.device, beside: Sequence["torch.cuda.Stream"] | No
     the last candidate when none passes (a part with a single queue: correct, just serial).  Never call while capturing."""
     device = torch.device(device)
     busy = list(beside) if beside is not None else [torch.cuda.current_stream(device)]
-    if torch.cuda.is_current_stream_capturing() or os.environ.get("CUSRL_SIDE_STREAM_PROBE", "1") == "0":  # (A/B switch)
+    if torch.cuda.is_current_stream_capturing() or not switches.read("SIDE_STREAM_PROBE"):  # (A/B switch)
         return torch.cuda.Stream(device=device)
     # (Not a high-priority stream, although the runtime keeps a pool of hardware queues per priority and such a stream could share a
     # queue with nothing else here: with the six randperm draws of an update on one, the single-process iteration went from 4.8 to
     # 10.3 ms and a one-rank iteration from 5.0 to 7.2 ms on this stack — profiles/r06/experiments/side_stream_priority_ab.txt.)
-    high = os.environ.get("CUSRL_SIDE_STREAM_PRIORITY", "0") == "1"  # (A/B switch, off: see above)
+    high = switches.read("SIDE_STREAM_PRIORITY")  # (A/B switch, off: see above)
     candidate = torch.cuda.Stream(device=device, priority=-1) if high else torch.cuda.Stream(device=device)
     rejected = []  # (kept alive until the choice is made: a released stream would be handed out again)
     for _ in range(_CANDIDATES):

@@ -14,6 +14,8 @@ from pathlib import Path
 
 import torch
 
+from cusrl_amd.utils import switches
+
 __all__ = ["enable_tuned_gemms", "TUNED_GEMMS_FILE"]
 
 TUNED_GEMMS_FILE = Path(__file__).resolve().parent.parent / "tuned_gemms_gfx950.csv"
@@ -26,9 +28,9 @@ def enable_tuned_gemms(path: str | os.PathLike | None = None) -> bool:
     if _state["enabled"] is not None and path is None:
         return bool(_state["enabled"])
     active = False
-    choice = os.environ.get("CUSRL_TUNED_GEMMS", "1")
-    file = Path(path) if path is not None else (TUNED_GEMMS_FILE if choice in ("0", "1") else Path(choice))
-    if choice != "0" and torch.cuda.is_available() and file.exists():
+    choice = switches.read("TUNED_GEMMS")  # False: off, True: the shipped file, else the path of another one
+    file = Path(path) if path is not None else (TUNED_GEMMS_FILE if isinstance(choice, bool) else Path(choice))
+    if choice is not False and torch.cuda.is_available() and file.exists():
         import torch.cuda.tunable as tunable
 
         if not tunable.tuning_is_enabled() or not tunable.is_enabled():  # a user's own TunableOp session is left alone

@@ -14,6 +14,7 @@ def child():
     import torch
 
     from cusrl_amd import ops
+    from cusrl_amd.utils import switches
     from kernel_bench import timeit
 
     B = 24576
@@ -23,7 +24,7 @@ def child():
         g, y = f(B, H), torch.relu(f(B, H))
         out.append(timeit(lambda: ops.relu_backward_bias(g, y, defer=True), 400))
         out.append(timeit(lambda: ops.relu_backward_bias(g, y), 400))
-    print(f"rows/block {os.environ.get('CUSRL_COLSUM_ROWS', 'default'):>8}: [B,256] deferred {out[0]:6.2f} us, with finalize {out[1]:6.2f} us | "
+    print(f"rows/block {switches.read('COLSUM_ROWS') or 'default':>8}: [B,256] deferred {out[0]:6.2f} us, with finalize {out[1]:6.2f} us | "
           f"[B,128] deferred {out[2]:6.2f} us, with finalize {out[3]:6.2f} us")
 
 

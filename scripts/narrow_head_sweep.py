@@ -14,6 +14,7 @@ def child():
     import torch
 
     from cusrl_amd import ops
+    from cusrl_amd.utils import switches
     from kernel_bench import timeit
 
     B = 24576
@@ -24,7 +25,7 @@ def child():
         g, w = f(B, O), f(O, 128)
         out.append(timeit(lambda: ops.narrow_linear_backward(g, h, w, relu_input=True, defer=True), 400))
         out.append(timeit(lambda: ops.narrow_linear_backward(g, h, w), 400))
-    print(f"rows/block {os.environ.get('CUSRL_HEAD_ROWS', 'default'):>8}: 128->12 relu+deferred {out[0]:6.2f} us, plain {out[1]:6.2f} us | "
+    print(f"rows/block {switches.read('HEAD_ROWS') or 'default':>8}: 128->12 relu+deferred {out[0]:6.2f} us, plain {out[1]:6.2f} us | "
           f"128->1 relu+deferred {out[2]:6.2f} us, plain {out[3]:6.2f} us")
 
 

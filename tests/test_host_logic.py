@@ -1170,12 +1170,147 @@ def test_ahead_of_time_noise_draws_are_opt_in_contracts():
     assert actor.pending_noise is None and actor.noise_shape is None
 
 
-def test_side_stream_module_names_its_switches():
-    """``utils/streams.py`` needs a GPU to do anything; what a CPU process can hold is that it imports and documents its switches."""
-    from cusrl_amd.utils import streams
+# ------------------------------------------------------------------------------------------------ environment switches
+_ON = {None: True, "": True, "0": False, "1": True, "bogus": True}      # parent: os.environ.get(X, "1") != "0"
+_OFF = {None: False, "": False, "0": False, "1": True, "bogus": False}  # parent: os.environ.get(X) == "1"
+
+
+def _text(unset, *documented):
+    """Parent: the text as it stands (``os.environ.get(X, unset)``)."""
+    return {None: unset, **{text: text for text in ("", "0", "1", "bogus") + documented}}
+
+
+def _option(**known):
+    """Parent (_native._options_from_environment): unset, empty and unknown texts are skipped (None here)."""
+    return {None: None, "": None, "0": None, "1": None, "bogus": None, **known}
+
+
+# {switch: {text (None: unset): parsed value, or the exception it raises}}, written down from the parent commit's expression at
+# each read site — not produced by the registry
+_SWITCH_TABLE = {
+    **{key: _ON for key in (
+        "NATIVE_COLLECTIVES", "CAPTURE_ROLLOUT", "WHOLE_ROLLOUT_GRAPH", "DEFER_LOSS_FINALIZE", "PREFETCH_PERMUTATIONS", "FUSED_RNN",
+        "AMP_CLOSED_FORM", "SEPARATE_VALUE_TERM", "INPUT_LAYER_KERNEL", "FUSED_INFERENCE", "TWO_WINDOW_STEP", "SIDE_STREAM_PROBE",
+        "NORMED_MAIN_FIRST", "PREDRAW_NOISE", "FUSE_EPILOGUE_PUSH", "FUSED_ENV")},
+    **{key: _OFF for key in ("SPLIT_ALLREDUCE", "SIDE_STREAM_PRIORITY", "STEP_MAIN_FIRST", "HOST_FORMS", "SHARE_GPU")},
+    # int(os.environ.get(X, default))
+    "RECORD_THRESHOLD_BYTES": {None: 128 << 20, "": ValueError, "0": 0, "1": 1, "268435456": 268435456, "bogus": ValueError},
+    "WIDE_LINEAR_MIN_ROWS": {None: 1, "": ValueError, "0": 0, "1": 1, "4096": 4096, "bogus": ValueError},
+    # forced = os.environ.get(X); None if forced is None else forced != "0"
+    "CONCURRENT_CRITIC": {None: None, "": True, "0": False, "1": True, "bogus": True},
+    # os.environ.get(X, "replace") != "keep"
+    "GRAPH_MEMSETS": {None: "replace", "": "replace", "0": "replace", "1": "replace", "keep": "keep", "replace": "replace",
+                      "bogus": "replace"},
+    # {"0": "off", "1": "epoch", "epoch": "epoch"}.get(os.environ.get(X, "update"), "update")
+    "EPOCH_GRAPHS": {None: "update", "": "update", "0": "off", "1": "epoch", "epoch": "epoch", "update": "update", "bogus": "update"},
+    # pipeline_logs = os.environ.get(X, "1") != "0"; _late_flush = os.environ.get(X) == "late"
+    "PIPELINE_LOGS": {None: "on", "": "on", "0": "off", "1": "on", "late": "late", "bogus": "on"},
+    # choice = os.environ.get(X, "1"); off: choice == "0"; the shipped file: choice in ("0", "1"); else Path(choice)
+    "TUNED_GEMMS": {None: True, "": "", "0": False, "1": True, "/tmp/selection.csv": "/tmp/selection.csv", "bogus": "bogus"},
+    "HIP_LIBRARY": _text(None, "/tmp/libcusrl_hip.so"),             # os.environ.get(X) or <the library beside the package>
+    "RCCL_LIBRARY": _text(None, "/tmp/librccl.so"),                 # (the host never reads it)
+    "CAPTURE_ERROR_MODE": _text(None, "global", "thread_local"),    # os.environ.get(X) or (by kind of job)
+    "PREFETCH_GATHER": _text("tail", "tail", "side"),               # os.environ.get(X, "tail"), compared against "side" and "tail"
+    "COMM_FAULT": _text("", "probe:0"),                             # os.environ.get(X, "").partition(":")
+    "GAE_POLICY": _option(**{"0": 1, "5": 6, "7": 8}),
+    "LOSS_POLICY": _option(**{"0": 1, "1": 2}),
+    "PUSH_POLICY": _option(**{"0": 1, "3": 2}),
+    "GAE_BLOCK": _option(**{"0": 0, "1": 1, "128": 128, "256": 256}),   # int(text) as it stands
+    "COLSUM_ROWS": _option(**{"0": 0, "1": 1, "64": 64}),
+    "HEAD_ROWS": _option(**{"0": 0, "1": 1, "96": 96}),
+    "GRU_BIAS_ROWS": _option(**{"0": 0, "1": 1, "4": 4, "8": 8, "16": 16, "32": 32}),
+}
+
+
+def test_every_switch_parses_as_its_read_site_did(monkeypatch):
+    """``switches.read`` against the parent commit's expression of every read site: unset, empty, ``0``, ``1``, each documented value
+    and an undocumented text — leniency included (only the two plain integers raise)."""
+    from cusrl_amd.utils import switches
+
+    assert set(_SWITCH_TABLE) == set(switches.SWITCHES) == {switch.name.removeprefix("CUSRL_") for switch in switches.declared()}
+    for key, cases in _SWITCH_TABLE.items():
+        assert {None, "", "0", "1", "bogus"} <= set(cases), key
+        for text, expected in cases.items():
+            if text is None:
+                monkeypatch.delenv(f"CUSRL_{key}", raising=False)
+            else:
+                monkeypatch.setenv(f"CUSRL_{key}", text)
+            if expected is ValueError:
+                with pytest.raises(ValueError):
+                    switches.read(key)
+            else:
+                value = switches.read(key)
+                assert value == expected and type(value) is type(expected), (key, text, value)
+        monkeypatch.delenv(f"CUSRL_{key}", raising=False)
+    for switch in switches.declared():
+        assert switch.kind in ("on", "off", "choice", "int", "path", "text") and switch.effect and switch.mark in ("", "test-only", "library")
+        assert set(switch.moment.split(", ")) <= {"import", "construct", "call"}, switch.name
+        if switch.kind in ("on", "off"):
+            assert switch.default == switch.kind and switch.parse(None) is (switch.kind == "on")
+
+
+def test_switches_take_effect_at_their_declared_moment(monkeypatch):
+    """``import``: frozen into a constant; ``construct``: read by the constructor; ``call``: follows the environment at every call."""
+    from cusrl_amd.nn import module
+    from cusrl_amd.utils import switches
+    from cusrl_amd.utils.misc import host_form
+
+    assert switches.SWITCHES["FUSED_INFERENCE"].moment == "import"
+    frozen = module._FUSED_INFERENCE
+    monkeypatch.setenv("CUSRL_FUSED_INFERENCE", "0" if frozen else "1")
+    assert switches.read("FUSED_INFERENCE") is not frozen and module._FUSED_INFERENCE is frozen
+
+    assert switches.SWITCHES["RECORD_THRESHOLD_BYTES"].moment == "construct"
+    monkeypatch.setenv("CUSRL_RECORD_THRESHOLD_BYTES", "4096")
+    buffer = cusrl.Buffer(4, 2, device="cpu")
+    assert buffer.record_threshold_bytes == 4096
+    monkeypatch.setenv("CUSRL_RECORD_THRESHOLD_BYTES", "8192")
+    assert buffer.record_threshold_bytes == 4096 and cusrl.Buffer(4, 2, device="cpu").record_threshold_bytes == 8192
+
+    assert switches.SWITCHES["HOST_FORMS"].moment == "call"
+    monkeypatch.setenv("CUSRL_HOST_FORMS", "1")
+    host_form("a hook")
+    monkeypatch.setenv("CUSRL_HOST_FORMS", "0")
+    with pytest.raises(RuntimeError, match="CPU tensors"):
+        host_form("a hook")
+    monkeypatch.setenv("CUSRL_HOST_FORMS", "1")
+    host_form("a hook")
+
+
+def test_integration_table_and_the_switch_registry_agree():
+    """INTEGRATION.md, "Environment switches", against ``utils/switches.py``: the same names, the declared default in front of the
+    default column, ``TEST ONLY:`` / ``READ BY THE LIBRARY:`` in front of the effect of exactly the switches marked so.
+    (``utils/streams.py`` needs a GPU to do anything; what a CPU process can hold is that it imports and that its switches —
+    like everyone's — are documented.)"""
+    from cusrl_amd.utils import streams, switches
 
     assert callable(streams.side_stream) and callable(streams.runs_beside)
-    integration = (ROOT / "INTEGRATION.md").read_text()
-    for switch in ("CUSRL_SIDE_STREAM_PROBE", "CUSRL_SIDE_STREAM_PRIORITY", "CUSRL_NORMED_MAIN_FIRST", "CUSRL_STEP_MAIN_FIRST",
-                   "CUSRL_PREDRAW_NOISE", "CUSRL_TWO_WINDOW_STEP"):
-        assert switch in integration, switch
+    section = (ROOT / "INTEGRATION.md").read_text().split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    rows = [re.split(r"\s*(?<!\\)\|\s*", line.strip("| \n")) for line in section.splitlines() if line.startswith("| `CUSRL_")]
+    documented = {}
+    for names, default, effect in rows:
+        for name in re.findall(r"CUSRL_[A-Z_]+", names):
+            assert name not in documented, name
+            mark = "test-only" if effect.startswith("TEST ONLY:") else "library" if effect.startswith("READ BY THE LIBRARY:") else ""
+            documented[name] = (default.split(" (")[0].strip("`"), mark)
+    assert documented == {switch.name: (switch.default, switch.mark) for switch in switches.declared()}
+    assert {"CUSRL_SIDE_STREAM_PROBE", "CUSRL_SIDE_STREAM_PRIORITY", "CUSRL_NORMED_MAIN_FIRST", "CUSRL_STEP_MAIN_FIRST",
+            "CUSRL_PREDRAW_NOISE", "CUSRL_TWO_WINDOW_STEP"} <= set(documented)
+    assert re.findall(r"CUSRL_[A-Z_]+", section.split("\n| variable", 1)[0]) == ["CUSRL_RCCL_LIBRARY"]  # (the heading's own mention)
+
+
+def test_the_package_reads_its_switches_through_the_registry_only():
+    """No module of the package other than ``utils/switches.py`` looks a ``CUSRL_*`` variable up in the environment (the host-side
+    counterpart of the ``getenv(`` count over csrc/ in ``test_options_of_the_c_abi_without_a_gpu``), and ``os.environ`` is left to
+    the registry, the torchrun variables of ``utils/config.py`` and the ``PYTHONHASHSEED`` write of ``utils/misc.py``."""
+    package = ROOT / "cusrl_amd"
+    sources = {path.relative_to(package).as_posix(): path.read_text() for path in sorted(package.glob("**/*.py"))}
+    assert len(sources) > 40 and "utils/switches.py" in sources
+    access = re.compile(r"(?:environ|getenv)[^\n]*?[\[(]\s*f?[\"']CUSRL_|\benv\.get\(\s*f?[\"']CUSRL_")
+    stray = {name: access.findall(text) for name, text in sources.items() if name != "utils/switches.py" and access.search(text)}
+    assert not stray, stray
+    assert access.search('os.environ.get("CUSRL_X")') and access.search("os.getenv('CUSRL_X', '1')") and access.search('os.environ["CUSRL_X"]')
+    assert sorted(name for name, text in sources.items() if "environ" in text.replace("environment", "").replace("Environment", "")) == [
+        "utils/config.py", "utils/misc.py", "utils/switches.py"]
+    assert sources["utils/misc.py"].count("os.environ") == 1 and 'os.environ["PYTHONHASHSEED"]' in sources["utils/misc.py"]
+    assert sources["utils/config.py"].count("os.environ") == 1  # (`env = os.environ` of the torchrun variables)
