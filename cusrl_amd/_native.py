@@ -7,18 +7,14 @@ The library is the product: there is no CPU or eager fallback.  If it has not be
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+import re
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 from pathlib import Path
 
 from cusrl_amd.utils import switches
 
 # (another build of the same library: A/B runs of compile-time variants, profiles/r05/loss_variants_ab.txt)
 LIB_PATH = Path(switches.read("HIP_LIBRARY") or Path(__file__).resolve().parent / "libcusrl_hip.so")
-ABI_VERSION = 7
-MAX_FIELDS = 24
-MAX_PACKED = 16
-MAX_MIRROR_FIELDS = 24
-MAX_SYMMETRIZE_CHANNELS = 4096
 
 
 class Field(Structure):
@@ -52,131 +48,62 @@ class NativeError(RuntimeError):
 
 _lib = None
 
-_P = c_void_p
-_SIGNATURES = {
-    "cusrl_abi_version": (c_int, []),
-    "cusrl_error_string": (c_char_p, [c_int]),
-    "cusrl_set_option": (c_int, [c_char_p, c_int64]),
-    "cusrl_get_option": (c_int, [c_char_p, POINTER(c_int64)]),
-    "cusrl_buffer_push": (c_int, [POINTER(Field), c_int, c_int64, c_int64, _P]),
-    "cusrl_buffer_push_through": (c_int, [POINTER(Field), c_int, c_int64, c_int64, _P, c_int64, POINTER(ctypes.c_int32), _P]),
-    "cusrl_next_value": (c_int, [_P, _P, _P, _P, c_float, c_int, _P, _P, c_int64, c_int64, c_int64, _P]),
-    "cusrl_flag_blocks": (c_int64, [c_int64]),
-    "cusrl_compact_flags": (c_int, [_P, c_int64, _P, c_int, _P, _P, _P]),
-    "cusrl_scatter_rows": (c_int, [_P, _P, _P, c_int64, c_int64, _P, _P]),
-    "cusrl_splice_rows": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P]),
-    "cusrl_gae": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_double, c_double, c_double, _P]),
-    "cusrl_gae_num_partials": (c_int64, [c_int64, c_int64, c_int64]),
-    "cusrl_col_stats": (c_int, [_P, c_int64, c_int64, _P, _P]),
-    "cusrl_col_stats_num_partials": (c_int64, [c_int64, c_int64]),
-    "cusrl_stats_finalize": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P]),
-    "cusrl_normalize": (c_int, [_P, _P, _P, c_float, c_int64, c_int64, _P]),
-    "cusrl_normalize_from_partials": (c_int, [_P, _P, c_int64, c_int64, c_float, c_int64, c_int64, _P, _P, _P]),
-    "cusrl_merge_mean_var": (c_int, [_P, c_int64, c_int64, _P, _P, _P]),
-    "cusrl_normalize_from_gathered": (c_int, [_P, _P, c_int64, c_float, c_int64, c_int64, _P, _P, _P]),
-    "cusrl_gather_rows": (c_int, [POINTER(Field), c_int, _P, c_int64, c_int64, c_int64, c_int, _P]),
-    "cusrl_pack_rows": (c_int, [POINTER(PackedField), c_int, _P, c_int64, c_int64, _P]),
-    "cusrl_pack_rows_owned": (c_int, [POINTER(PackedField), c_int, _P, c_int64, c_int64, c_int, c_int, _P]),
-    "cusrl_gather_rows_packed": (c_int, [POINTER(Field), c_int, _P, c_int64, POINTER(PackedField), c_int, _P, c_int64, c_int64,
-                                         c_int64, c_int, _P]),
-    "cusrl_window_indices": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P]),
-    "cusrl_ppo_loss_fwd_bwd": (
-        c_int,
-        [_P] * 8 + [c_int64] * 3 + [c_double] * 5 + [_P] * 8 + [_P, c_int64, _P, c_int, _P],
-    ),
-    "cusrl_ppo_loss_categorical_fwd_bwd": (c_int, [_P] * 7 + [c_int64] * 3 + [c_double] * 5 + [_P] * 7 + [_P, c_int, _P]),
-    "cusrl_ppo_loss_num_partials": (c_int64, [c_int64]),
-    "cusrl_ppo_loss_std_partial_rows": (c_int64, [c_int64]),
-    "cusrl_ppo_loss_blocks": (c_int64, [c_int64, c_int64]),
-    "cusrl_value_loss_fwd_bwd": (c_int, [_P, _P, _P, c_int64, c_int64, c_double, c_double, _P, _P, _P, c_int, _P]),
-    "cusrl_value_loss_blocks": (c_int64, [c_int64, c_int64]),
-    "cusrl_normal_sample_logp": (c_int, [_P] * 5 + [c_int64, c_int64, c_int64, _P, _P, _P, _P]),
-    "cusrl_categorical_sample_logp": (c_int, [_P] * 4 + [c_int64, c_int64, _P]),
-    "cusrl_gru_gates_fwd": (c_int, [_P] * 6 + [c_int64, c_int64, c_int64, _P]),
-    "cusrl_gru_gates_bwd": (c_int, [_P] * 7 + [c_int64, c_int64, c_int64, _P]),
-    "cusrl_gru_gates_bwd_bias": (c_int, [_P] * 7 + [c_int64, c_int64, c_int64, _P, _P]),
-    "cusrl_gru_bias_partial_rows": (c_int64, [c_int64]),
-    "cusrl_gru_bias_supported": (c_int, [c_int64, _P, _P, _P, _P, _P, _P, _P]),
-    "cusrl_lstm_gates_fwd": (c_int, [_P] * 8 + [c_int64, c_int64, c_int64, _P]),
-    "cusrl_lstm_gates_bwd": (c_int, [_P] * 7 + [c_int64, c_int64, c_int64, _P]),
-    "cusrl_rnn_cell_fwd": (c_int, [_P] * 6 + [c_int64, c_int64, c_int64, c_int, _P]),
-    "cusrl_rnn_cell_bwd": (c_int, [_P] * 5 + [c_int64, c_int64, c_int64, c_int, _P]),
-    "cusrl_episode_stats": (c_int, [_P] * 8 + [c_int64, c_int64, c_int64, c_int, _P]),
-    "cusrl_step_epilogue": (c_int, [_P] * 12 + [c_int64, c_int64, c_int64, c_int, _P]),
-    "cusrl_step_epilogue_max_envs": (c_int64, []),
-    "cusrl_step_epilogue_push": (c_int, [_P] * 12 + [c_int64, c_int64, c_int64, c_int, POINTER(Field), c_int, c_int, c_int64, _P]),
-    "cusrl_policy_stats": (c_int, [_P] * 7 + [c_int64, c_int64, c_int64, _P, _P, _P]),
-    "cusrl_policy_stats_num_partials": (c_int64, [c_int64]),
-    "cusrl_categorical_policy_stats": (c_int, [_P] * 5 + [c_int64, c_int64, c_int64, _P, _P, _P]),
-    "cusrl_policy_terms_fwd": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
-    "cusrl_policy_terms_bwd": (c_int, [_P, _P, c_int64] + [_P] * 6 + [c_int64, c_int64, _P, _P, _P, _P]),
-    "cusrl_policy_terms_std_partial_rows": (c_int64, [c_int64]),
-    "cusrl_categorical_terms_fwd": (c_int, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
-    "cusrl_categorical_terms_bwd": (c_int, [_P] * 7 + [c_int64, c_int64, _P, _P]),
-    "cusrl_relu_bwd_colsum": (c_int, [_P] * 5 + [c_int64, c_int64, _P]),
-    "cusrl_colsum_num_partials": (c_int64, [c_int64, c_int64]),
-    "cusrl_input_layer_bwd": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P]),
-    "cusrl_input_layer_supported": (c_int, [c_int64, c_int64]),
-    "cusrl_input_layer_row_blocks": (c_int64, [c_int64, c_int64]),
-    "cusrl_narrow_linear_bwd": (c_int, [_P] * 6 + [c_int64, c_int64, c_int64, c_int, _P]),
-    "cusrl_narrow_linear_num_partials": (c_int64, [c_int64]),
-    "cusrl_narrow_linear_supported": (c_int, [c_int64, c_int64]),
-    "cusrl_narrow_linear_fwd": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P]),
-    "cusrl_mlp2_forward": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P]),
-    "cusrl_mlp2_forward_supported": (c_int, [c_int64, c_int64, c_int64, c_int64]),
-    "cusrl_clip_grad_norm": (c_int, [_P, c_int64, c_float, _P, _P, _P]),
-    "cusrl_clip_grad_norm_num_partials": (c_int64, [c_int64]),
-    "cusrl_assemble_gradients": (c_int, [POINTER(GradPiece), c_int64, _P, _P, _P]),
-    "cusrl_assemble_gradients_blocks": (c_int64, [POINTER(GradPiece), c_int64]),
-    "cusrl_grad_sumsq": (c_int, [_P, c_int64, _P, _P]),
-    "cusrl_adam_step": (c_int, [_P] * 6 + [c_int64, c_double, c_double, c_double, c_double, c_int, c_int, _P, c_int64, c_float, _P, _P, _P, _P]),
-    "cusrl_adam_step_window": (c_int, [_P] * 6 + [c_int64, c_double, c_double, c_double, c_double, c_int, c_int, _P, c_int64, _P, c_int64,
-                                       c_float, _P, _P, _P, _P, _P]),
-    "cusrl_adam_step_normed": (c_int, [_P] * 6 + [c_int64, c_double, c_double, c_double, c_double, c_int, c_int, _P, c_int64, _P,
-                                       c_float, _P, _P, _P, _P, _P]),
-    "cusrl_adam_step_normed_workspace_bytes": (c_int64, []),
-    "cusrl_masked_col_stats": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
-    "cusrl_masked_stats_num_partials": (c_int64, [c_int64, c_int64]),
-    "cusrl_rms_merge": (c_int, [_P] * 7 + [c_float, c_double, c_int64, _P]),
-    "cusrl_rms_normalize": (c_int, [_P, _P, _P, c_float, _P, c_int64, c_int64, _P]),
-    "cusrl_rnd_reward": (c_int, [_P, _P, _P, _P, c_float, c_int64, c_int64, _P]),
-    "cusrl_amp_style_reward": (c_int, [_P, _P, _P, c_float, c_int64, _P]),
-    "cusrl_amp_style_reward_mean": (c_int, [_P, _P, _P, c_float, c_int64, _P, _P]),
-    "cusrl_amp_prepare": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_float, c_double,
-                                  c_float, _P, _P, _P, _P]),
-    "cusrl_amp_prepare_max_elements": (c_int64, []),
-    "cusrl_amp_prepare_workspace": (c_int64, [c_int64, c_int64]),
-    "cusrl_synthetic_env_step": (c_int, [ctypes.c_uint64, _P, c_int64, c_int64, c_int64, c_float, c_float, _P, _P, _P, _P, _P, _P]),
-    "cusrl_accumulate_scalars": (c_int, [POINTER(c_void_p), c_int, _P, _P]),
-    "cusrl_reward_shaping": (c_int, [_P, c_float, c_float, c_float, c_float, c_int, c_int, c_int64, _P]),
-    "cusrl_mse_loss_fwd_bwd": (c_int, [_P, _P, c_int64, _P, _P, _P, _P]),
-    "cusrl_mse_loss_num_partials": (c_int64, [c_int64]),
-    "cusrl_sumsq_fwd_bwd": (c_int, [_P, c_int64, c_double, c_double, _P, _P, _P, _P]),
-    "cusrl_bce_pair_fwd_bwd": (c_int, [_P, c_int64, c_float, _P, _P, _P]),
-    "cusrl_graph_census": (c_int, [_P, POINTER(c_int64), c_int, ctypes.c_char_p, c_int64, POINTER(c_int64)]),
-    "cusrl_graph_replace_memsets": (c_int, [_P, POINTER(c_int64)]),
-    "cusrl_comm_available": (c_int, []),
-    "cusrl_comm_last_error": (c_char_p, []),
-    "cusrl_comm_unique_id": (c_int, [_P]),
-    "cusrl_comm_create": (c_int, [_P, c_int, c_int, POINTER(c_void_p)]),
-    "cusrl_comm_destroy": (c_int, [_P]),
-    "cusrl_comm_abort": (c_int, [_P]),
-    "cusrl_comm_world_size": (c_int, [_P]),
-    "cusrl_allreduce_mean": (c_int, [_P, c_int64, _P, _P]),
-    "cusrl_allgather": (c_int, [_P, _P, c_int64, _P, _P]),
-    "cusrl_broadcast": (c_int, [_P, c_int64, c_int, _P, _P]),
-    "cusrl_sequence_count": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
-    "cusrl_sequence_blocks": (c_int64, [c_int64]),
-    "cusrl_sequence_layout": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
-    "cusrl_gather_memory": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P]),
-    "cusrl_mirror_rows": (c_int, [POINTER(MirrorField), c_int, c_int64, _P]),
-    "cusrl_mirror_rows_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, _P]),
-    "cusrl_mirror_mse_fwd_bwd": (c_int, [_P, _P, _P, _P, c_int, _P, c_int64, c_int64, c_double, _P, _P, _P, _P, _P, _P, _P]),
-    "cusrl_mirror_mse_num_partials": (c_int64, [c_int64]),
-    "cusrl_symmetrize_mean_var": (c_int, [_P, _P, _P, c_int64, _P]),
-}
+# The binding is READ from the header, not copied from it: `ret name(args);` for every prototype and the `#define`d integer
+# constants of include/cusrl_hip.h, in the header's own restricted C.  The mapping is fixed; a declaration outside it is an error.
+HEADER_PATH = Path(__file__).resolve().parent.parent / "include" / "cusrl_hip.h"
+_SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_float, "double": c_double}
+_STRUCTS = {"cusrl_field_t": Field, "cusrl_packed_field_t": PackedField, "cusrl_grad_piece_t": GradPiece,
+            "cusrl_mirror_field_t": MirrorField}
+_POINTEES = {"void", "char", "float", "double", "int", "uint8_t", "int32_t", "uint32_t", "int64_t", "uint64_t"}
 
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+def _ctype(declaration: str, where: str, opaque: frozenset = frozenset()):
+    """ctypes type of one C declaration (``const float *x``, ``int64_t n``, a bare return type); ``opaque``: names the header
+    declares as incomplete struct types.  Pointers other than strings and the registered structs are addresses."""
+    words = [word for word in re.findall(r"\w+|\*", declaration) if word != "const"]
+    base, stars = (words[0] if words else ""), words.count("*")
+    if stars == 0 and base in _SCALARS and len(words) <= 2:
+        return _SCALARS[base]
+    if len(words) <= stars + 2 and words[1 : stars + 1] == ["*"] * stars:
+        if stars == 1 and base == "char":
+            return c_char_p
+        if stars == 1 and base in _STRUCTS:
+            return POINTER(_STRUCTS[base])
+        if stars >= 1 and (base in _POINTEES or base in opaque):
+            return c_void_p
+    raise NativeError(f"{HEADER_PATH.name}: no ctypes mapping for '{declaration.strip()}' in '{where.strip()}'")
+
+
+def parse_header(text: str) -> tuple[dict[str, int], dict[str, tuple]]:
+    """``({constant: value}, {symbol: (restype, argtypes)})`` of a header in the style of include/cusrl_hip.h."""
+    constants = {name: int(value) for name, value in re.findall(r"^#define\s+CUSRL_(\w+)\s+\(?(-?\d+)\)?", text, re.M)}
+    text = re.sub(r"^\s*#.*$", "", re.sub(r"/\*.*?\*/", " ", text, flags=re.S), flags=re.M)
+    statements = [" ".join(part.split()) for part in re.split(r"[;{}]", text)]
+    opaque = frozenset(m.group(1) for m in map(re.compile(r"typedef struct \w+ (\w+)").fullmatch, statements) if m)
+    prototypes = {}
+    for statement in statements:
+        if "(" not in statement:
+            continue
+        match = re.fullmatch(r"([\w\s*]+?)(\w+) ?\(([^()]*)\)", statement)
+        if match is None:
+            raise NativeError(f"{HEADER_PATH.name}: not a prototype of the form `ret name(args)`: '{statement}'")
+        ret, name, args = match.groups()
+        arguments = [] if args.strip() == "void" else args.split(",")
+        prototypes[name] = (_ctype(ret, statement, opaque), [_ctype(arg, statement, opaque) for arg in arguments])
+    return constants, prototypes
+
+
+# (read here and not on the first lib(): ABI_VERSION, the MAX_* and EXPORTED_SYMBOLS are attributes of this module)
+try:
+    _CONSTANTS, _PROTOTYPES = parse_header(HEADER_PATH.read_text())
+except OSError as error:
+    raise NativeError(f"{HEADER_PATH} cannot be read ({error}): the ctypes binding is derived from it") from error
+ABI_VERSION = _CONSTANTS["ABI_VERSION"]
+MAX_FIELDS = _CONSTANTS["MAX_FIELDS"]
+MAX_PACKED = _CONSTANTS["MAX_PACKED"]
+MAX_MIRROR_FIELDS = _CONSTANTS["MAX_MIRROR_FIELDS"]
+MAX_SYMMETRIZE_CHANNELS = _CONSTANTS["MAX_SYMMETRIZE_CHANNELS"]
+EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
 
 def lib() -> ctypes.CDLL:
@@ -190,7 +117,7 @@ def lib() -> ctypes.CDLL:
                 "cusrl_amd has no CPU / eager fallback for the rollout + PPO-update hot path."
             )
         handle = ctypes.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in _SIGNATURES.items():
+        for name, (restype, argtypes) in _PROTOTYPES.items():
             fn = getattr(handle, name)  # AttributeError here = stale library
             fn.restype = restype
             fn.argtypes = argtypes
@@ -235,7 +162,12 @@ def _options_from_environment() -> None:
 launch_counts: dict[str, int] = {}
 
 
-def check(code: int, what: str) -> None:
+def check(code: int, what, arguments: tuple | None = None) -> None:
+    """Two ways in.  ``check(status, "cusrl_x")``: count the call under that name and raise on a non-zero status.  As a ctypes
+    ``errcheck``, ``check(status, function, arguments)``: ctypes passes the library function and the (always non-None) argument
+    tuple; the call is counted under the function's symbol name.  The call then returns None."""
+    if arguments is not None:
+        what = what.__name__
     launch_counts[what] = launch_counts.get(what, 0) + 1
     if code != 0:
         text = lib().cusrl_error_string(code).decode()

@@ -1,0 +1,207 @@
+"""Running statistics and the auxiliary hooks' kernels: RND / AMP rewards, reward shaping, small losses, scalar
+accumulation (``csrc/normalization.hip``, ``aux_hooks.hip``)."""
+
+from __future__ import annotations
+
+import ctypes
+from collections.abc import Sequence
+
+import torch
+
+from cusrl_amd import _native
+from cusrl_amd.ops._common import _checked, _f32, _flag, _modified_in_place, _ptr, _stream, require_device
+
+
+def masked_col_stats(x: torch.Tensor, mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``mean_var_count`` (population variance) of the rows of ``x [rows, C]`` whose ``mask`` byte is set
+    (cusrl/nn/utils/normalization.py:15-50 after the ``observation[indices]`` select of observation.py:206-208);
+    the count stays on the device (double[1]) — no host synchronisation."""
+    x = _f32(x, "input")
+    C = x.shape[-1]
+    rows = x.numel() // C
+    if mask is not None:
+        mask = _flag(mask, "mask")
+        if mask.numel() != rows:
+            raise ValueError("masked_col_stats: mask must have one entry per row")
+    lib = _native.lib()
+    dev = x.device
+    partials = torch.empty((max(int(lib.cusrl_masked_stats_num_partials(rows, C)), 1), C + 1, 2), dtype=torch.float64, device=dev)
+    mean, var = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+    count = torch.empty(1, dtype=torch.float64, device=dev)
+    _checked.cusrl_masked_col_stats(x.data_ptr(), _ptr(mask), rows, C, partials.data_ptr(), mean.data_ptr(), var.data_ptr(),
+            count.data_ptr(), _stream())
+    return mean, var, count
+
+
+def rms_merge_(mean, var, std, count, batch_mean, batch_var, batch_count, eps: float, max_count: float | None) -> None:
+    """In-place Chan merge of batch statistics into running statistics (normalization.py:80-93, rms.py:163-167)."""
+    _checked.cusrl_rms_merge(
+        _f32(mean, "mean").data_ptr(), _f32(var, "var").data_ptr(), _f32(std, "std").data_ptr(), count.data_ptr(),
+        _f32(batch_mean, "batch_mean").data_ptr(), _f32(batch_var, "batch_var").data_ptr(), batch_count.data_ptr(),
+        float(eps), -1.0 if max_count is None else float(max_count), mean.numel(), _stream(),
+    )
+
+
+def rms_normalize(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, clamp: float | None) -> torch.Tensor:
+    """``((x - mean) / std).clamp(-clamp, clamp)`` as one launch (rms.py:198-203)."""
+    x = _f32(x, "input")
+    C = x.shape[-1]
+    out = torch.empty_like(x)
+    _checked.cusrl_rms_normalize(x.data_ptr(), _f32(mean, "mean").data_ptr(), _f32(std, "std").data_ptr(),
+            -1.0 if clamp is None else float(clamp),
+            out.data_ptr(), x.numel() // C, C, _stream())
+    return out
+
+
+def rnd_reward_(reward: torch.Tensor, target: torch.Tensor, prediction: torch.Tensor, scale: float) -> torch.Tensor:
+    """``reward += scale * (target - prediction).square().mean(-1, keepdim=True)`` in place, one launch; returns the
+    added bonus (cusrl/hook/auxiliary/rnd.py:71-74)."""
+    target, prediction = _f32(target, "target"), _f32(prediction, "prediction")
+    require_device(reward, "reward")
+    if reward.dtype != torch.float32 or not reward.is_contiguous() or reward.shape[-1] != 1:
+        raise TypeError("rnd_reward_: reward must be a contiguous float32 [..., 1] tensor")
+    K = target.shape[-1]
+    rows = target.numel() // K
+    if reward.numel() != rows or prediction.shape != target.shape:
+        raise ValueError("rnd_reward_: shape mismatch")
+    bonus = torch.empty_like(reward)
+    _checked.cusrl_rnd_reward(target.data_ptr(), prediction.data_ptr(), reward.data_ptr(), bonus.data_ptr(), float(scale), rows, K, _stream())
+    _modified_in_place(reward)
+    return bonus
+
+
+def amp_style_reward_(reward: torch.Tensor, logit: torch.Tensor, scale: float) -> torch.Tensor:
+    """``reward += scale * -log(clamp(1 - sigmoid(logit), 1e-4))`` in place, one launch; returns the bonus
+    (cusrl/hook/auxiliary/amp.py:134-136)."""
+    logit = _f32(logit, "logit")
+    require_device(reward, "reward")
+    if reward.dtype != torch.float32 or not reward.is_contiguous() or reward.numel() != logit.numel():
+        raise TypeError("amp_style_reward_: reward must be a contiguous float32 tensor matching the logits")
+    bonus = torch.empty_like(reward)
+    _checked.cusrl_amp_style_reward(logit.data_ptr(), reward.data_ptr(), bonus.data_ptr(), float(scale), logit.numel(), _stream())
+    _modified_in_place(reward)
+    return bonus
+
+
+def amp_style_reward_mean_(reward: torch.Tensor, logit: torch.Tensor, scale: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """:func:`amp_style_reward_` + the mean of the bonus (what ``agent.record(amp_reward=...)`` reduces) from ONE launch;
+    returns ``(bonus, mean[1])``.  Falls back to the two-launch form beyond the single-workgroup size."""
+    logit = _f32(logit, "logit")
+    require_device(reward, "reward")
+    if reward.dtype != torch.float32 or not reward.is_contiguous() or reward.numel() != logit.numel():
+        raise TypeError("amp_style_reward_mean_: reward must be a contiguous float32 tensor matching the logits")
+    if logit.numel() > (1 << 20):
+        bonus = amp_style_reward_(reward, logit, scale)
+        return bonus, bonus.mean().reshape(1)
+    bonus = torch.empty_like(reward)
+    mean = torch.empty(1, dtype=torch.float32, device=reward.device)
+    _checked.cusrl_amp_style_reward_mean(logit.data_ptr(), reward.data_ptr(), bonus.data_ptr(), float(scale), logit.numel(),
+            mean.data_ptr(), _stream())
+    _modified_in_place(reward)
+    return bonus, mean
+
+
+def amp_prepare_supported(rows: int, channels: int) -> bool:
+    return 0 < channels <= 128 and 0 < rows * channels <= int(_native.lib().cusrl_amp_prepare_max_elements())
+
+
+def amp_prepare(rms, *, state=None, next_state=None, columns=None, width: int | None = None, agent_raw=None, dataset=None,
+                indices=None, expert_raw=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """AMP's ``post_step`` up to the discriminator (amp.py:112-128) as ONE C-ABI call (two launches): assemble ``state[cols] || next_state[cols]``
+    (or take ``agent_raw``), fetch ``dataset[indices]`` (or take ``expert_raw``), update ``rms`` (a RunningMeanStd) with the
+    agent rows, then the expert rows, normalise both.  ``columns``: int32 device vector of the selected state columns, or
+    None with ``width`` = K for the first K columns.  Returns ``(agent_transition, expert_transition)``, ``[N, C]`` each."""
+    if agent_raw is not None:
+        agent_raw = _f32(agent_raw, "agent_raw")
+        N, C = agent_raw.shape
+        K = C // 2
+    else:
+        state, next_state = _f32(state, "state"), _f32(next_state, "next_state")
+        if state.dim() != 2 or state.shape != next_state.shape:
+            raise ValueError("amp_prepare: state / next_state must be [N, S] tensors of one shape")
+        N = state.shape[0]
+        K = int(columns.numel()) if columns is not None else int(width)
+        C = 2 * K
+        if columns is not None and (columns.dtype != torch.int32 or not columns.is_cuda):
+            raise TypeError("amp_prepare: 'columns' must be an int32 device vector")
+    if expert_raw is not None:
+        expert_raw = _f32(expert_raw, "expert_raw")
+        if tuple(expert_raw.shape) != (N, C):
+            raise ValueError("amp_prepare: expert rows do not match the agent rows")
+    else:
+        dataset = _f32(dataset, "dataset")
+        if indices.dtype != torch.int64 or indices.numel() != N or dataset.shape[-1] != C:
+            raise ValueError("amp_prepare: need one int64 dataset index per agent row and rows of the transition's width")
+        indices = indices.contiguous()
+    dev = rms.mean.device
+    agent_out = torch.empty((N, C), dtype=torch.float32, device=dev)
+    expert_out = torch.empty((N, C), dtype=torch.float32, device=dev)
+    workspace = torch.empty(max(int(_native.lib().cusrl_amp_prepare_workspace(N, C)), 1), dtype=torch.float64, device=dev)
+    _checked.cusrl_amp_prepare(
+        _ptr(state), _ptr(next_state), 0 if state is None else state.shape[1], _ptr(columns), K, _ptr(agent_raw), _ptr(dataset),
+        _ptr(indices), _ptr(expert_raw), N, C, rms.mean.data_ptr(), rms.var.data_ptr(), rms.std.data_ptr(), rms._count.data_ptr(),
+        float(rms.epsilon), -1.0 if rms.max_count is None else float(rms.max_count), -1.0 if rms.clamp is None else float(rms.clamp),
+        agent_out.data_ptr(), expert_out.data_ptr(), workspace.data_ptr(), _stream(),
+    )
+    return agent_out, expert_out
+
+
+def reward_shaping_(reward: torch.Tensor, scale: float, shift: float, lower: float | None, upper: float | None) -> torch.Tensor:
+    """``reward.mul_(scale).add_(shift).clamp_(lower, upper)`` (reward.py:43-47) in place, one launch."""
+    require_device(reward, "reward")
+    if reward.dtype != torch.float32 or not reward.is_contiguous():
+        raise TypeError("reward_shaping_: expected a contiguous float32 tensor")
+    _checked.cusrl_reward_shaping(reward.data_ptr(), float(scale), float(shift), 0.0 if lower is None else float(lower),
+            0.0 if upper is None else float(upper), int(lower is not None), int(upper is not None), reward.numel(), _stream())
+    _modified_in_place(reward)
+    return reward
+
+
+def mse_loss_fwd_bwd(prediction: torch.Tensor, target: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(mean((prediction - target)^2), d loss / d prediction)`` from one pass (+ a one-block finalize)."""
+    prediction, target = _f32(prediction, "prediction"), _f32(target, "target")
+    if prediction.shape != target.shape or prediction.numel() == 0:
+        raise ValueError("mse_loss_fwd_bwd: shapes differ or are empty")
+    lib = _native.lib()
+    n = prediction.numel()
+    loss = torch.empty((), dtype=torch.float32, device=prediction.device)
+    grad = torch.empty_like(prediction)
+    partials = torch.empty(max(int(lib.cusrl_mse_loss_num_partials(n)), 1), dtype=torch.float64, device=prediction.device)
+    _checked.cusrl_mse_loss_fwd_bwd(prediction.data_ptr(), target.data_ptr(), n, loss.data_ptr(), grad.data_ptr(), partials.data_ptr(), _stream())
+    return loss, grad
+
+
+def sumsq_fwd_bwd(x: torch.Tensor, loss_scale: float, grad_scale: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(loss_scale * sum(x^2), grad_scale * x)`` from one pass (AMP's gradient penalty and what it sends back)."""
+    x = _f32(x, "x")
+    lib = _native.lib()
+    n = x.numel()
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    grad = torch.empty_like(x)
+    partials = torch.empty(max(int(lib.cusrl_mse_loss_num_partials(n)), 1), dtype=torch.float64, device=x.device)
+    _checked.cusrl_sumsq_fwd_bwd(x.data_ptr(), n, float(loss_scale), float(grad_scale), loss.data_ptr(), grad.data_ptr(),
+            partials.data_ptr(), _stream())
+    return loss, grad
+
+
+def bce_pair_fwd_bwd(logit: torch.Tensor, weight: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """Discrimination loss of a joint ``[2N, 1]`` logit batch (agent rows first: target 0, expert rows: target 1) times
+    ``weight``, and its gradient wrt the logits — one launch."""
+    logit = _f32(logit, "logit")
+    if logit.numel() % 2:
+        raise ValueError("bce_pair_fwd_bwd: the joint batch holds as many expert as agent rows")
+    loss = torch.empty((), dtype=torch.float32, device=logit.device)
+    grad = torch.empty_like(logit)
+    _checked.cusrl_bce_pair_fwd_bwd(logit.data_ptr(), logit.numel() // 2, float(weight), loss.data_ptr(), grad.data_ptr(), _stream())
+    return loss, grad
+
+
+def accumulate_scalars_(accumulator: torch.Tensor, values: Sequence[torch.Tensor]) -> None:
+    """``accumulator[i] += values[i]`` for 0-d fp32 device tensors — ONE launch per 32 values (pointer table by value)."""
+    if accumulator.dtype != torch.float32 or not accumulator.is_contiguous() or accumulator.numel() < len(values):
+        raise ValueError("accumulate_scalars_: need a contiguous float32 accumulator with one slot per value")
+    staged = [v if v.dtype == torch.float32 else v.float() for v in values]
+    for start in range(0, len(staged), 32):
+        chunk = staged[start:start + 32]
+        table = (ctypes.c_void_p * len(chunk))(*[require_device(v, "value").data_ptr() for v in chunk])
+        _checked.cusrl_accumulate_scalars(table, len(chunk), accumulator.data_ptr() + 4 * start, _stream())

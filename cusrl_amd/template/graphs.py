@@ -992,7 +992,7 @@ class GraphedRolloutStep:
             if state is not None:
                 act.static_state.copy_(state)
         noise = self._noise_plan(steps)
-        key = (trainer.stats._parity, steps, None if noise is None else noise.data_ptr())
+        key = (trainer.stats._parity, steps, noise.data_ptr() if noise is not None else None)
         entry = self.rollouts.get(key)
         if noise is not None:
             self._draw_noise(noise)

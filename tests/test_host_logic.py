@@ -28,6 +28,48 @@ def test_library_exports_every_symbol_declared_in_the_header():
     assert declared == set(_native.EXPORTED_SYMBOLS)
     assert lib.cusrl_abi_version() == _native.ABI_VERSION
     assert b"invalid" in lib.cusrl_error_string(-1) and lib.cusrl_error_string(0) == b"success"
+    # the binding's constants are the header's #defines
+    defines = {name: int(value) for name, value in re.findall(r"^#define\s+CUSRL_(\w+)\s+\(?(-?\d+)\)?", header, re.M)}
+    assert _native.ABI_VERSION == defines["ABI_VERSION"] == 7
+    for name in ("MAX_FIELDS", "MAX_PACKED", "MAX_MIRROR_FIELDS", "MAX_SYMMETRIZE_CHANNELS"):
+        assert getattr(_native, name) == defines[name]
+    # every hand-written Structure has the fields of its `typedef struct`: names, order and sizes
+    import ctypes
+
+    sizes = {"int32_t": 4, "int64_t": 8}
+    structs = dict((name, body) for body, name in re.findall(r"typedef struct \{(.*?)\}\s*(\w+);", header, re.S))
+    assert set(structs) == set(_native._STRUCTS) and len(structs) == 4
+    for c_name, body in structs.items():
+        fields = re.findall(r"([\w ]+?)\s*(\*?)\s*(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+        declared_fields = [(name, 8 if star else sizes[kind.replace("const", "").strip()]) for kind, star, name in fields]
+        structure = _native._STRUCTS[c_name]
+        assert [(name, ctypes.sizeof(kind)) for name, kind in structure._fields_] == declared_fields, c_name
+        assert ctypes.sizeof(structure) == sum(size for _, size in declared_fields), c_name  # (no padding in either layout)
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    """The binding's argtypes are read from the header with a fixed mapping: a type outside it is an error naming the
+    prototype, never a guess."""
+    import ctypes
+
+    constants, prototypes = _native.parse_header(
+        "#define CUSRL_MAX_THINGS 3 /* c */\ntypedef struct cusrl_comm cusrl_comm_t;\n"
+        "int64_t cusrl_ok(const cusrl_field_t *f, const char *key, uint64_t seed, float x, double y, int32_t k, const uint8_t *m,\n"
+        "                 cusrl_comm_t **out, void *stream); /* comment */\nconst char *cusrl_text(void);")
+    assert constants == {"MAX_THINGS": 3}
+    assert prototypes["cusrl_ok"] == (ctypes.c_int64, [ctypes.POINTER(_native.Field), ctypes.c_char_p, ctypes.c_uint64, ctypes.c_float,
+                                                       ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
+    assert prototypes["cusrl_text"] == (ctypes.c_char_p, [])
+    for bad in ("int cusrl_bad(size_t n);", "int cusrl_bad(unsigned n);", "long cusrl_bad(void);", "int cusrl_bad(struct thing *p);",
+                "int cusrl_bad(cusrl_unknown_t *p);", "int cusrl_bad(int (*callback)(int));", "int cusrl_bad(int a b);"):
+        with pytest.raises(_native.NativeError, match="cusrl_bad"):
+            _native.parse_header(bad)
+
+
+def test_integration_document_names_every_exported_symbol():
+    """INTEGRATION.md is what an integrator binds from: every symbol the library exports appears there by its full name."""
+    named = set(re.findall(r"\bcusrl_[a-z0-9_]+", (ROOT / "INTEGRATION.md").read_text()))
+    assert not [symbol for symbol in _native.EXPORTED_SYMBOLS if symbol not in named]
 
 
 def test_size_helpers_and_argument_validation_without_a_gpu():
