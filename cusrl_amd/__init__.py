@@ -6,6 +6,7 @@ gather, PPO objective forward+backward) runs as hand-written HIP kernels for gfx
 """
 
 from cusrl_amd import hook, nn, preset, sampler, template, testing, utils
+from cusrl_amd.hook import NextStatePrediction, PolicyDistillationLoss, ReturnPrediction, StateEstimation, StatePrediction
 from cusrl_amd.nn import (
     Actor, AdaptiveNormalDist, Distribution, Gru, LinearFp32, Lstm, Mlp, Module, ModuleFactory, NormalDist,
     OneHotCategoricalDist, Rnn, RunningMeanStd, Value,
@@ -49,13 +50,18 @@ __all__ = [
     "Mlp",
     "Module",
     "ModuleFactory",
+    "NextStatePrediction",
     "NormalDist",
     "OneHotCategoricalDist",
     "OptimizerFactory",
+    "PolicyDistillationLoss",
     "RandomSampler",
+    "ReturnPrediction",
     "Rnn",
     "RunningMeanStd",
     "Sampler",
+    "StateEstimation",
+    "StatePrediction",
     "TemporalMiniBatchSampler",
     "TemporalRandomSampler",
     "Trainer",

@@ -7,6 +7,8 @@
 //   cusrl_amp_style_reward_mean the style reward (amp.py:130-134) + the mean the metric records, one launch
 //   cusrl_mse_loss_fwd_bwd      nn.MSELoss(predictor(x), target(x)) of RandomNetworkDistillation.objective (rnd.py:78-81):
 //                               loss and d loss / d prediction in one pass
+//   cusrl_column_mse_fwd_bwd    weight * nn.MSELoss(prediction, leaf[..., columns]) of the privileged-information hooks
+//                               (estimation.py, representation.py, distillation.py): the same, the target read in place
 // All of these are a few hundred KB per launch at 4096 envs: latency-bound chains of tiny kernels in the reference's form,
 // so what counts is the NUMBER of dependent launches inside the captured step (>= 1.5 us each + their own latency).
 #include "common.hpp"
@@ -267,6 +269,54 @@ __global__ __launch_bounds__(kBlock) void mse_finalize_kernel(const double *__re
     if (threadIdx.x == 0) *loss_out = float(total * loss_scale);
 }
 
+// --------------------------------------------------------------------------------------------- column MSE, forward + backward
+// weight * mean((prediction - target[..., columns])^2) and its gradient wrt the prediction, the target read IN PLACE: row r of
+// the target starts at target + r * pitch (a buffer leaf, or a row view of one), column k of the prediction is compared with
+// target column columns[k] (NULL: k).  What StateEstimation / the *Prediction hooks / PolicyDistillationLoss compute per
+// minibatch step (estimation.py:126-131, representation.py:40-45,108-113,167-173, distillation.py:44-47) as index + sub +
+// pow + mean + mul forward and fill + mse_backward + mul backward.
+// Threads walk the dense [rows * K] index space of the prediction: its loads and the gradient's stores are coalesced; the
+// target's reads are K-wide runs pitch apart (K is small and the rows of one wave share cache lines).  n < 2^31: 32-bit
+// index arithmetic (one unsigned division per element).
+__global__ __launch_bounds__(kBlock) void column_mse_fwd_bwd_kernel(const float *__restrict__ prediction,
+                                                                    const float *__restrict__ target, int64_t pitch,
+                                                                    const int32_t *__restrict__ columns, uint32_t n, uint32_t K,
+                                                                    int vector, float grad_scale,
+                                                                    float *__restrict__ d_prediction,
+                                                                    double *__restrict__ partials, double loss_scale,
+                                                                    float *__restrict__ loss_out) {
+    __shared__ double scratch[kWavesPerBlock];
+    const uint32_t tid = blockIdx.x * kBlock + threadIdx.x, stride = gridDim.x * kBlock;
+    double acc = 0.0;
+    if (vector) {  // columns == NULL, K % 4 == 0, pitch % 4 == 0, every pointer 16-byte aligned (checked by the host)
+        const uint32_t quads = n / 4, row_quads = K / 4;
+        for (uint32_t q = tid; q < quads; q += stride) {
+            const uint32_t r = q / row_quads, kq = q - r * row_quads;
+            const float4 p = reinterpret_cast<const float4 *>(prediction)[q];
+            const float4 t = *reinterpret_cast<const float4 *>(target + int64_t(r) * pitch + 4 * kq);
+            const float d[4] = {p.x - t.x, p.y - t.y, p.z - t.z, p.w - t.w};
+            acc += double(d[0] * d[0]) + double(d[1] * d[1]) + double(d[2] * d[2]) + double(d[3] * d[3]);
+            reinterpret_cast<float4 *>(d_prediction)[q] =
+                make_float4(grad_scale * d[0], grad_scale * d[1], grad_scale * d[2], grad_scale * d[3]);
+        }
+    } else {
+        for (uint32_t i = tid; i < n; i += stride) {
+            const uint32_t r = i / K, k = i - r * K;
+            const int64_t column = columns ? int64_t(columns[k]) : int64_t(k);
+            const float d = prediction[i] - target[int64_t(r) * pitch + column];
+            acc += double(d * d);
+            d_prediction[i] = grad_scale * d;  // d (w mean((p - t)^2)) / d p = 2 w (p - t) / n
+        }
+    }
+    const double total = block_sum(acc, scratch);
+    if (threadIdx.x == 0) {
+        if (gridDim.x == 1)
+            *loss_out = float(total * loss_scale);
+        else
+            partials[blockIdx.x] = total;
+    }
+}
+
 // --------------------------------------------------------------------------------------------- BCE-with-logits of a joint batch
 // logit [2 * rows]: the first `rows` are agent transitions (target 0), the rest expert transitions (target 1).
 //   loss = mean_i ((1 - t_i) x_i - log_sigmoid(x_i))     torch.nn.functional.binary_cross_entropy_with_logits
@@ -482,6 +532,32 @@ extern "C" int cusrl_sumsq_fwd_bwd(const float *x, int64_t n, double loss_scale,
     if (n <= 0) return CUSRL_E_INVALID;
     if (!x || !loss_out || !grad_out || !partials) return CUSRL_E_INVALID;
     return launch_sumsq(x, nullptr, n, loss_scale, float(grad_scale), loss_out, grad_out, partials, as_stream(stream));
+}
+
+extern "C" int64_t cusrl_column_mse_num_partials(int64_t rows, int64_t K) {
+    if (rows <= 0 || K <= 0 || rows > INT32_MAX / K) return 0;
+    return cusrl_mse_loss_num_partials(rows * K);  // the launch rule of the contiguous loss: one block up to 16 K elements
+}
+
+extern "C" int cusrl_column_mse_fwd_bwd(const float *prediction, const float *target, int64_t target_pitch,
+                                        const int32_t *columns, int64_t rows, int64_t K, float weight, float *loss_out,
+                                        float *d_prediction, double *partials, void *stream) {
+    if (rows <= 0 || K <= 0) return CUSRL_E_INVALID;
+    if (!prediction || !target || !loss_out || !d_prediction || !partials) return CUSRL_E_INVALID;
+    if (target_pitch <= 0 || (!columns && target_pitch < K)) return CUSRL_E_INVALID;
+    if (rows > INT32_MAX / K) return CUSRL_E_UNSUPPORTED;  // 32-bit element index
+    const int64_t n = rows * K, blocks = cusrl_column_mse_num_partials(rows, K);
+    const int vector = !columns && K % 4 == 0 && target_pitch % 4 == 0 && aligned(prediction, 16) && aligned(target, 16) &&
+                       aligned(d_prediction, 16);
+    const double loss_scale = double(weight) / double(n);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(column_mse_fwd_bwd_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, prediction, target, target_pitch,
+                       columns, uint32_t(n), uint32_t(K), vector, float(2.0 * loss_scale), d_prediction, partials, loss_scale,
+                       loss_out);
+    if (int rc = launch_status()) return rc;
+    if (blocks == 1) return 0;  // the one block finalised itself
+    hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), loss_scale, loss_out);
+    return launch_status();
 }
 
 extern "C" int cusrl_bce_pair_fwd_bwd(const float *logit, int64_t rows, float weight, float *loss_out, float *d_logit,

@@ -1,4 +1,7 @@
 from cusrl_amd.hook.auxiliary.amp import AdversarialMotionPrior
+from cusrl_amd.hook.auxiliary.distillation import PolicyDistillationLoss
+from cusrl_amd.hook.auxiliary.estimation import StateEstimation
+from cusrl_amd.hook.auxiliary.representation import NextStatePrediction, ReturnPrediction, StatePrediction
 from cusrl_amd.hook.auxiliary.rnd import RandomNetworkDistillation
 from cusrl_amd.hook.auxiliary.symmetry import (
     MirrorDef,
@@ -11,7 +14,12 @@ __all__ = [
     "AdversarialMotionPrior",
     "MirrorDef",
     "MirrorSymmetryLoss",
+    "NextStatePrediction",
+    "PolicyDistillationLoss",
     "RandomNetworkDistillation",
+    "ReturnPrediction",
+    "StateEstimation",
+    "StatePrediction",
     "SymmetricDataAugmentation",
     "TransitionMirroring",
 ]

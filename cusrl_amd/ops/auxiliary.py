@@ -171,6 +171,84 @@ def mse_loss_fwd_bwd(prediction: torch.Tensor, target: torch.Tensor) -> tuple[to
     return loss, grad
 
 
+def resolve_columns(indices, width: int) -> torch.Tensor | None:
+    """The columns ``target[..., indices]`` selects of a ``width``-wide target, as a host int32 vector:
+    ``torch.arange(width)[indices]`` (a slice, an int list or an index tensor; negative entries resolved), or None for
+    ``slice(None)`` — every column in place.  A slice is resolved as Python resolves it, so a negative step (which torch's
+    own indexing refuses) selects the columns in descending order."""
+    if isinstance(indices, slice):
+        if indices == slice(None):
+            return None
+        resolved = torch.tensor(list(range(int(width))[indices]), dtype=torch.int32)
+    else:
+        if isinstance(indices, torch.Tensor):
+            indices = indices.cpu()
+        resolved = torch.arange(int(width))[indices].reshape(-1).to(torch.int32)
+    if resolved.numel() == 0:
+        raise ValueError(f"{indices!r} selects no column of a {width}-wide target")
+    return resolved
+
+
+def column_table(indices, width: int, device) -> torch.Tensor | None:
+    """:func:`resolve_columns` as the int32 device table of ``cusrl_column_mse_fwd_bwd`` (None stays None).  Uploaded here —
+    call it outside any capture."""
+    resolved = resolve_columns(indices, width)
+    if resolved is None:
+        return None
+    table = resolved.to(device)
+    table._cusrl_column_range = (int(resolved.min()), int(resolved.max()))  # what the binding validates against the pitch
+    return table
+
+
+def _target_rows(target: torch.Tensor) -> tuple[torch.Tensor, int]:
+    """``(tensor, row pitch in elements)`` of a ``[..., W]`` target whose rows lie one pitch apart (a contiguous tensor, or a
+    row / column view of one with last-dim stride 1); anything else is staged contiguously."""
+    W = target.shape[-1]
+    lead = [(size, stride) for size, stride in zip(target.shape[:-1], target.stride()[:-1]) if size != 1]
+    pitch = lead[-1][1] if lead else W
+    uniform = target.stride(-1) == 1 and pitch >= W and all(
+        outer[1] == inner[0] * inner[1] for outer, inner in zip(lead[:-1], lead[1:]))
+    if not uniform:
+        target, pitch = target.contiguous(), W
+    return target, pitch
+
+
+def column_mse_fwd_bwd(prediction: torch.Tensor, target: torch.Tensor, columns: torch.Tensor | None,
+                       weight: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(weight * mean((prediction - target[..., columns])^2), d loss / d prediction)`` from one pass (+ a one-block finalize
+    beyond one block).  ``prediction [..., K]``; ``target [..., W]`` with the same leading shape is read IN PLACE (a buffer
+    leaf, or a view whose last-dim stride is 1); ``columns``: a :func:`column_table` (or any int32 device vector of K entries),
+    None for the first K columns."""
+    prediction = _f32(prediction, "prediction")
+    require_device(target, "target")
+    if target.dtype != torch.float32:
+        raise TypeError(f"'target' must be float32, got {target.dtype}")
+    K, W = prediction.shape[-1], target.shape[-1]
+    if prediction.numel() == 0 or prediction.shape[:-1] != target.shape[:-1]:
+        raise ValueError(f"column_mse_fwd_bwd: prediction {tuple(prediction.shape)} and target {tuple(target.shape)} differ in "
+                         "their leading shape or are empty")
+    if columns is None:
+        if K > W:
+            raise ValueError(f"column_mse_fwd_bwd: a {K}-wide prediction against a {W}-wide target")
+    else:
+        if columns.dtype != torch.int32 or not columns.is_cuda or columns.dim() != 1 or not columns.is_contiguous():
+            raise TypeError("column_mse_fwd_bwd: 'columns' must be a contiguous int32 device vector")
+        if columns.numel() != K:
+            raise ValueError(f"column_mse_fwd_bwd: {columns.numel()} columns for a {K}-wide prediction")
+        low, high = getattr(columns, "_cusrl_column_range", None) or (int(columns.min()), int(columns.max()))
+        if low < 0 or high >= W:
+            raise IndexError(f"column_mse_fwd_bwd: columns {low}..{high} out of range for a {W}-wide target")
+    target, pitch = _target_rows(target)
+    rows = prediction.numel() // K
+    partials_needed = int(_native.lib().cusrl_column_mse_num_partials(rows, K))
+    loss = torch.empty((), dtype=torch.float32, device=prediction.device)
+    grad = torch.empty_like(prediction)
+    partials = torch.empty(max(partials_needed, 1), dtype=torch.float64, device=prediction.device)
+    _checked.cusrl_column_mse_fwd_bwd(prediction.data_ptr(), target.data_ptr(), pitch, _ptr(columns), rows, K, float(weight),
+            loss.data_ptr(), grad.data_ptr(), partials.data_ptr(), _stream())
+    return loss, grad
+
+
 def sumsq_fwd_bwd(x: torch.Tensor, loss_scale: float, grad_scale: float) -> tuple[torch.Tensor, torch.Tensor]:
     """``(loss_scale * sum(x^2), grad_scale * x)`` from one pass (AMP's gradient penalty and what it sends back)."""
     x = _f32(x, "x")

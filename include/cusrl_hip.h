@@ -700,6 +700,23 @@ int cusrl_sumsq_fwd_bwd(const float *x, int64_t n, double loss_scale, double gra
  * (amp.py:143-147), d_logit = weight * (sigmoid(logit) - target) / (2 rows).  One launch instead of ~10 torch ops. */
 int cusrl_bce_pair_fwd_bwd(const float *logit, int64_t rows, float weight, float *loss_out, float *d_logit, void *stream);
 
+/* ---- weight * nn.MSELoss(prediction, target[..., columns]) forward AND backward with the target read in place ----
+ * StateEstimation.objective (estimation.py:126-131), ReturnPrediction / StatePrediction / NextStatePrediction.objective
+ * (representation.py:40-45, 108-113, 167-173), PolicyDistillationLoss.objective (distillation.py:44-47).
+ * prediction [rows, K] contiguous; row r of the target starts at target + r * target_pitch (elements): a buffer leaf or a
+ * row view of one, never copied.  columns: K int32 device entries, column k of the prediction is compared with target column
+ * columns[k] (any order, repeats allowed); NULL: columns 0..K-1.  The CALLER guarantees 0 <= columns[k] < target_pitch (the
+ * table lives on the device: the kernel does not check it); with columns == NULL, target_pitch >= K is checked here.
+ *   loss_out[0]        = weight / (rows K) * sum_{r,k} (prediction[r,k] - target[r, columns[k]])^2
+ *   d_prediction[r,k]  = 2 weight / (rows K) * (prediction[r,k] - target[r, columns[k]])
+ * fp64 block partials in fixed order (bit-reproducible, no atomics, no memset); partials: double[max(1,
+ * cusrl_column_mse_num_partials(rows, K))].  One block finalises itself; beyond that a one-block finalize follows.
+ * rows * K > INT32_MAX: CUSRL_E_UNSUPPORTED (cusrl_column_mse_num_partials then returns 0). */
+int cusrl_column_mse_fwd_bwd(const float *prediction, const float *target, int64_t target_pitch, const int32_t *columns,
+                             int64_t rows, int64_t K, float weight, float *loss_out, float *d_prediction, double *partials,
+                             void *stream);
+int64_t cusrl_column_mse_num_partials(int64_t rows, int64_t K);
+
 
 /* ---- Mirror symmetry — cusrl/hook/auxiliary/symmetry.py:30-62,155-356, cusrl/hook/mdp/observation.py:213-217 (ABI 7) ----
  * A mirror table (int32, device) describes MirrorDef(destination_indices, flipped_indices), out[j] = in[dest[j]] * (-1 if j is

@@ -42,13 +42,17 @@ def timeit(fn, iters):
         torch.cuda.synchronize()
         return start.elapsed_time(end) * 1e3 / iters  # us
     per_graph = 10
-    stream, graph = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+    stream, graph = torch.cuda.Stream(), torch.cuda.CUDAGraph(keep_graph=True)
     with torch.cuda.stream(stream):
         fn()
     torch.cuda.synchronize()
     with torch.cuda.graph(graph, stream=stream):
         for _ in range(per_graph):
             fn()
+    # (a torch-op reference row brings ATen's split reductions and their memset nodes, which this stack does not replay
+    # reliably: turned into fill kernels as every captured region of the package is, template/graphs.py _Capture.capture)
+    ops.graph_replace_memsets(graph)
+    graph.instantiate()
     graph.replay()
     torch.cuda.synchronize()
     replays = max(iters // per_graph, 1)
@@ -174,6 +178,24 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
                      loss_bytes - B * 8 * act - B * 12)
     rows.measure(f"value term fwd+bwd (B={B})",
                  lambda: ops.value_loss_fwd_bwd(a["ret"], a["curr_value"], None, value_clip=None, w_val=0.5), B * 12)
+
+    # ---- column MSE of the privileged-information hooks: a [B, 16] prediction against 16 of a 48-wide leaf's columns, read in
+    # place; beside it torch's expression for the same objective (index -> mse_loss -> * w -> backward), same run
+    K, W = 16, obs
+    prediction, leaf = f(B, K).requires_grad_(), f(B, W)
+    column_list = torch.randperm(W)[:K].tolist()
+    columns, gather_index = ops.column_table(column_list, W, DEV), torch.tensor(column_list, device=DEV)
+    column_bytes = B * K * 12  # prediction read, its target column read, gradient written
+    rows.measure(f"column mse fwd+bwd [B,{K}] of {W} columns (B={B})",
+                 lambda: ops.column_mse_fwd_bwd(prediction.detach(), leaf, columns, 0.01), column_bytes)
+    rows.measure(f"column mse fwd+bwd [B,{K}], no table (B={B})",
+                 lambda: ops.column_mse_fwd_bwd(prediction.detach(), leaf, None, 0.01), column_bytes)
+
+    def torch_column_mse():
+        loss = torch.nn.functional.mse_loss(prediction, leaf[..., gather_index]) * 0.01
+        return torch.autograd.grad(loss, prediction)
+
+    rows.measure(f"column mse as torch ops: index, mse_loss, mul, backward (B={B})", torch_column_mse, column_bytes)
 
     # ---- MLP backward epilogues and the optimizer-side kernels of one minibatch step
     g256, y256 = f(B, 256), torch.relu(f(B, 256))
