@@ -8,8 +8,8 @@ gather, PPO objective forward+backward) runs as hand-written HIP kernels for gfx
 from cusrl_amd import hook, nn, preset, sampler, template, testing, utils
 from cusrl_amd.hook import NextStatePrediction, PolicyDistillationLoss, ReturnPrediction, StateEstimation, StatePrediction
 from cusrl_amd.nn import (
-    Actor, AdaptiveNormalDist, Distribution, Gru, LinearFp32, Lstm, Mlp, Module, ModuleFactory, NormalDist,
-    OneHotCategoricalDist, Rnn, RunningMeanStd, Value,
+    Actor, AdaptiveNormalDist, Distribution, GradientPenaltyLoss, Gru, L2RegularizationLoss, LinearFp32, Lstm, Mlp, Module,
+    ModuleFactory, NormalDist, NormalNllLoss, OneHotCategoricalDist, Rnn, RunningMeanStd, Value,
 )
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
@@ -42,8 +42,10 @@ __all__ = [
     "Distribution",
     "Environment",
     "EnvironmentSpec",
+    "GradientPenaltyLoss",
     "Gru",
     "Hook",
+    "L2RegularizationLoss",
     "LinearFp32",
     "Lstm",
     "MiniBatchSampler",
@@ -52,6 +54,7 @@ __all__ = [
     "ModuleFactory",
     "NextStatePrediction",
     "NormalDist",
+    "NormalNllLoss",
     "OneHotCategoricalDist",
     "OptimizerFactory",
     "PolicyDistillationLoss",

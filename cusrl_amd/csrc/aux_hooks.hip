@@ -9,6 +9,7 @@
 //                               loss and d loss / d prediction in one pass
 //   cusrl_column_mse_fwd_bwd    weight * nn.MSELoss(prediction, leaf[..., columns]) of the privileged-information hooks
 //                               (estimation.py, representation.py, distillation.py): the same, the target read in place
+//   cusrl_normal_nll_fwd_bwd    nn.NormalNllLoss (cusrl/nn/layer/loss.py:62-141): the loss and both gradients in one pass
 // All of these are a few hundred KB per launch at 4096 envs: latency-bound chains of tiny kernels in the reference's form,
 // so what counts is the NUMBER of dependent launches inside the captured step (>= 1.5 us each + their own latency).
 #include "common.hpp"
@@ -317,6 +318,81 @@ __global__ __launch_bounds__(kBlock) void column_mse_fwd_bwd_kernel(const float 
     }
 }
 
+// --------------------------------------------------------------------------------------------- Normal NLL, forward + backward
+// NormalNllLoss (cusrl/nn/layer/loss.py:110-141): nll = 0.5 (log_var + (target - mean)^2 / var) [+ log sqrt(2 pi)], reduced by
+// mean or sum, and its gradients wrt the mean and the variance parameter `dist` from the same pass.  `mode` says what `dist`
+// holds (0 log_var, 1 log_std, 2 var, 3 std); it is clamped from below at `bound`, given in its own domain.  Per element in
+// fp32 in the reference's order; with w = (incoming gradient of the reduction) / 2 and e = 1 - (target - mean)^2 / var:
+//   d nll / d mean = -2 w (target - mean) / var        d nll / d dist = w e * d log_var / d dist  (1, 2, 1 / var, 2 / std)
+// and zero where dist < bound (torch's clamp_min backward).  The clamp is a comparison, not fmaxf: a NaN stays a NaN.
+// mean, dist and target are rows of K elements one pitch apart (the halves of a chunked [rows, 2K] input: pitch 2K); both
+// gradients share one pitch, so the chunked form's gradient is written as ONE [rows, 2K] tensor.  Threads walk the dense
+// [rows * K] index space like column_mse_fwd_bwd_kernel (n < 2^31, one unsigned division per element).
+constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
+
+__device__ __forceinline__ float normal_nll_element(float m, float d, float t, int mode, int full, float bound, float half_g,
+                                                    float &d_mean, float &d_dist) {
+    const bool below = d < bound;
+    const float c = below ? bound : d;
+    float log_var, var, slope;  // slope = d log_var / d dist
+    switch (mode) {
+        case 0: log_var = c, var = expf(log_var), slope = 1.0f; break;
+        case 1: log_var = c * 2.0f, var = expf(log_var), slope = 2.0f; break;
+        case 2: var = c, log_var = logf(var), slope = 1.0f / var; break;
+        default: var = c * c, log_var = logf(c) * 2.0f, slope = 2.0f / c; break;
+    }
+    const float diff = t - m, ratio = diff * diff / var;
+    float nll = 0.5f * (log_var + ratio);
+    if (full) nll = nll + kLogSqrt2Pi;
+    d_mean = -(2.0f * half_g * diff / var);
+    d_dist = below ? 0.0f : half_g * (1.0f - ratio) * slope;
+    return nll;
+}
+
+__global__ __launch_bounds__(kBlock) void normal_nll_fwd_bwd_kernel(
+    const float *__restrict__ mean, int64_t mean_pitch, const float *__restrict__ dist, int64_t dist_pitch,
+    const float *__restrict__ target, int64_t target_pitch, uint32_t n, uint32_t K, int vector, int mode, int full, float bound,
+    float half_g, float *__restrict__ d_mean, float *__restrict__ d_dist, int64_t grad_pitch, double *__restrict__ partials,
+    double loss_scale, float *__restrict__ loss_out) {
+    __shared__ double scratch[kWavesPerBlock];
+    const uint32_t tid = blockIdx.x * kBlock + threadIdx.x, stride = gridDim.x * kBlock;
+    double acc = 0.0;
+    if (vector) {  // K % 4 == 0, every pitch % 4 == 0, every pointer 16-byte aligned (checked by the host)
+        const uint32_t quads = n / 4, row_quads = K / 4;
+        for (uint32_t q = tid; q < quads; q += stride) {
+            const uint32_t r = q / row_quads;
+            const int64_t k = 4 * int64_t(q - r * row_quads);
+            const float4 m = *reinterpret_cast<const float4 *>(mean + int64_t(r) * mean_pitch + k);
+            const float4 d = *reinterpret_cast<const float4 *>(dist + int64_t(r) * dist_pitch + k);
+            const float4 t = *reinterpret_cast<const float4 *>(target + int64_t(r) * target_pitch + k);
+            float4 gm, gd;
+            acc += double(normal_nll_element(m.x, d.x, t.x, mode, full, bound, half_g, gm.x, gd.x));
+            acc += double(normal_nll_element(m.y, d.y, t.y, mode, full, bound, half_g, gm.y, gd.y));
+            acc += double(normal_nll_element(m.z, d.z, t.z, mode, full, bound, half_g, gm.z, gd.z));
+            acc += double(normal_nll_element(m.w, d.w, t.w, mode, full, bound, half_g, gm.w, gd.w));
+            *reinterpret_cast<float4 *>(d_mean + int64_t(r) * grad_pitch + k) = gm;
+            *reinterpret_cast<float4 *>(d_dist + int64_t(r) * grad_pitch + k) = gd;
+        }
+    } else {
+        for (uint32_t i = tid; i < n; i += stride) {
+            const uint32_t r = i / K;
+            const int64_t k = int64_t(i - r * K);
+            float gm, gd;
+            acc += double(normal_nll_element(mean[int64_t(r) * mean_pitch + k], dist[int64_t(r) * dist_pitch + k],
+                                             target[int64_t(r) * target_pitch + k], mode, full, bound, half_g, gm, gd));
+            d_mean[int64_t(r) * grad_pitch + k] = gm;
+            d_dist[int64_t(r) * grad_pitch + k] = gd;
+        }
+    }
+    const double total = block_sum(acc, scratch);
+    if (threadIdx.x == 0) {
+        if (gridDim.x == 1)
+            *loss_out = float(total * loss_scale);
+        else
+            partials[blockIdx.x] = total;
+    }
+}
+
 // --------------------------------------------------------------------------------------------- BCE-with-logits of a joint batch
 // logit [2 * rows]: the first `rows` are agent transitions (target 0), the rest expert transitions (target 1).
 //   loss = mean_i ((1 - t_i) x_i - log_sigmoid(x_i))     torch.nn.functional.binary_cross_entropy_with_logits
@@ -554,6 +630,34 @@ extern "C" int cusrl_column_mse_fwd_bwd(const float *prediction, const float *ta
     hipLaunchKernelGGL(column_mse_fwd_bwd_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, prediction, target, target_pitch,
                        columns, uint32_t(n), uint32_t(K), vector, float(2.0 * loss_scale), d_prediction, partials, loss_scale,
                        loss_out);
+    if (int rc = launch_status()) return rc;
+    if (blocks == 1) return 0;  // the one block finalised itself
+    hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), loss_scale, loss_out);
+    return launch_status();
+}
+
+extern "C" int64_t cusrl_normal_nll_num_partials(int64_t rows, int64_t K) { return cusrl_column_mse_num_partials(rows, K); }
+
+extern "C" int cusrl_normal_nll_fwd_bwd(const float *mean, int64_t mean_pitch, const float *dist, int64_t dist_pitch,
+                                        const float *target, int64_t target_pitch, int64_t rows, int64_t K, int mode, int full,
+                                        float bound, int reduction, float *loss_out, float *d_mean, float *d_dist,
+                                        int64_t grad_pitch, double *partials, void *stream) {
+    if (rows <= 0 || K <= 0) return CUSRL_E_INVALID;
+    if (!mean || !dist || !target || !loss_out || !d_mean || !d_dist || !partials) return CUSRL_E_INVALID;
+    if (mean_pitch < K || dist_pitch < K || target_pitch < K || grad_pitch < K) return CUSRL_E_INVALID;
+    if (mode < 0 || mode > 3 || full < 0 || full > 1 || reduction < 1 || reduction > 2) return CUSRL_E_INVALID;
+    if (rows > INT32_MAX / K) return CUSRL_E_UNSUPPORTED;  // 32-bit element index
+    const int64_t n = rows * K, blocks = cusrl_normal_nll_num_partials(rows, K);
+    const int vector = K % 4 == 0 && mean_pitch % 4 == 0 && dist_pitch % 4 == 0 && target_pitch % 4 == 0 &&
+                       grad_pitch % 4 == 0 && aligned(mean, 16) && aligned(dist, 16) && aligned(target, 16) &&
+                       aligned(d_mean, 16) && aligned(d_dist, 16);
+    // reduction 1: mean, 2: sum.  What arrives at every element from the reduction's backward, halved (nll = 0.5 (...))
+    const double loss_scale = reduction == 1 ? 1.0 / double(n) : 1.0;
+    const float half_g = 0.5f * float(loss_scale);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(normal_nll_fwd_bwd_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, mean, mean_pitch, dist, dist_pitch,
+                       target, target_pitch, uint32_t(n), uint32_t(K), vector, mode, full, bound, half_g, d_mean, d_dist,
+                       grad_pitch, partials, loss_scale, loss_out);
     if (int rc = launch_status()) return rc;
     if (blocks == 1) return 0;  // the one block finalised itself
     hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), loss_scale, loss_out);

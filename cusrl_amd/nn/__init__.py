@@ -1,5 +1,6 @@
 from cusrl_amd.nn.actor import Actor, Value
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
+from cusrl_amd.nn.loss import L2RegularizationLoss, NormalNllLoss
 from cusrl_amd.nn.module import LinearFp32, Mlp, Module, ModuleFactory
 from cusrl_amd.nn.rms import RunningMeanStd
 from cusrl_amd.nn.rnn import Gru, Lstm, Rnn
@@ -8,11 +9,14 @@ __all__ = [
     "Actor",
     "AdaptiveNormalDist",
     "Distribution",
+    "GradientPenaltyLoss",
+    "L2RegularizationLoss",
     "LinearFp32",
     "Mlp",
     "Module",
     "ModuleFactory",
     "NormalDist",
+    "NormalNllLoss",
     "OneHotCategoricalDist",
     "Gru",
     "Lstm",
@@ -20,3 +24,13 @@ __all__ = [
     "RunningMeanStd",
     "Value",
 ]
+
+
+def __getattr__(name):
+    # GradientPenaltyLoss stays beside its user in hook/auxiliary/amp.py, which itself imports this package: looked up on first
+    # use instead of at import
+    if name == "GradientPenaltyLoss":
+        from cusrl_amd.hook.auxiliary.amp import GradientPenaltyLoss
+
+        return GradientPenaltyLoss
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -4,6 +4,7 @@ accumulation (``csrc/normalization.hip``, ``aux_hooks.hip``)."""
 from __future__ import annotations
 
 import ctypes
+import math
 from collections.abc import Sequence
 
 import torch
@@ -247,6 +248,59 @@ def column_mse_fwd_bwd(prediction: torch.Tensor, target: torch.Tensor, columns: 
     _checked.cusrl_column_mse_fwd_bwd(prediction.data_ptr(), target.data_ptr(), pitch, _ptr(columns), rows, K, float(weight),
             loss.data_ptr(), grad.data_ptr(), partials.data_ptr(), _stream())
     return loss, grad
+
+
+NORMAL_NLL_MODES = {"log_var": 0, "log_std": 1, "var": 2, "std": 3}
+_REDUCTIONS = {"mean": 1, "sum": 2}
+
+
+def normal_nll_bound(mode: str, eps: float) -> float:
+    """The clamp bound of ``NormalNllLoss`` in the variance parameter's own domain (cusrl/nn/layer/loss.py:116-129), in double."""
+    eps = float(eps)
+    return {"log_var": math.log(eps), "log_std": math.log(eps) / 2, "var": eps, "std": math.sqrt(eps)}[mode]
+
+
+def normal_nll_fwd_bwd(mean: torch.Tensor, dist: torch.Tensor | None, target: torch.Tensor, mode: str, full: bool, eps: float,
+                       reduction: str) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(NormalNllLoss(mode, full, eps, reduction)(input, target), d loss / d mean, d loss / d dist)`` from one pass (+ a
+    one-block finalize beyond one block).  ``mean`` / ``dist [..., K]``: the tuple input; ``dist`` None: ``mean`` is the chunked
+    ``[..., 2K]`` input, read in place as its two halves, and the two gradients are the halves of ONE ``[..., 2K]`` tensor
+    (``d_mean._base``) — no ``cat``, no zero-fill.  ``target [..., K]`` with the same leading shape is read in place where its rows
+    lie one pitch apart (a column view of a wider leaf), staged contiguously otherwise."""
+    if mode not in NORMAL_NLL_MODES or reduction not in _REDUCTIONS:
+        raise ValueError(f"normal_nll_fwd_bwd: mode {mode!r} / reduction {reduction!r} (the kernel reduces by 'mean' or 'sum')")
+    mean = _f32(mean, "mean" if dist is not None else "input")
+    require_device(target, "target")
+    if target.dtype != torch.float32:
+        raise TypeError(f"'target' must be float32, got {target.dtype}")
+    if dist is None:
+        if mean.dim() < 1 or mean.shape[-1] % 2:
+            raise ValueError(f"normal_nll_fwd_bwd: a chunked input {tuple(mean.shape)} needs an even last dimension")
+        K = mean.shape[-1] // 2
+        shape, pitch = (*mean.shape[:-1], K), 2 * K
+        grad = torch.empty_like(mean)
+        d_mean, d_dist = grad[..., :K], grad[..., K:]
+        dist_ptr = mean.data_ptr() + 4 * K
+    else:
+        dist = _f32(dist, "dist")
+        if mean.dim() < 1 or dist.shape != mean.shape:
+            raise ValueError(f"normal_nll_fwd_bwd: mean {tuple(mean.shape)} and dist {tuple(dist.shape)} differ in shape")
+        K = mean.shape[-1]
+        shape, pitch = tuple(mean.shape), K
+        d_mean, d_dist = torch.empty_like(mean), torch.empty_like(dist)
+        dist_ptr = dist.data_ptr()
+    if mean.numel() == 0 or tuple(target.shape) != tuple(shape):
+        raise ValueError(f"normal_nll_fwd_bwd: input halves {tuple(shape)} and target {tuple(target.shape)} differ in shape or "
+                         "are empty")
+    target, target_pitch = _target_rows(target)
+    rows = d_mean.numel() // K
+    partials_needed = int(_native.lib().cusrl_normal_nll_num_partials(rows, K))
+    loss = torch.empty((), dtype=torch.float32, device=mean.device)
+    partials = torch.empty(max(partials_needed, 1), dtype=torch.float64, device=mean.device)
+    _checked.cusrl_normal_nll_fwd_bwd(mean.data_ptr(), pitch, dist_ptr, pitch, target.data_ptr(), target_pitch, rows, K,
+            NORMAL_NLL_MODES[mode], int(bool(full)), normal_nll_bound(mode, eps), _REDUCTIONS[reduction], loss.data_ptr(),
+            d_mean.data_ptr(), d_dist.data_ptr(), pitch, partials.data_ptr(), _stream())
+    return loss, d_mean, d_dist
 
 
 def sumsq_fwd_bwd(x: torch.Tensor, loss_scale: float, grad_scale: float) -> tuple[torch.Tensor, torch.Tensor]:

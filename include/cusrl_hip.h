@@ -717,6 +717,23 @@ int cusrl_column_mse_fwd_bwd(const float *prediction, const float *target, int64
                              void *stream);
 int64_t cusrl_column_mse_num_partials(int64_t rows, int64_t K);
 
+/* ---- NormalNllLoss forward AND backward — cusrl/nn/layer/loss.py:62-141 ----
+ * nll[r,k] = 0.5 (log_var + (target[r,k] - mean[r,k])^2 / var) (+ log sqrt(2 pi) when full = 1), where dist[r,k], clamped from
+ * below at `bound`, is log_var (mode 0), log_std (1), var (2) or std (3); `bound` is given in that domain (log eps, log eps / 2,
+ * eps, sqrt eps).  loss_out[0] = mean (reduction 1) or sum (reduction 2) of nll over rows * K elements; d_mean and d_dist are
+ * its gradients, d_dist zero where dist < bound (torch's clamp_min backward).  A NaN in dist stays a NaN.
+ * Row r of mean / dist / target starts at the pointer + r * its pitch (elements), K elements wide; row r of BOTH gradients at
+ * d_mean / d_dist + r * grad_pitch.  A chunked [rows, 2K] input is mean = input, dist = input + K, both pitches 2K, and one
+ * [rows, 2K] gradient, d_mean = grad, d_dist = grad + K, grad_pitch = 2K; a target that is a column view of a wider leaf is
+ * read in place.  Every pitch >= K.  float4 accesses when K and every pitch are multiples of 4 and every pointer is 16-byte
+ * aligned, scalar ones otherwise.  Per element in fp32, fp64 block partials in fixed order (bit-reproducible, no atomics, no
+ * memset); partials: double[max(1, cusrl_normal_nll_num_partials(rows, K))], the launch rule of cusrl_column_mse_fwd_bwd.
+ * rows * K > INT32_MAX: CUSRL_E_UNSUPPORTED (cusrl_normal_nll_num_partials then returns 0). */
+int cusrl_normal_nll_fwd_bwd(const float *mean, int64_t mean_pitch, const float *dist, int64_t dist_pitch, const float *target,
+                             int64_t target_pitch, int64_t rows, int64_t K, int mode, int full, float bound, int reduction,
+                             float *loss_out, float *d_mean, float *d_dist, int64_t grad_pitch, double *partials, void *stream);
+int64_t cusrl_normal_nll_num_partials(int64_t rows, int64_t K);
+
 
 /* ---- Mirror symmetry — cusrl/hook/auxiliary/symmetry.py:30-62,155-356, cusrl/hook/mdp/observation.py:213-217 (ABI 7) ----
  * A mirror table (int32, device) describes MirrorDef(destination_indices, flipped_indices), out[j] = in[dest[j]] * (-1 if j is

@@ -196,6 +196,11 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
         return torch.autograd.grad(loss, prediction)
 
     rows.measure(f"column mse as torch ops: index, mse_loss, mul, backward (B={B})", torch_column_mse, column_bytes)
+    # NormalNllLoss of a chunked [B, 2K] estimator output against K columns of the same leaf, read in place
+    estimate, nll_target = f(B, 2 * K), leaf[..., :K]
+    rows.measure(f"normal nll fwd+bwd [B,2x{K}] chunked, log_var (B={B})",
+                 lambda: ops.normal_nll_fwd_bwd(estimate, None, nll_target, "log_var", False, 1e-6, "mean"),
+                 B * K * 20)  # mean, parameter and target read, both gradients written
 
     # ---- MLP backward epilogues and the optimizer-side kernels of one minibatch step
     g256, y256 = f(B, 256), torch.relu(f(B, 256))
