@@ -24,14 +24,17 @@ def gru_gates_backward(gi: torch.Tensor, gh: torch.Tensor, b_hh: torch.Tensor | 
                        bias_partials: torch.Tensor | None = None) -> None:
     """Backward of :func:`gru_gates_forward`, in place: ``gi`` / ``gh`` become their gradients, ``dh`` (the gradient that
     arrived from step t + 1) becomes the direct-path gradient of ``h_prev`` (``cusrl_gru_gates_bwd``).  With
-    ``bias_partials`` (``[gru_bias_partial_rows(B), 4H]``) every block of 16 rows also leaves the column sums of the gate
-    gradients it wrote — {d_r, d_z, d_n, d_q} — for the bias gradients (``cusrl_gru_gates_bwd_bias``)."""
+    ``bias_partials`` (``[gru_bias_partial_rows(B), 4H]`` = ``[ceil(B / rows), 4H]``, ``rows`` being the ``gru_bias_rows``
+    option: 4 | 8 | 16 | 32, 16 unless set) every block of ``rows`` rows also leaves the column sums of the gate gradients it
+    wrote — {d_r, d_z, d_n, d_q} — for the bias gradients (``cusrl_gru_gates_bwd_bias``)."""
     B, H = dh.shape
     if gi.shape != (B, 3 * H) or gh.shape != (B, 3 * H) or h_prev.shape != (B, H):
         raise ValueError("gru_gates_backward: shape mismatch")
     if bias_partials is not None:
-        if bias_partials.shape != (gru_bias_partial_rows(B), 4 * H) or not bias_partials.is_contiguous():
-            raise ValueError("gru_gates_backward: 'bias_partials' must be a contiguous [ceil(B / 16), 4H] tensor")
+        expected = (gru_bias_partial_rows(B), 4 * H)
+        if bias_partials.shape != expected or not bias_partials.is_contiguous():
+            raise ValueError(f"gru_gates_backward: 'bias_partials' must be a contiguous [ceil(B / gru_bias_rows), 4H] = "
+                             f"{list(expected)} tensor, got {list(bias_partials.shape)}")
         _checked.cusrl_gru_gates_bwd_bias(gi.data_ptr(), gh.data_ptr(), _ptr(b_hh), h_prev.data_ptr(), _ptr(d_out), dh.data_ptr(),
                 _ptr(lengths), t, B, H, bias_partials.data_ptr(), _stream())
         return

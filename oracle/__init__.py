@@ -593,6 +593,125 @@ def lstm_sequence(x, state, weights, lengths=None):
     return x.astype(np.float32), (np.stack(last_h).astype(np.float32), np.stack(last_c).astype(np.float32))
 
 
+# ---- one time step of the recurrent gate passes (csrc/gru.hip), operands as the launches take them ---------------------
+# The sequence functions above are pinned to the reference's recordings; chained over the steps of a sequence the forward
+# steps below reproduce them bit for bit (tests/test_recurrent_gates.py), and the backward steps are hand-derived from the
+# same cell equations and pinned against float64 autograd there.  Ended sequences (t >= lengths[b]): the state is kept and
+# the output is zero; backward they get zero gate gradients and the state gradient passes through untouched.  Whatever
+# their rows hold (a length-sorted batch never writes them: NaN in the tests) must not reach any result.
+
+
+def _sigmoid(v):
+    return 1.0 / (1.0 + np.exp(-v))
+
+
+def _live_rows(lengths, t, B):
+    return (np.ones(B, bool) if lengths is None else t < np.asarray(lengths))[:, None]
+
+
+def _f64(x, shape=None):
+    return np.zeros(shape) if x is None else np.asarray(x, np.float64)
+
+
+def gru_gates_step(gi, gh, b_hh, h, lengths, t):
+    """``cusrl_gru_gates_fwd`` in float64: ``gi`` = W_ih x + b_ih and ``gh`` = W_hh h, both [B, 3H] in gate order r, z, n.
+    Returns (h_next, out)."""
+    gi, gh, h = _f64(gi), _f64(gh), _f64(h)
+    B, H = h.shape
+    gh = gh + _f64(b_hh, 3 * H)
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = _sigmoid(gi[:, :H] + gh[:, :H])
+        z = _sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        n = np.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+        nxt = (1.0 - z) * n + z * h
+    live = _live_rows(lengths, t, B)
+    return np.where(live, nxt, h), np.where(live, nxt, 0.0)
+
+
+def gru_gates_step_backward(gi, gh, b_hh, h_prev, d_out, dh, lengths, t):
+    """``cusrl_gru_gates_bwd`` / ``_bwd_bias`` in float64.  With G = dh + d_out the gradient of h' = (1 - z) n + z h:
+    dL/dn = G (1 - z), dL/dz = G (h - n), dL/dh = G z directly; through n = tanh(a), a = gi_n + r q, q = gh_n + b_hn:
+    dL/da = dL/dn (1 - n^2), dL/dq = dL/da r, dL/dr = dL/da q; a sigmoid s contributes s (1 - s).  gi collects the
+    pre-activation gradients {r, z, a}, gh collects {r, z, q}.
+    Returns (d_gi, d_gh, dh_out, column_sums [4H] = {sum d_r, sum d_z, sum d_a, sum d_q} over the live rows)."""
+    gi, gh, h, dh = _f64(gi), _f64(gh), _f64(h_prev), _f64(dh)
+    B, H = dh.shape
+    gh = gh + _f64(b_hh, 3 * H)
+    upstream = dh + _f64(d_out, (B, H))
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = _sigmoid(gi[:, :H] + gh[:, :H])
+        z = _sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        q = gh[:, 2 * H:]
+        n = np.tanh(gi[:, 2 * H:] + r * q)
+        d_a = upstream * (1.0 - z) * (1.0 - n * n)
+        d_r = d_a * q * (r * (1.0 - r))
+        d_z = upstream * (h - n) * (z * (1.0 - z))
+        d_q = d_a * r
+        direct = upstream * z
+    live = _live_rows(lengths, t, B)
+    d_r, d_z, d_a, d_q = (np.where(live, d, 0.0) for d in (d_r, d_z, d_a, d_q))
+    sums = np.concatenate([d.sum(0) for d in (d_r, d_z, d_a, d_q)])
+    return (np.concatenate([d_r, d_z, d_a], 1), np.concatenate([d_r, d_z, d_q], 1), np.where(live, direct, dh), sums)
+
+
+def lstm_gates_step(gi, gh, b_hh, h, c, lengths, t):
+    """``cusrl_lstm_gates_fwd`` in float64 ([B, 4H] projections, gate order i, f, g, o).
+    Returns (h_next, c_next, out, pre, c_saved): ``pre`` = gi + gh + b_hh is what the training form stores over ``gi`` (for
+    every row, ended or not) and ``c_saved`` = c_next what it stores for the backward pass."""
+    gi, gh, h, c = _f64(gi), _f64(gh), _f64(h), _f64(c)
+    B, H = h.shape
+    with np.errstate(over="ignore", invalid="ignore"):
+        pre = gi + gh + _f64(b_hh, 4 * H)
+        i, f, g, o = _sigmoid(pre[:, :H]), _sigmoid(pre[:, H:2 * H]), np.tanh(pre[:, 2 * H:3 * H]), _sigmoid(pre[:, 3 * H:])
+        c_new = f * c + i * g
+        h_new = o * np.tanh(c_new)
+    live = _live_rows(lengths, t, B)
+    c_next = np.where(live, c_new, c)
+    return np.where(live, h_new, h), c_next, np.where(live, h_new, 0.0), pre, c_next
+
+
+def lstm_gates_step_backward(pre, c_prev, c_next, d_out, dh, dc, lengths, t):
+    """``cusrl_lstm_gates_bwd`` in float64, from h' = o tanh(c'), c' = f c + i g with G = dh + d_out:
+    dL/dc' = dc + G o (1 - tanh^2 c'), dL/do = G tanh c', dL/di = dL/dc' g, dL/df = dL/dc' c, dL/dg = dL/dc' i, dL/dc = dL/dc' f;
+    sigmoids contribute s (1 - s), the tanh 1 - g^2.  A live row hands its whole state gradient to the gates (dh_out = 0);
+    an ended row passes dh and dc through.  Returns (d_pre [B, 4H], dh_out, dc_out)."""
+    pre, c_prev, c_next, dh, dc = _f64(pre), _f64(c_prev), _f64(c_next), _f64(dh), _f64(dc)
+    B, H = dh.shape
+    upstream = dh + _f64(d_out, (B, H))
+    with np.errstate(over="ignore", invalid="ignore"):
+        i, f, g, o = _sigmoid(pre[:, :H]), _sigmoid(pre[:, H:2 * H]), np.tanh(pre[:, 2 * H:3 * H]), _sigmoid(pre[:, 3 * H:])
+        tc = np.tanh(c_next)
+        d_c = dc + upstream * o * (1.0 - tc * tc)
+        d_pre = np.concatenate([d_c * g * (i * (1.0 - i)), d_c * c_prev * (f * (1.0 - f)), d_c * i * (1.0 - g * g),
+                                upstream * tc * (o * (1.0 - o))], 1)
+        through = d_c * f
+    live = _live_rows(lengths, t, B)
+    return np.where(live, d_pre, 0.0), np.where(live, 0.0, dh), np.where(live, through, dc)
+
+
+def rnn_cell_step(gi, gh, b_hh, h, lengths, t, relu):
+    """``cusrl_rnn_cell_fwd`` in float64: h' = tanh | relu(gi + gh + b_hh), [B, H] projections.  Returns (h_next, out)."""
+    gi, gh, h = _f64(gi), _f64(gh), _f64(h)
+    B, H = h.shape
+    with np.errstate(over="ignore", invalid="ignore"):
+        pre = gi + gh + _f64(b_hh, H)
+        nxt = np.maximum(pre, 0.0) if relu else np.tanh(pre)
+    live = _live_rows(lengths, t, B)
+    return np.where(live, nxt, h), np.where(live, nxt, 0.0)
+
+
+def rnn_cell_step_backward(out, d_out, dh, lengths, t, relu):
+    """``cusrl_rnn_cell_bwd`` in float64: the saved output y = act(pre) is all the derivative needs (1 - y^2, or [y > 0]).
+    Returns (d_pre, dh_out): a live row hands its state gradient to d_pre (dh_out = 0), an ended row passes dh through."""
+    y, dh = _f64(out), _f64(dh)
+    B, H = dh.shape
+    upstream = dh + _f64(d_out, (B, H))
+    with np.errstate(invalid="ignore"):
+        d_pre = np.where(y > 0.0, upstream, 0.0) if relu else upstream * (1.0 - y * y)
+    live = _live_rows(lengths, t, B)
+    return np.where(live, d_pre, 0.0), np.where(live, 0.0, dh)
+
+
 def categorical_sample(logits, noise):
     """Acting side of a one-hot categorical policy, restated in numpy float64: cusrl/nn/module/distribution.py:332-366
     (``OneHotCategorical(logits).sample()`` and ``log_prob`` of the sample).  The draw itself happens inside
