@@ -5,6 +5,14 @@
 // file built with -ffp-contract=off) in exactly the reference's association order, which makes advantage and
 // return BIT-EXACT with cusrl/hook/on_policy/gae.py:8-20.  Statistics accumulate in fp64 with a fixed
 // (launch-shape-determined) summation order, so results are run-to-run deterministic.
+//
+// One body per computation — what several kernels must agree on bit for bit is a function they all call:
+//   write_channel_partials  a block's {sum, sumsq} rows per channel                  gae_kernel, col_stats_kernel
+//   partials_mean_var       partial rows -> mean, unbiased variance                  stats_finalize_kernel, normalize_from_partials_kernel
+//   merged_mean_var         all-gathered [W, 2D] rows -> merged mean, variance       merge_mean_var_kernel, normalize_from_gathered_kernel
+//   normalize_share         (x - mean) / sqrt(var + eps) over a grid-stride share    the three normalise kernels
+// Host side: cusrl_gae picks the launch shape, zeroes the partial rows it leaves unwritten, launches; normalize_grid sizes
+// the three normalise launches.
 #include <stdlib.h>
 
 #include "common.hpp"
@@ -71,6 +79,45 @@ __global__ __launch_bounds__(kBlock) void next_value_kernel(const float *__restr
     if (block_counts && threadIdx.x == 0) block_counts[blockIdx.x] = total;
 }
 
+// --------------------------------------------------------------------------------------------- block partials
+// A block of BLK threads writes its {sum, sumsq} per value channel to partials[blockIdx][d][2].  Thread k owns flat
+// column blockIdx * BLK + k, i.e. channel (blockIdx * BLK + k) % D, and brings the fp64 sums of what it read (zeros if
+// nothing).  D == 1: wave_sum of each, then the waves in the order 0..n-1 (block_sum's order).  D > 1: thread d < D adds up the threads of its
+// channel in rising order, starting at the block's first column of that channel.  Fixed order, so deterministic.
+template <int BLK>
+__device__ __forceinline__ void write_channel_partials(double sum, double sumsq, int D, double *__restrict__ partials) {
+    if (D == 1) {
+        // block_sum's order for both sums through ONE exchange (one barrier at the tail of the scan, not four)
+        __shared__ double scratch[BLK / kWave][2];
+        const double s = wave_sum(sum), q = wave_sum(sumsq);
+        if ((threadIdx.x & (kWave - 1)) == 0) scratch[threadIdx.x / kWave][0] = s, scratch[threadIdx.x / kWave][1] = q;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double ts = 0.0, tq = 0.0;
+#pragma unroll
+            for (int w = 0; w < BLK / kWave; ++w) ts += scratch[w][0], tq += scratch[w][1];
+            partials[int64_t(blockIdx.x) * 2 + 0] = ts;
+            partials[int64_t(blockIdx.x) * 2 + 1] = tq;
+        }
+    } else {
+        __shared__ double red[BLK][2];
+        red[threadIdx.x][0] = sum;
+        red[threadIdx.x][1] = sumsq;
+        __syncthreads();
+        if (threadIdx.x < D) {
+            const int64_t base = int64_t(blockIdx.x) * BLK;
+            const int first = int((int64_t(threadIdx.x) - base % D + D) % D);
+            double s = 0.0, q = 0.0;
+            for (int k = first; k < BLK; k += D) {
+                s += red[k][0];
+                q += red[k][1];
+            }
+            partials[(int64_t(blockIdx.x) * D + threadIdx.x) * 2 + 0] = s;
+            partials[(int64_t(blockIdx.x) * D + threadIdx.x) * 2 + 1] = q;
+        }
+    }
+}
+
 // --------------------------------------------------------------------------------------------- GAE
 // One lane owns VEC adjacent columns of the [T, C] (C = N*D) matrices and walks time backwards.  Loads along
 // the env axis are unit-stride across lanes (16 B per lane when VEC == 4).  The horizon is consumed in chunks of
@@ -114,15 +161,12 @@ __device__ __forceinline__ typename Vec<VEC>::type pack(const float (&in)[VEC]) 
 //   kNtRet    return is stored non-temporally (its next reader is a random minibatch gather, many launches later)
 constexpr int kNtLoad = 1, kNtAdv = 2, kNtRet = 4;
 
-typedef float native_float4 __attribute__((ext_vector_type(4)));
-
 template <int VEC, bool NT>
 __device__ __forceinline__ typename Vec<VEC>::type load_stream(const float *p) {
     if constexpr (!NT) {
         return *reinterpret_cast<const typename Vec<VEC>::type *>(p);
     } else if constexpr (VEC == 4) {
-        const native_float4 v = __builtin_nontemporal_load(reinterpret_cast<const native_float4 *>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
+        return nt_load16(reinterpret_cast<const float4 *>(p));
     } else {
         return __builtin_nontemporal_load(p);
     }
@@ -133,8 +177,7 @@ __device__ __forceinline__ void store_stream(float *p, const typename Vec<VEC>::
     if constexpr (!NT) {
         *reinterpret_cast<typename Vec<VEC>::type *>(p) = v;
     } else if constexpr (VEC == 4) {
-        const native_float4 n = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(n, reinterpret_cast<native_float4 *>(p));
+        nt_store16(reinterpret_cast<float4 *>(p), v);
     } else {
         __builtin_nontemporal_store(v, p);
     }
@@ -220,39 +263,8 @@ __global__ __launch_bounds__(BLK) void gae_kernel(const float *__restrict__ rewa
         }
     }
 
-    if (partials) {
-        // per-block {sum, sumsq} per value channel, written to partials[blockIdx][d][2]
-        __shared__ double red[BLK][2];
-        if (D == 1) {
-            __shared__ double scratch[BLK / kWave][2];
-            const double s = wave_sum(sum), q = wave_sum(sumsq);
-            if ((threadIdx.x & (kWave - 1)) == 0) scratch[threadIdx.x / kWave][0] = s, scratch[threadIdx.x / kWave][1] = q;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                double ts = 0.0, tq = 0.0;
-#pragma unroll
-                for (int w = 0; w < BLK / kWave; ++w) ts += scratch[w][0], tq += scratch[w][1];
-                partials[int64_t(blockIdx.x) * 2 + 0] = ts;
-                partials[int64_t(blockIdx.x) * 2 + 1] = tq;
-            }
-        } else {
-            red[threadIdx.x][0] = active ? sum : 0.0;
-            red[threadIdx.x][1] = active ? sumsq : 0.0;
-            __syncthreads();
-            if (threadIdx.x < D) {
-                // thread k of this block owns column base + k, channel (base + k) % D
-                const int64_t base = int64_t(blockIdx.x) * BLK;
-                int first = int((int64_t(threadIdx.x) - base % D + D) % D);
-                double s = 0.0, q = 0.0;
-                for (int k = first; k < BLK; k += D) {
-                    s += red[k][0];
-                    q += red[k][1];
-                }
-                partials[(int64_t(blockIdx.x) * D + threadIdx.x) * 2 + 0] = s;
-                partials[(int64_t(blockIdx.x) * D + threadIdx.x) * 2 + 1] = q;
-            }
-        }
-    }
+    // (an inactive lane's sums are still the zeros they started as)
+    if (partials) write_channel_partials<BLK>(sum, sumsq, D, partials);
 }
 
 // --------------------------------------------------------------------------------------------- column statistics
@@ -286,31 +298,30 @@ __global__ __launch_bounds__(kBlock) void col_stats_kernel(const float *__restri
             sumsq += double(x[i]) * double(x[i]);
         }
     }
-    __shared__ double red[kBlock][2];
-    if (D == 1) {
-        __shared__ double scratch[kWavesPerBlock];
-        const double s = block_sum(sum, scratch);
-        const double q = block_sum(sumsq, scratch);
-        if (threadIdx.x == 0) {
-            partials[int64_t(blockIdx.x) * 2 + 0] = s;
-            partials[int64_t(blockIdx.x) * 2 + 1] = q;
-        }
-    } else {
-        red[threadIdx.x][0] = sum;
-        red[threadIdx.x][1] = sumsq;
-        __syncthreads();
-        if (threadIdx.x < D) {
-            const int64_t base = int64_t(blockIdx.x) * kBlock;
-            int first = int((int64_t(threadIdx.x) - base % D + D) % D);
-            double s = 0.0, q = 0.0;
-            for (int k = first; k < kBlock; k += D) {
-                s += red[k][0];
-                q += red[k][1];
-            }
-            partials[(int64_t(blockIdx.x) * D + threadIdx.x) * 2 + 0] = s;
-            partials[(int64_t(blockIdx.x) * D + threadIdx.x) * 2 + 1] = q;
-        }
+    write_channel_partials<kBlock>(sum, sumsq, D, partials);
+}
+
+// Channel d of the [P][D][2] partial rows -> mean and unbiased variance, in ONE fixed order wherever it is needed: the
+// strided per-thread sums, block_sum of the sums, block_sum of the squares, the fp64 formula.  Valid in thread 0; every
+// thread of the block calls it.  `scratch` holds kWavesPerBlock entries.
+struct MeanVar {
+    float mean, var;
+};
+
+__device__ __forceinline__ MeanVar partials_mean_var(const double *__restrict__ partials, int64_t P, int D, int d,
+                                                     int64_t count, double *scratch) {
+    double s = 0.0, q = 0.0;
+    for (int64_t p = threadIdx.x; p < P; p += kBlock) {
+        s += partials[(p * D + d) * 2 + 0];
+        q += partials[(p * D + d) * 2 + 1];
     }
+    s = block_sum(s, scratch);
+    q = block_sum(q, scratch);
+    const double n = double(count);
+    const double m = s / n;
+    // unbiased (correction = 1) like torch.var_mean; count == 1 gives 0/0 = nan like torch
+    const double v = (q - s * m) / (n - 1.0);
+    return {float(m), float(v < 0.0 ? 0.0 : v)};
 }
 
 __global__ __launch_bounds__(kBlock) void stats_finalize_kernel(const double *__restrict__ partials, int64_t P, int D,
@@ -318,33 +329,29 @@ __global__ __launch_bounds__(kBlock) void stats_finalize_kernel(const double *__
                                                                 float *__restrict__ var) {
     __shared__ double scratch[kWavesPerBlock];
     for (int d = 0; d < D; ++d) {
-        double s = 0.0, q = 0.0;
-        for (int64_t p = threadIdx.x; p < P; p += kBlock) {
-            s += partials[(p * D + d) * 2 + 0];
-            q += partials[(p * D + d) * 2 + 1];
-        }
-        s = block_sum(s, scratch);
-        q = block_sum(q, scratch);
-        if (threadIdx.x == 0) {
-            const double n = double(count);
-            const double m = s / n;
-            // unbiased (correction = 1) like torch.var_mean; count == 1 gives 0/0 = nan like torch
-            const double v = (q - s * m) / (n - 1.0);
-            mean[d] = float(m);
-            var[d] = float(v < 0.0 ? 0.0 : v);
-        }
+        const MeanVar mv = partials_mean_var(partials, P, D, d, count, scratch);
+        if (threadIdx.x == 0) mean[d] = mv.mean, var[d] = mv.var;
     }
 }
 
 // --------------------------------------------------------------------------------------------- normalise
-__global__ __launch_bounds__(kBlock) void normalize_kernel(float *__restrict__ x, const float *__restrict__ mean,
-                                                           const float *__restrict__ var, float eps, int64_t E, int D,
-                                                           int vec4) {
+// The statistics of one channel as the loop below uses them.  The three kernels agree bit for bit because they share
+// std_of and normalize_share and differ only in where mean / var come from.
+struct MeanStd {
+    float mean, sd;
+};
+
+__device__ __forceinline__ float std_of(float var, float eps) { return sqrtf(__fadd_rn(var, eps)); }  // (var + 1e-8).sqrt()   advantage.py:114
+
+// This thread's grid-stride share of x[i] = (x[i] - mean[d]) / sd[d], d = i % D; `stats(d)` returns channel d's MeanStd.
+// D == 1 with vec4 (16-byte aligned x): float4 body, the E % 4 tail by thread 0 of the grid.
+template <typename Stats>
+__device__ __forceinline__ void normalize_share(float *__restrict__ x, int64_t E, int D, int vec4, Stats stats) {
     const int64_t tid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
     const int64_t stride = int64_t(gridDim.x) * kBlock;
     if (D == 1) {
-        const float m = mean[0];
-        const float sd = sqrtf(__fadd_rn(var[0], eps));  // (var + 1e-8).sqrt()     advantage.py:114
+        const MeanStd c = stats(0);
+        const float m = c.mean, sd = c.sd;
         if (vec4) {
             const int64_t n4 = E / 4;
             for (int64_t i = tid; i < n4; i += stride) {
@@ -362,16 +369,22 @@ __global__ __launch_bounds__(kBlock) void normalize_kernel(float *__restrict__ x
         }
     } else {
         for (int64_t i = tid; i < E; i += stride) {
-            const int d = int(i % D);
-            const float sd = sqrtf(__fadd_rn(var[d], eps));
-            x[i] = __fdiv_rn(__fsub_rn(x[i], mean[d]), sd);
+            const MeanStd c = stats(int(i % D));
+            x[i] = __fdiv_rn(__fsub_rn(x[i], c.mean), c.sd);
         }
     }
 }
 
+__global__ __launch_bounds__(kBlock) void normalize_kernel(float *__restrict__ x, const float *__restrict__ mean,
+                                                           const float *__restrict__ var, float eps, int64_t E, int D,
+                                                           int vec4) {
+    // few channels, L1/L2-resident: read where they are, no staging barrier
+    normalize_share(x, E, D, vec4, [&](int d) { return MeanStd{mean[d], std_of(var[d], eps)}; });
+}
+
 // Normalisation straight from the block partials (single-process case: no cross-rank merge sits between the statistics
-// and their use): every block re-reduces the few partial rows itself (P x D x 16 bytes, L2-resident) in the same fixed
-// order as stats_finalize_kernel, so the separate one-block finalize launch disappears; block 0 also publishes mean / var.
+// and their use): every block re-reduces the few partial rows itself (P x D x 16 bytes, L2-resident) with
+// stats_finalize_kernel's function, so the separate one-block finalize launch disappears; block 0 also publishes mean / var.
 __global__ __launch_bounds__(kBlock) void normalize_from_partials_kernel(float *__restrict__ x,
                                                                          const double *__restrict__ partials, int64_t P,
                                                                          int64_t count, float eps, int64_t E, int D,
@@ -380,57 +393,21 @@ __global__ __launch_bounds__(kBlock) void normalize_from_partials_kernel(float *
     __shared__ double scratch[kWavesPerBlock];
     __shared__ float s_mean[kBlock], s_sd[kBlock];
     for (int d = 0; d < D; ++d) {
-        double s = 0.0, q = 0.0;
-        for (int64_t p = threadIdx.x; p < P; p += kBlock) {
-            s += partials[(p * D + d) * 2 + 0];
-            q += partials[(p * D + d) * 2 + 1];
-        }
-        s = block_sum(s, scratch);
-        q = block_sum(q, scratch);
+        const MeanVar mv = partials_mean_var(partials, P, D, d, count, scratch);
         if (threadIdx.x == 0) {
-            const double n = double(count);
-            const double m = s / n;
-            const double v = (q - s * m) / (n - 1.0);
-            const float mean = float(m), var = float(v < 0.0 ? 0.0 : v);
-            s_mean[d] = mean;
-            s_sd[d] = sqrtf(__fadd_rn(var, eps));
-            if (blockIdx.x == 0) mean_out[d] = mean, var_out[d] = var;
+            s_mean[d] = mv.mean;
+            s_sd[d] = std_of(mv.var, eps);
+            if (blockIdx.x == 0) mean_out[d] = mv.mean, var_out[d] = mv.var;
         }
     }
     __syncthreads();
-    const int64_t tid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    if (D == 1) {
-        const float m = s_mean[0], sd = s_sd[0];
-        if (vec4) {
-            const int64_t n4 = E / 4;
-            for (int64_t i = tid; i < n4; i += stride) {
-                float4 v = reinterpret_cast<float4 *>(x)[i];
-                v.x = __fdiv_rn(__fsub_rn(v.x, m), sd);
-                v.y = __fdiv_rn(__fsub_rn(v.y, m), sd);
-                v.z = __fdiv_rn(__fsub_rn(v.z, m), sd);
-                v.w = __fdiv_rn(__fsub_rn(v.w, m), sd);
-                reinterpret_cast<float4 *>(x)[i] = v;
-            }
-            if (tid == 0)
-                for (int64_t i = n4 * 4; i < E; ++i) x[i] = __fdiv_rn(__fsub_rn(x[i], m), sd);
-        } else {
-            for (int64_t i = tid; i < E; i += stride) x[i] = __fdiv_rn(__fsub_rn(x[i], m), sd);
-        }
-    } else {
-        for (int64_t i = tid; i < E; i += stride) {
-            const int d = int(i % D);
-            x[i] = __fdiv_rn(__fsub_rn(x[i], s_mean[d]), s_sd[d]);
-        }
-    }
+    normalize_share(x, E, D, vec4, [&](int d) { return MeanStd{s_mean[d], s_sd[d]}; });
 }
 
 // --------------------------------------------------------------------------------------------- merge
-__global__ void merge_mean_var_kernel(const float *__restrict__ gathered, int W, int D, float *__restrict__ mean,
-                                      float *__restrict__ var) {
-    const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= D) return;
-    // torch.mean(all_means, dim=0); torch.mean(all_vars + (all_means - mean).square(), dim=0)
+// Channel d of the all-gathered [W, 2D] rows (every rank's mean | var) -> the merged statistics:
+// torch.mean(all_means, dim=0); torch.mean(all_vars + (all_means - mean).square(), dim=0), rank 0 first.
+__device__ __forceinline__ MeanVar merged_mean_var(const float *__restrict__ gathered, int W, int D, int d) {
     float s = 0.0f;
     for (int r = 0; r < W; ++r) s = __fadd_rn(s, gathered[int64_t(r) * 2 * D + d]);
     const float m = __fdiv_rn(s, float(W));
@@ -439,58 +416,34 @@ __global__ void merge_mean_var_kernel(const float *__restrict__ gathered, int W,
         const float e = __fsub_rn(gathered[int64_t(r) * 2 * D + d], m);
         q = __fadd_rn(q, __fadd_rn(gathered[int64_t(r) * 2 * D + D + d], __fmul_rn(e, e)));
     }
-    mean[d] = m;
-    var[d] = __fdiv_rn(q, float(W));
+    return {m, __fdiv_rn(q, float(W))};
 }
 
-// Merge + normalise in one launch (a job with several ranks: the all-gathered [W, 2D] rows of every rank's mean | var sit
-// between the statistics and their use): every block re-derives the merged statistics with merge_mean_var_kernel's operations in
-// its order (W x 2D floats, L2-resident), then normalises its share like normalize_kernel; block 0 publishes mean / var.
+__global__ void merge_mean_var_kernel(const float *__restrict__ gathered, int W, int D, float *__restrict__ mean,
+                                      float *__restrict__ var) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= D) return;
+    const MeanVar mv = merged_mean_var(gathered, W, D, d);
+    mean[d] = mv.mean;
+    var[d] = mv.var;
+}
+
+// Merge + normalise in one launch (a job with several ranks: the all-gathered rows sit between the statistics and their
+// use): every block re-derives the merged statistics itself (W x 2D floats, L2-resident), then normalises its share;
+// block 0 publishes mean / var.
 __global__ __launch_bounds__(kBlock) void normalize_from_gathered_kernel(float *__restrict__ x, const float *__restrict__ gathered,
                                                                          int W, float eps, int64_t E, int D, int vec4,
                                                                          float *__restrict__ mean_out, float *__restrict__ var_out) {
     __shared__ float s_mean[kBlock], s_sd[kBlock];
     if (threadIdx.x < D) {
         const int d = threadIdx.x;
-        float s = 0.0f;
-        for (int r = 0; r < W; ++r) s = __fadd_rn(s, gathered[int64_t(r) * 2 * D + d]);
-        const float m = __fdiv_rn(s, float(W));
-        float q = 0.0f;
-        for (int r = 0; r < W; ++r) {
-            const float e = __fsub_rn(gathered[int64_t(r) * 2 * D + d], m);
-            q = __fadd_rn(q, __fadd_rn(gathered[int64_t(r) * 2 * D + D + d], __fmul_rn(e, e)));
-        }
-        const float var = __fdiv_rn(q, float(W));
-        s_mean[d] = m;
-        s_sd[d] = sqrtf(__fadd_rn(var, eps));
-        if (blockIdx.x == 0) mean_out[d] = m, var_out[d] = var;
+        const MeanVar mv = merged_mean_var(gathered, W, D, d);
+        s_mean[d] = mv.mean;
+        s_sd[d] = std_of(mv.var, eps);
+        if (blockIdx.x == 0) mean_out[d] = mv.mean, var_out[d] = mv.var;
     }
     __syncthreads();
-    const int64_t tid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    if (D == 1) {
-        const float m = s_mean[0], sd = s_sd[0];
-        if (vec4) {
-            const int64_t n4 = E / 4;
-            for (int64_t i = tid; i < n4; i += stride) {
-                float4 v = reinterpret_cast<float4 *>(x)[i];
-                v.x = __fdiv_rn(__fsub_rn(v.x, m), sd);
-                v.y = __fdiv_rn(__fsub_rn(v.y, m), sd);
-                v.z = __fdiv_rn(__fsub_rn(v.z, m), sd);
-                v.w = __fdiv_rn(__fsub_rn(v.w, m), sd);
-                reinterpret_cast<float4 *>(x)[i] = v;
-            }
-            if (tid == 0)
-                for (int64_t i = n4 * 4; i < E; ++i) x[i] = __fdiv_rn(__fsub_rn(x[i], m), sd);
-        } else {
-            for (int64_t i = tid; i < E; i += stride) x[i] = __fdiv_rn(__fsub_rn(x[i], m), sd);
-        }
-    } else {
-        for (int64_t i = tid; i < E; i += stride) {
-            const int d = int(i % D);
-            x[i] = __fdiv_rn(__fsub_rn(x[i], s_mean[d]), s_sd[d]);
-        }
-    }
+    normalize_share(x, E, D, vec4, [&](int d) { return MeanStd{s_mean[d], s_sd[d]}; });
 }
 
 }  // namespace cusrl
@@ -546,36 +499,34 @@ static int gae_block(int64_t columns) {
     return ceil_div(columns / 4, 256) <= 5 * 256 ? 256 : 128;
 }
 
-template <int POLICY, int BLK, bool TWO>
-static void launch_gae_one(uint32_t blocks, hipStream_t s, const float *reward, const float *value, const float *next_value,
-                           const uint8_t *done, float *advantage, float *ret, double *partials, int T, int64_t N, int D,
-                           float g, float c_adv, float c_val) {
-    hipLaunchKernelGGL((gae_kernel<4, 6, TWO, BLK, POLICY>), dim3(blocks), dim3(BLK), 0, s, reward, value, next_value, done,
-                       advantage, ret, partials, T, N, D, g, c_adv, c_val);
+// One launch of the scan: the kernel's arguments and its grid, passed whole through the instantiation choice below.
+struct GaeLaunch {
+    const float *reward, *value, *next_value;
+    const uint8_t *done;
+    float *advantage, *ret;
+    double *partials;
+    int T;
+    int64_t N;
+    int D;
+    float gamma, c_adv, c_val;
+    bool two;  // a second lambda for the return
+    uint32_t blocks;
+    hipStream_t stream;
+};
+
+template <int VEC, int TC, int BLK, int POLICY = 0>
+static void launch_gae(const GaeLaunch &a) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(BLK), 0, a.stream, a.reward, a.value, a.next_value, a.done,
+                           a.advantage, a.ret, a.partials, a.T, a.N, a.D, a.gamma, a.c_adv, a.c_val);
+    };
+    a.two ? go(gae_kernel<VEC, TC, true, BLK, POLICY>) : go(gae_kernel<VEC, TC, false, BLK, POLICY>);
 }
 
+// the at-scale shape: 4 columns per lane, 6 steps per load round, {3 cache policies} x {128, 256 threads}
 template <int POLICY>
-static void launch_gae_policy(int blk, bool two, uint32_t blocks, hipStream_t s, const float *reward, const float *value,
-                              const float *next_value, const uint8_t *done, float *advantage, float *ret, double *partials,
-                              int T, int64_t N, int D, float g, float c_adv, float c_val) {
-#define CUSRL_GAE_ARGS blocks, s, reward, value, next_value, done, advantage, ret, partials, T, N, D, g, c_adv, c_val
-    if (blk == 256)
-        two ? launch_gae_one<POLICY, 256, true>(CUSRL_GAE_ARGS) : launch_gae_one<POLICY, 256, false>(CUSRL_GAE_ARGS);
-    else
-        two ? launch_gae_one<POLICY, 128, true>(CUSRL_GAE_ARGS) : launch_gae_one<POLICY, 128, false>(CUSRL_GAE_ARGS);
-#undef CUSRL_GAE_ARGS
-}
-
-static void launch_gae_scaled(int policy, int blk, bool two, uint32_t blocks, hipStream_t s, const float *reward,
-                              const float *value, const float *next_value, const uint8_t *done, float *advantage, float *ret,
-                              double *partials, int T, int64_t N, int D, float g, float c_adv, float c_val) {
-#define CUSRL_GAE_ARGS blk, two, blocks, s, reward, value, next_value, done, advantage, ret, partials, T, N, D, g, c_adv, c_val
-    switch (policy) {
-        case 0: launch_gae_policy<0>(CUSRL_GAE_ARGS); break;
-        case kNtLoad | kNtRet: launch_gae_policy<kNtLoad | kNtRet>(CUSRL_GAE_ARGS); break;
-        default: launch_gae_policy<kNtLoad | kNtAdv | kNtRet>(CUSRL_GAE_ARGS); break;
-    }
-#undef CUSRL_GAE_ARGS
+static void launch_gae_scaled(int blk, const GaeLaunch &a) {
+    blk == 256 ? launch_gae<4, 6, 256, POLICY>(a) : launch_gae<4, 6, 128, POLICY>(a);
 }
 
 // Partial rows no block of the chosen launch shape writes.  A KERNEL, not hipMemsetAsync: a memset becomes a memset NODE when
@@ -608,48 +559,31 @@ extern "C" int cusrl_gae(const float *reward, const float *value, const float *n
     const bool two = lamda_value >= 0.0;
     const float c_val = two ? float(gamma * lamda_value) : c_adv;
     const int64_t C = N * D;
-    hipStream_t s = as_stream(stream);
-    // 4 columns per lane only when that still fills the chip (>= 256 blocks); small rollouts (config 2: 4096 envs)
-    // are latency-bound and want every lane they can get
-    if (gae_vec4(reward, value, next_value, done, advantage, ret, N, D) && C >= int64_t(4) * kBlock * 256) {
-        const int policy = gae_policy(T * C);
-        const int blk = gae_block(C);
-        const int64_t blocks = ceil_div(C / 4, blk);
-        // the host sizes `stat_partials` with cusrl_gae_num_partials (>= blocks); unused rows are zeroed
-        if (stat_partials) {
-            const int64_t rows = cusrl_gae_num_partials(T, N, D);
-            if (rows > blocks) zero_partial_rows(stat_partials + blocks * D * 2, (rows - blocks) * D * 2, s);
-        }
-        launch_gae_scaled(policy, blk, two, uint32_t(blocks), s, reward, value, next_value, done, advantage, ret,
-                          stat_partials, int(T), N, int(D), g, c_adv, c_val);
-    } else if (C <= 65536 && T <= 32) {
-        // small rollouts (config 2: 4096 columns x 24 steps): one-wave blocks on 4x more CUs, the whole horizon in ONE
-        // load round (32 steps x 4 streams in flight per lane) — the launch is one memory latency + the scan
-        const int64_t blocks = ceil_div(C, kWave);
-        if (stat_partials) {
-            const int64_t rows = cusrl_gae_num_partials(T, N, D);
-            if (rows > blocks) zero_partial_rows(stat_partials + blocks * D * 2, (rows - blocks) * D * 2, s);
-        }
-        if (two)
-            hipLaunchKernelGGL((gae_kernel<1, 32, true, kWave>), dim3(uint32_t(blocks)), dim3(kWave), 0, s, reward, value,
-                               next_value, done, advantage, ret, stat_partials, int(T), N, int(D), g, c_adv, c_val);
-        else
-            hipLaunchKernelGGL((gae_kernel<1, 32, false, kWave>), dim3(uint32_t(blocks)), dim3(kWave), 0, s, reward, value,
-                               next_value, done, advantage, ret, stat_partials, int(T), N, int(D), g, c_adv, c_val);
-    } else {
-        const int64_t blocks = ceil_div(C, kBlock);
-        if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
-        if (stat_partials) {
-            const int64_t rows = cusrl_gae_num_partials(T, N, D);
-            if (rows > blocks) zero_partial_rows(stat_partials + blocks * D * 2, (rows - blocks) * D * 2, s);
-        }
-        if (two)
-            hipLaunchKernelGGL((gae_kernel<1, 8, true>), dim3(uint32_t(blocks)), dim3(kBlock), 0, s, reward, value,
-                               next_value, done, advantage, ret, stat_partials, int(T), N, int(D), g, c_adv, c_val);
-        else
-            hipLaunchKernelGGL((gae_kernel<1, 8, false>), dim3(uint32_t(blocks)), dim3(kBlock), 0, s, reward, value,
-                               next_value, done, advantage, ret, stat_partials, int(T), N, int(D), g, c_adv, c_val);
+    // The launch shape.  4 columns per lane only when that still fills the chip (>= 256 blocks); small rollouts (config 2:
+    // 4096 columns x 24 steps) are latency-bound and want every lane they can get: one-wave blocks on 4x more CUs, the
+    // whole horizon in ONE load round (32 steps x 4 streams in flight per lane) — one memory latency + the scan.
+    const bool scaled = gae_vec4(reward, value, next_value, done, advantage, ret, N, D) && C >= int64_t(4) * kBlock * 256;
+    const bool one_wave = !scaled && C <= 65536 && T <= 32;
+    const int blk = scaled ? gae_block(C) : one_wave ? kWave : kBlock;
+    const int64_t blocks = ceil_div(scaled ? C / 4 : C, blk);
+    if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
+    const GaeLaunch a = {reward, value, next_value, done, advantage, ret, stat_partials, int(T), N, int(D), g, c_adv, c_val,
+                         two, uint32_t(blocks), as_stream(stream)};
+    // the host sizes `stat_partials` with cusrl_gae_num_partials (>= blocks); the rows this shape does not write are zeroed
+    if (stat_partials) {
+        const int64_t rows = cusrl_gae_num_partials(T, N, D);
+        if (rows > blocks) zero_partial_rows(stat_partials + blocks * D * 2, (rows - blocks) * D * 2, a.stream);
     }
+    if (one_wave)
+        launch_gae<1, 32, kWave>(a);
+    else if (!scaled)
+        launch_gae<1, 8, kBlock>(a);
+    else
+        switch (gae_policy(T * C)) {
+            case 0: launch_gae_scaled<0>(blk, a); break;
+            case kNtLoad | kNtRet: launch_gae_scaled<kNtLoad | kNtRet>(blk, a); break;
+            default: launch_gae_scaled<kNtLoad | kNtAdv | kNtRet>(blk, a); break;
+        }
     return launch_status();
 }
 
@@ -680,17 +614,28 @@ extern "C" int cusrl_stats_finalize(const double *stat_partials, int64_t num_par
     return launch_status();
 }
 
+// Grid of the three normalise entry points: one thread per float4 (+ 1 for the tail) when D == 1 and x is 16-byte aligned,
+// else one per element; at most 2048 blocks, grid-stride beyond.
+struct NormalizeGrid {
+    int vec4;
+    uint32_t blocks;
+};
+
+static NormalizeGrid normalize_grid(const float *x, int64_t E, int64_t D) {
+    const int vec4 = D == 1 && aligned(x, 16);
+    const int64_t blocks = ceil_div(vec4 ? E / 4 + 1 : E, kBlock);
+    return {vec4, uint32_t(blocks > 2048 ? 2048 : blocks)};
+}
+
 extern "C" int cusrl_normalize(float *x, const float *mean, const float *var, float eps, int64_t rows, int64_t D,
                                void *stream) {
     if (rows < 0 || D < 0) return CUSRL_E_INVALID;
     if (rows == 0 || D == 0) return 0;
     if (!x || !mean || !var) return CUSRL_E_INVALID;
     const int64_t E = rows * D;
-    const int vec4 = D == 1 && aligned(x, 16);
-    int64_t blocks = ceil_div(vec4 ? E / 4 + 1 : E, kBlock);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(normalize_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), x, mean, var, eps,
-                       E, int(D), vec4);
+    const NormalizeGrid grid = normalize_grid(x, E, D);
+    hipLaunchKernelGGL(normalize_kernel, dim3(grid.blocks), dim3(kBlock), 0, as_stream(stream), x, mean, var, eps,
+                       E, int(D), grid.vec4);
     return launch_status();
 }
 
@@ -702,11 +647,9 @@ extern "C" int cusrl_normalize_from_partials(float *x, const double *stat_partia
     if (!x || !stat_partials || !mean_out || !var_out) return CUSRL_E_INVALID;
     if (D > kBlock) return CUSRL_E_UNSUPPORTED;
     const int64_t E = rows * D;
-    const int vec4 = D == 1 && aligned(x, 16);
-    int64_t blocks = ceil_div(vec4 ? E / 4 + 1 : E, kBlock);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(normalize_from_partials_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), x,
-                       stat_partials, num_partials, count, eps, E, int(D), vec4, mean_out, var_out);
+    const NormalizeGrid grid = normalize_grid(x, E, D);
+    hipLaunchKernelGGL(normalize_from_partials_kernel, dim3(grid.blocks), dim3(kBlock), 0, as_stream(stream), x,
+                       stat_partials, num_partials, count, eps, E, int(D), grid.vec4, mean_out, var_out);
     return launch_status();
 }
 
@@ -727,10 +670,8 @@ extern "C" int cusrl_normalize_from_gathered(float *x, const float *gathered, in
     if (!x || !gathered || !mean_out || !var_out) return CUSRL_E_INVALID;
     if (D > kBlock) return CUSRL_E_UNSUPPORTED;
     const int64_t E = rows * D;
-    const int vec4 = D == 1 && aligned(x, 16);
-    int64_t blocks = ceil_div(vec4 ? E / 4 + 1 : E, kBlock);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(normalize_from_gathered_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), x, gathered,
-                       int(W), eps, E, int(D), vec4, mean_out, var_out);
+    const NormalizeGrid grid = normalize_grid(x, E, D);
+    hipLaunchKernelGGL(normalize_from_gathered_kernel, dim3(grid.blocks), dim3(kBlock), 0, as_stream(stream), x, gathered,
+                       int(W), eps, E, int(D), grid.vec4, mean_out, var_out);
     return launch_status();
 }

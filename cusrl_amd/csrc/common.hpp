@@ -39,6 +39,19 @@ inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintp
 
 __device__ __forceinline__ bool aligned_ptr16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- 16-byte accesses with the non-temporal hint (streams nobody reads again soon); clang's builtins take native vectors ----
+typedef float native_float4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float4 nt_load16(const float4 *p) {
+    const native_float4 v = __builtin_nontemporal_load(reinterpret_cast<const native_float4 *>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ void nt_store16(float4 *p, const float4 &v) {
+    const native_float4 n = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(n, reinterpret_cast<native_float4 *>(p));
+}
+
 // ---- wave / block reductions (wave64 shuffles; LDS only across the 4 waves of a block) ----
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
@@ -61,6 +74,27 @@ __device__ __forceinline__ T block_sum(T v, T *scratch) {
     }
     __syncthreads();
     return total;
+}
+
+// Wave-wide sum of a double by DPP moves of its two halves (quad swaps, row rotations, row broadcasts): six steps of
+// 2 v_mov_dpp + 1 v_add_f64 instead of six ds_bpermute round trips per half; fixed order; the total lands in lane 63.
+// NOT wave_sum's order (neighbours first here, halves first there): the two give different last bits, so a sum whose
+// bits are pinned stays with the one it was written with.
+template <int kCtrl>
+__device__ __forceinline__ double dpp_move(double v) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), kCtrl, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), kCtrl, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double wave_sum_to_last_lane(double v) {
+    v += dpp_move<0xb1>(v);   // quad_perm:[1,0,3,2]
+    v += dpp_move<0x4e>(v);   // quad_perm:[2,3,0,1]
+    v += dpp_move<0x124>(v);  // row_ror:4
+    v += dpp_move<0x128>(v);  // row_ror:8   -> every lane holds its row's (16 lanes) sum
+    v += dpp_move<0x142>(v);  // row_bcast:15 -> rows 1 and 3 add the row in front of them
+    v += dpp_move<0x143>(v);  // row_bcast:31 -> the upper half adds lane 31: lane 63 holds the wave's sum
+    return v;
 }
 
 // Exclusive prefix sum of one int per thread over the block; also returns the block total.

@@ -10,26 +10,20 @@
 // clipping, d loss / d logp) itself — no LDS tile, ONE barrier per block (for the block's fp64 partial sums).  A std handed
 // over as its [A] vector keeps d_std in four registers per lane, reduced over the wave's rows by a stride-LPR shuffle tree.
 // Per element one v_rcp_f32 of sigma and multiplications instead of five IEEE divisions (the textbook form was bound by its
-// own VALU instructions).  Any other width: ppo_loss_rowwise_kernel (one lane per row).  Scalar statistics: fp32 lane sums,
-// fp64 wave / block / grid sums in fixed order.
+// own VALU instructions).  Any other width: ppo_loss_rowwise_kernel (one lane per row); one-hot categorical policies:
+// ppo_loss_categorical_kernel; the value term alone: value_loss_kernel.  Scalar statistics: fp32 lane sums (row groups) or
+// fp64 lane sums (one lane per row), fp64 wave / block / grid sums in fixed order.
+//
+// One body per computation: row_scalars (ratio, clamp, min term, d loss / d logp) and value_scalars (one value channel) are
+// the per-row arithmetic of EVERY kernel here; park_wave_sums / store_block_partials / write_block_partials reduce a block's
+// kSums fp64 sums (5 for the objective, 2 for the value term) and sum_partial_rows adds the blocks' rows up in the finalize
+// kernels; loss_rows_per_block_of(LPR) is the one expression behind RowGroup<LPR>::kRowsPerBlock and the host's grid.
 #include <float.h>
 #include <stdlib.h>
 
 #include "common.hpp"
 
 namespace cusrl {
-
-// the [B, A] streams with the non-temporal hint (kStream); clang's builtins take native vectors
-typedef float loss_native_float4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 loss_nt_load(const float4 *p) {
-    const loss_native_float4 v = __builtin_nontemporal_load(reinterpret_cast<const loss_native_float4 *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void loss_nt_store(float4 *p, const float4 &v) {
-    loss_native_float4 n;
-    n.x = v.x, n.y = v.y, n.z = v.z, n.w = v.w;
-    __builtin_nontemporal_store(n, reinterpret_cast<loss_native_float4 *>(p));
-}
 
 struct LossParams {
     float lo, hi;            // fp32(1 - clip), fp32(1 + clip)                         ppo.py:16
@@ -41,163 +35,11 @@ struct LossParams {
 __device__ __forceinline__ float log_sqrt_2pi() { return 0.918938533204672741780329736406f; }  // log(sqrt(2 pi))
 __device__ __forceinline__ float entropy_const() { return 1.418938533204672741780329736406f; }  // 0.5 + 0.5 log(2 pi)
 
-// Per-row scalar part shared by both kernels.  Returns d(loss)/d(logp_row).
-__device__ __forceinline__ float row_terms(float logp, float entropy, float old_logp, float adv, const LossParams &p,
-                                           double &sur_acc, double &ent_acc, double &abs_lr_acc, float &ratio_out,
-                                           float &lr_out) {
-    const float lr = logp - old_logp;                 // action_logp_ratio        common.py:35
-    abs_lr_acc += double(fabsf(lr));                  // metric `ratio` = |logp ratio|   common.py:47
-    const float ratio = expf(lr);                     // action_prob_ratio        common.py:41
-    const float s1 = adv * ratio;                     // ppo.py:14
-    const float rc = fminf(fmaxf(ratio, p.lo), p.hi); // clamp                    ppo.py:16
-    const float s2 = adv * rc;
-    sur_acc += double(fminf(s1, s2));
-    ent_acc += double(entropy);
-    const bool inside = ratio >= p.lo && ratio <= p.hi;
-    float d_ratio;  // autograd of min(): ties split evenly, clamp passes on the closed interval
-    if (s1 < s2)
-        d_ratio = adv;
-    else if (s1 > s2)
-        d_ratio = inside ? adv : 0.0f;
-    else
-        d_ratio = 0.5f * adv + (inside ? 0.5f * adv : 0.0f);
-    ratio_out = ratio;
-    lr_out = lr;
-    return p.g_sur * d_ratio * ratio;
-}
-
-// One value channel: (clipped) squared error, its gradient, the `value` metric.  `v` (the old value) is only read in
-// the clipped form.
-__device__ __forceinline__ void value_term(float cv, float R, float v, float *__restrict__ d_value_slot,
-                                           const LossParams &p, double &val_acc, double &value_sum_acc) {
-    value_sum_acc += double(cv);  // metric `value` = curr_value.sum(-1)        value.py:141
-    const float e1 = cv - R, l1 = e1 * e1, g1 = 2.0f * e1;
-    float g;
-    if (p.value_clip < 0.0f) {
-        val_acc += double(l1);  // mse_loss(return, curr_value)             value.py:132
-        g = g1;
-    } else {
-        const float c = p.value_clip;
-        const float dv = cv - v;
-        const float dvc = fminf(fmaxf(dv, -c), c);
-        const float e2 = (v + dvc) - R, l2 = e2 * e2;   // value.py:85-89
-        const float g2 = (dv >= -c && dv <= c) ? 2.0f * e2 : 0.0f;
-        val_acc += double(fmaxf(l1, l2));
-        g = l1 > l2 ? g1 : (l1 < l2 ? g2 : 0.5f * (g1 + g2));
-    }
-    if (d_value_slot) *d_value_slot = p.g_val * g;
-}
-
-__device__ __forceinline__ void value_terms(const float *__restrict__ ret, const float *__restrict__ curr_value,
-                                            const float *__restrict__ old_value, float *__restrict__ d_value,
-                                            int64_t row, int D, const LossParams &p, double &val_acc,
-                                            double &value_sum_acc) {
-    for (int d = 0; d < D; ++d) {
-        const int64_t i = row * D + d;
-        value_term(curr_value[i], ret[i], p.value_clip < 0.0f ? 0.0f : old_value[i], d_value ? d_value + i : nullptr, p,
-                   val_acc, value_sum_acc);
-    }
-}
-
 constexpr int kLossSums = 5;  // value loss, surrogate, entropy, |logp ratio|, value
 
-// All five sums through ONE LDS exchange: wave-shuffle each, lane 0 of every wave parks its five totals, the first five
-// threads add the four waves up in fixed order.  kAccumulate: the block ADDS to its row instead of overwriting it — the
-// row belongs to this block alone, so a plain read-modify-write is race-free and launches of the same grid, ordered on
-// one stream, build up per-block running sums in a fixed order (CUSRL_LOSS_DEFER, see cusrl_ppo_loss_fwd_bwd).
-// Wave-wide sum of a double by DPP moves of its two halves (quad swaps, row rotations, row broadcasts): six steps of
-// 2 v_mov_dpp + 1 v_add_f64 instead of six ds_bpermute round trips per half; fixed order; the total lands in lane 63.
-template <int kCtrl>
-__device__ __forceinline__ double dpp_move(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), kCtrl, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), kCtrl, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_sum_to_last_lane(double v) {
-    v += dpp_move<0xb1>(v);   // quad_perm:[1,0,3,2]
-    v += dpp_move<0x4e>(v);   // quad_perm:[2,3,0,1]
-    v += dpp_move<0x124>(v);  // row_ror:4
-    v += dpp_move<0x128>(v);  // row_ror:8   -> every lane holds its row's (16 lanes) sum
-    v += dpp_move<0x142>(v);  // row_bcast:15 -> rows 1 and 3 add the row in front of them
-    v += dpp_move<0x143>(v);  // row_bcast:31 -> the upper half adds lane 31: lane 63 holds the wave's sum
-    return v;
-}
-
-__device__ __forceinline__ void park_wave_sums(const double (&acc)[kLossSums], double (*scratch)[kLossSums]) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int k = 0; k < kLossSums; ++k) {
-        const double total = wave_sum_to_last_lane(acc[k]);
-        if (lane == kWave - 1) scratch[wave][k] = total;
-    }
-}
-
-__device__ __forceinline__ void store_block_partials(double (*scratch)[kLossSums], double *__restrict__ partials,
-                                                     bool accumulate) {
-    if (threadIdx.x < kLossSums) {
-        double total = 0.0;
-#pragma unroll
-        for (int w = 0; w < kWavesPerBlock; ++w) total += scratch[w][threadIdx.x];
-        double *slot = partials + int64_t(blockIdx.x) * kLossSums + threadIdx.x;
-        *slot = accumulate ? *slot + total : total;
-    }
-}
-
-__device__ __forceinline__ void write_block_partials(const double (&acc)[kLossSums], double *__restrict__ partials,
-                                                     bool accumulate = false) {
-    __shared__ double scratch[kWavesPerBlock][kLossSums];
-    park_wave_sums(acc, scratch);
-    __syncthreads();
-    store_block_partials(scratch, partials, accumulate);
-}
-
-__device__ __forceinline__ void reduce_std_rows(const float *in, int64_t rows, int A, float *__restrict__ out);
-__device__ __forceinline__ void finalize_losses(const double *partials, int64_t P, int64_t B, int D,
-                                                const LossParams &p, float *__restrict__ losses_out,
-                                                const float *d_std_partials, int A, float *__restrict__ d_std_vector);
-
-// ---- the row-group layout of the [B, A] streams (A = 4 * LPR) --------------------------------------------------------
-// A row is LPR 16-byte chunks.  The LPR chunks of a row are held by LPR ADJACENT LANES OF ONE WAVE, a wave covers
-// kRowsPerWave = 64 / LPR consecutive rows per round (64 % LPR lanes idle: 1 of 64 at A = 12), so
-//   * every global access is a dwordx4 and a wave's load covers kActive * 16 contiguous bytes (coalesced);
-//   * the row reductions (log-prob, entropy) are LPR wave shuffles among neighbours — no LDS tile, no barrier — and every
-//     lane of the row then evaluates the scalar part (ratio, clip, d loss / d logp) itself: nothing to publish;
-//   * a lane's chunks all belong to ONE column group (lane % LPR), so with a std vector its d_std contributions add up
-//     in four registers and the column sums of a wave are a strided shuffle tree — no select chain.
-// One barrier per block (the cross-wave exchange of the five loss sums and the d_std column sums), against four in the
-// flat-chunk layout this replaces (round 2: 0.41 of the HBM roofline with a std vector, bound by its own barriers).
-// kRounds chunks per lane are requested before anything is computed (memory-level parallelism).
-template <int LPR>
-struct RowGroup {
-    static constexpr int kRowsPerWave = kWave / LPR;
-    static constexpr int kActive = kRowsPerWave * LPR;
-    static constexpr int kRounds = LPR >= 4 ? 4 : LPR;
-    static constexpr int kRowsPerBlock = kWavesPerBlock * kRowsPerWave * kRounds;
-    static constexpr int kTreeStart = kRowsPerWave > 32 ? 32 : kRowsPerWave > 16 ? 16 : kRowsPerWave > 8 ? 8 : 4;
-};
-
-static int loss_rows_per_block(int64_t A) {
-    if (A % 4 != 0 || A / 4 > 8) return kBlock;  // row-wise kernel: one lane per row
-    switch (A / 4) {
-        case 1: return RowGroup<1>::kRowsPerBlock;
-        case 2: return RowGroup<2>::kRowsPerBlock;
-        case 3: return RowGroup<3>::kRowsPerBlock;
-        case 4: return RowGroup<4>::kRowsPerBlock;
-        case 5: return RowGroup<5>::kRowsPerBlock;
-        case 6: return RowGroup<6>::kRowsPerBlock;
-        case 7: return RowGroup<7>::kRowsPerBlock;
-        default: return RowGroup<8>::kRowsPerBlock;
-    }
-}
-constexpr int kMinLossRowsPerBlock = RowGroup<8>::kRowsPerBlock;  // the smallest of them: workspace bound for any A
-
-// kStdVec: `std` is ONE row [A] shared by every sample (a state-independent std vector, distribution.py:228-247)
-// instead of a [B, A] matrix: it is read once per lane instead of streamed, and d_std leaves the kernel as per-block
-// column sums [A] (the gradient of the vector) instead of a [B, A] matrix that a sum(0) launch would have to reduce —
-// 96 of the 264 bytes per sample disappear.
-// The scalar part of a row with float results (the row-group kernel sums at most kRounds of them per lane in fp32 before the
-// fp64 wave / block reduction): same decisions as row_terms / value_term above.
+// The scalar part of a row, ONE body for every kernel: ratio, clamp, the surrogate's min term and d(loss)/d(logp_row).
+// Float results; callers add them into their sums (the row-group kernel at most kRounds per lane in fp32 before the fp64
+// wave / block reduction, the one-lane-per-row kernels straight into fp64).
 struct RowScalars {
     float dlp, ratio, lr, min_term, abs_lr;
 };
@@ -218,6 +60,7 @@ __device__ __forceinline__ RowScalars row_scalars(float logp, float old_logp, fl
     return r;
 }
 
+// One value channel: (clipped) squared error and its gradient.  `v` (the old value) is only read in the clipped form.
 __device__ __forceinline__ void value_scalars(float cv, float R, float v, const LossParams &p, float &loss, float &grad) {
     const float e1 = cv - R, l1 = e1 * e1, g1 = 2.0f * e1;
     if (p.value_clip < 0.0f) {  // uniform
@@ -231,20 +74,124 @@ __device__ __forceinline__ void value_scalars(float cv, float R, float v, const 
     grad = p.g_val * (l1 > l2 ? g1 : (l1 < l2 ? g2 : 0.5f * (g1 + g2)));
 }
 
+// The row-wise sums of one lane's row for the one-lane-per-row kernels: surrogate, entropy, |logp ratio| into fp64.
+__device__ __forceinline__ void add_row_sums(const RowScalars &r, float entropy, double (&acc)[kLossSums]) {
+    acc[1] += double(r.min_term);
+    acc[2] += double(entropy);
+    acc[3] += double(r.abs_lr);
+}
+
+__device__ __forceinline__ void value_terms(const float *__restrict__ ret, const float *__restrict__ curr_value,
+                                            const float *__restrict__ old_value, float *__restrict__ d_value,
+                                            int64_t row, int D, const LossParams &p, double &val_acc,
+                                            double &value_sum_acc) {
+    for (int d = 0; d < D; ++d) {
+        const int64_t i = row * D + d;
+        float loss, grad;
+        value_scalars(curr_value[i], ret[i], p.value_clip < 0.0f ? 0.0f : old_value[i], p, loss, grad);
+        val_acc += double(loss);
+        value_sum_acc += double(curr_value[i]);  // metric `value` = curr_value.sum(-1)        value.py:141
+        if (d_value) d_value[i] = grad;
+    }
+}
+
+// A block's kSums fp64 sums through ONE LDS exchange: a DPP wave sum of each (wave_sum_to_last_lane, common.hpp), lane 63
+// of every wave parks its totals, the first kSums threads add the four waves up in fixed order.  accumulate: the block
+// ADDS to its row instead of overwriting it — the row belongs to this block alone, so a plain read-modify-write is
+// race-free and launches of the same grid, ordered on one stream, build up per-block running sums in a fixed order
+// (CUSRL_LOSS_DEFER, see cusrl_ppo_loss_fwd_bwd).
+template <int kSums>
+__device__ __forceinline__ void park_wave_sums(const double (&acc)[kSums], double (*scratch)[kSums]) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) {
+        const double total = wave_sum_to_last_lane(acc[k]);
+        if (lane == kWave - 1) scratch[wave][k] = total;
+    }
+}
+
+template <int kSums>
+__device__ __forceinline__ void store_block_partials(double (*scratch)[kSums], double *__restrict__ partials, bool accumulate) {
+    if (threadIdx.x < kSums) {
+        double total = 0.0;
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) total += scratch[w][threadIdx.x];
+        double *slot = partials + int64_t(blockIdx.x) * kSums + threadIdx.x;
+        *slot = accumulate ? *slot + total : total;
+    }
+}
+
+template <int kSums>
+__device__ __forceinline__ void write_block_partials(const double (&acc)[kSums], double *__restrict__ partials,
+                                                     bool accumulate = false) {
+    __shared__ double scratch[kWavesPerBlock][kSums];
+    park_wave_sums(acc, scratch);
+    __syncthreads();
+    store_block_partials(scratch, partials, accumulate);
+}
+
+// Sum k of the P partial rows [P][kSums] by one block in fixed order (strided per-thread sums, then block_sum); valid in
+// thread 0.  `scratch` holds kWavesPerBlock entries.
+template <int kSums>
+__device__ __forceinline__ double sum_partial_rows(const double *__restrict__ partials, int64_t P, int k, double *scratch) {
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < P; i += kBlock) s += partials[i * kSums + k];
+    return block_sum(s, scratch);
+}
+
+__device__ __forceinline__ void reduce_std_rows(const float *in, int64_t rows, int A, float *__restrict__ out);
+__device__ __forceinline__ void finalize_losses(const double *partials, int64_t P, int64_t B, int D,
+                                                const LossParams &p, float *__restrict__ losses_out,
+                                                const float *d_std_partials, int A, float *__restrict__ d_std_vector);
+
+// ---- the row-group layout of the [B, A] streams (A = 4 * LPR) --------------------------------------------------------
+// A row is LPR 16-byte chunks.  The LPR chunks of a row are held by LPR ADJACENT LANES OF ONE WAVE, a wave covers
+// kRowsPerWave = 64 / LPR consecutive rows per round (64 % LPR lanes idle: 1 of 64 at A = 12), so
+//   * every global access is a dwordx4 and a wave's load covers kActive * 16 contiguous bytes (coalesced);
+//   * the row reductions (log-prob, entropy) are LPR wave shuffles among neighbours — no LDS tile, no barrier — and every
+//     lane of the row then evaluates the scalar part (ratio, clip, d loss / d logp) itself: nothing to publish;
+//   * a lane's chunks all belong to ONE column group (lane % LPR), so with a std vector its d_std contributions add up
+//     in four registers and the column sums of a wave are a strided shuffle tree — no select chain.
+// One barrier per block (the cross-wave exchange of the five loss sums and the d_std column sums), against four in the
+// flat-chunk layout this replaces (round 2: 0.41 of the HBM roofline with a std vector, bound by its own barriers).
+// kRounds chunks per lane are requested before anything is computed (memory-level parallelism).
+constexpr int loss_rounds(int lpr) { return lpr >= 4 ? 4 : lpr; }
+constexpr int loss_rows_per_block_of(int lpr) { return kWavesPerBlock * (kWave / lpr) * loss_rounds(lpr); }
+
+template <int LPR>
+struct RowGroup {
+    static constexpr int kRowsPerWave = kWave / LPR;
+    static constexpr int kActive = kRowsPerWave * LPR;
+    static constexpr int kRounds = loss_rounds(LPR);
+    static constexpr int kRowsPerBlock = loss_rows_per_block_of(LPR);
+    static constexpr int kTreeStart = kRowsPerWave > 32 ? 32 : kRowsPerWave > 16 ? 16 : kRowsPerWave > 8 ? 8 : 4;
+};
+
+constexpr int kMaxLpr = 8;  // A <= 32
+static int loss_rows_per_block(int64_t A) {
+    return A % 4 == 0 && A / 4 <= kMaxLpr ? loss_rows_per_block_of(int(A / 4)) : kBlock;  // else row-wise: one lane per row
+}
+// the smallest of them (rows per wave and round only shrink as LPR grows past 4): workspace bound for any A
+constexpr int kMinLossRowsPerBlock = loss_rows_per_block_of(kMaxLpr);
+static_assert(kMinLossRowsPerBlock == 128, "the workspace-size functions of the C ABI are built on this value");
+
+// kStdVec: `std` is ONE row [A] shared by every sample (a state-independent std vector, distribution.py:228-247)
+// instead of a [B, A] matrix: it is read once per lane instead of streamed, and d_std leaves the kernel as per-block
+// column sums [A] (the gradient of the vector) instead of a [B, A] matrix that a sum(0) launch would have to reduce —
+// 96 of the 264 bytes per sample disappear.
 // kFull: every optional output is wanted (the training step) — no per-store pointer tests.
-// kWaveRows (round 5): a wave's rows of ALL its rounds are one contiguous run (R * kRowsPerWave <= 64 rows), so the nine
-// per-row scalar streams (advantage, old log-prob, return, value[, old value] in; log-prob, entropy, log-ratio, ratio,
-// d_value out) move as ONE dword access per stream and wave — lane L holds row L of the run, values travel between the
-// row-major lanes and the row groups by wave shuffles — instead of one access per stream and ROUND with a third of the
-// lanes active: 53 -> 20 vector-memory instructions per wave at A = 12 (the kernel moved 1.02x its algorithmic bytes
-// and still sat at 0.61-0.67 of the HBM roofline: it was bound by memory INSTRUCTIONS, not bytes).
+// Scalar streams: a wave's rows of ALL its rounds are one contiguous run (R * kRowsPerWave <= 64 rows), so the nine per-row
+// scalar streams (advantage, old log-prob, return, value[, old value] in; log-prob, entropy, log-ratio, ratio, d_value out)
+// move as ONE dword access per stream and wave — lane L holds row L of the run, values travel between the row-major lanes
+// and the row groups by wave shuffles: 20 vector-memory instructions per wave at A = 12.  (The form with one access per
+// stream and ROUND, 53 of them, was bound by memory INSTRUCTIONS, not bytes: profiles/r05/loss_layout_ab.txt.)
 // kStream (round 5): the [B, A] streams — action, mean, (std,) d_mean, (d_std) — with the non-temporal hint, loads AND stores,
 // chosen by footprint (loss_streaming below).  Beyond the 256 MB Infinity Cache every line these streams leave in the caches
 // is dead weight that evicts somebody's dirty line: 0.60 -> 0.70 of the HBM roofline in the std-vector form, 0.62-0.68 ->
 // 0.71 in the matrix form on one box (profiles/r05/loss_variants_ab.txt).  Both halves are needed: non-temporal loads alone
 // are SLOWER than the default policy (0.59) and non-temporal stores alone neutral — which is what round 4's policy sweep
 // ran into.  The per-row scalar streams (4 B per row each) keep the default policy.
-template <int LPR, bool kStdVec, bool kFull, bool kWaveRows, bool kStream>
+template <int LPR, bool kStdVec, bool kFull, bool kStream>
 __global__ __launch_bounds__(kBlock) void ppo_loss_rowgroup_kernel(
     const float *__restrict__ advantage, const float *__restrict__ old_logp, const float *__restrict__ action,
     const float *__restrict__ mean, const float *__restrict__ std, const float *__restrict__ ret,
@@ -282,58 +229,44 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_rowgroup_kernel(
     float4 x[R], mu[R], sg[kStdVec ? 1 : R];
     float adv[R], olp[R], pre_ret[R], pre_cv[R], pre_ov[R];
     if (kStdVec) sg[0] = sb[sub];
-    constexpr unsigned kRunRows = unsigned(R * G::kRowsPerWave);  // rows of one wave over all its rounds (kWaveRows)
+    constexpr unsigned kRunRows = unsigned(R * G::kRowsPerWave);  // rows of one wave over all its rounds
     const unsigned run_row0 = wave * kRunRows;
-    // kWaveRows: lane L requests the scalars of row L of the wave's run (clamped like every other load)
-    float s_adv = 0.f, s_olp = 0.f, s_ret = 0.f, s_cv = 0.f, s_ov = 0.f;
-    if (kWaveRows) {
-        const unsigned srow = min(run_row0 + lane, rows_here - 1u);
-        s_adv = advb[srow];
-        s_olp = olpb[srow];
-        if (D == 1) {  // uniform
-            s_ret = retb[srow];
-            s_cv = cvb[srow];
-            if (p.value_clip >= 0.0f) s_ov = ovb[srow];
-        }
+    // lane L requests the scalars of row L of the wave's run (clamped like every other load)
+    const unsigned srow = min(run_row0 + lane, rows_here - 1u);
+    const float s_adv = advb[srow], s_olp = olpb[srow];
+    float s_ret = 0.f, s_cv = 0.f, s_ov = 0.f;
+    if (D == 1) {  // uniform
+        s_ret = retb[srow];
+        s_cv = cvb[srow];
+        if (p.value_clip >= 0.0f) s_ov = ovb[srow];
     }
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-        lrow[k] = kWaveRows ? run_row0 + unsigned(k) * G::kRowsPerWave + rloc
-                            : (unsigned(k) * kWavesPerBlock + wave) * G::kRowsPerWave + rloc;
+        lrow[k] = run_row0 + unsigned(k) * G::kRowsPerWave + rloc;
         valid[k] = holder && lrow[k] < rows_here;
         const unsigned crow = min(lrow[k], rows_here - 1u);
         q[k] = crow * LPR + sub;
         if (kStream) {
-            x[k] = loss_nt_load(xb + q[k]);
-            mu[k] = loss_nt_load(mb + q[k]);
-            if (!kStdVec) sg[k] = loss_nt_load(sb + q[k]);
+            x[k] = nt_load16(xb + q[k]);
+            mu[k] = nt_load16(mb + q[k]);
+            if (!kStdVec) sg[k] = nt_load16(sb + q[k]);
         } else {
             x[k] = xb[q[k]];
             mu[k] = mb[q[k]];
             if (!kStdVec) sg[k] = sb[q[k]];
         }
-        pre_ret[k] = pre_cv[k] = pre_ov[k] = 0.f;
-        if (!kWaveRows) {
-            adv[k] = advb[crow];
-            olp[k] = olpb[crow];
-            if (D == 1) {  // uniform
-                pre_ret[k] = retb[crow];
-                pre_cv[k] = cvb[crow];
-                if (p.value_clip >= 0.0f) pre_ov[k] = ovb[crow];
-            }
-        }
     }
-    if (kWaveRows) {  // row-major lanes -> row groups (a clamped row's lane holds the clamped row's values: same semantics)
+    // row-major lanes -> row groups (a clamped row's lane holds the clamped row's values: same semantics)
 #pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const int src = int(unsigned(k) * G::kRowsPerWave + rloc) & (kWave - 1);
-            adv[k] = __shfl(s_adv, src, kWave);
-            olp[k] = __shfl(s_olp, src, kWave);
-            if (D == 1) {
-                pre_ret[k] = __shfl(s_ret, src, kWave);
-                pre_cv[k] = __shfl(s_cv, src, kWave);
-                if (p.value_clip >= 0.0f) pre_ov[k] = __shfl(s_ov, src, kWave);
-            }
+    for (int k = 0; k < R; ++k) {
+        const int src = int(unsigned(k) * G::kRowsPerWave + rloc) & (kWave - 1);
+        adv[k] = __shfl(s_adv, src, kWave);
+        olp[k] = __shfl(s_olp, src, kWave);
+        pre_ret[k] = pre_cv[k] = pre_ov[k] = 0.f;
+        if (D == 1) {
+            pre_ret[k] = __shfl(s_ret, src, kWave);
+            pre_cv[k] = __shfl(s_cv, src, kWave);
+            if (p.value_clip >= 0.0f) pre_ov[k] = __shfl(s_ov, src, kWave);
         }
     }
 
@@ -363,7 +296,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_rowgroup_kernel(
         for (int j = 0; j < LPR; ++j) entropy += __shfl(en, int(row_lane0) + j, kWave);
     };
     if (kStdVec) prepare_std(sg[0]);
-    float o_logp = 0.f, o_entropy = 0.f, o_lr = 0.f, o_ratio = 0.f, o_vgrad = 0.f;  // kWaveRows: row (run_row0 + lane)'s outputs
+    float o_logp = 0.f, o_entropy = 0.f, o_lr = 0.f, o_ratio = 0.f, o_vgrad = 0.f;  // row (run_row0 + lane)'s outputs
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         if (!kStdVec) prepare_std(sg[k]);
@@ -379,7 +312,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_rowgroup_kernel(
         float logp = 0.0f;
 #pragma unroll
         for (int j = 0; j < LPR; ++j) logp += __shfl(lp, int(row_lane0) + j, kWave);
-        // every lane of the row evaluates the scalar part; lane `sub == 0` owns the row's outputs and sums
+        // every lane of the row evaluates the scalar part; lane `sub == 0` owns the row's sums
         const RowScalars r = row_scalars(logp, olp[k], adv[k], p);
         float v_loss = 0.0f, v_grad = 0.0f;
         if (D == 1) value_scalars(pre_cv[k], pre_ret[k], pre_ov[k], p, v_loss, v_grad);
@@ -395,44 +328,34 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_rowgroup_kernel(
         if (kStdVec) ds_acc.x += live * gs[0], ds_acc.y += live * gs[1], ds_acc.z += live * gs[2], ds_acc.w += live * gs[3];
         if (valid[k]) {
             if (kStream) {
-                if (kFull || dmb) loss_nt_store(dmb + (lrow[k] * LPR + sub), make_float4(gm[0], gm[1], gm[2], gm[3]));
-                if (!kStdVec && (kFull || dsb)) loss_nt_store(dsb + (lrow[k] * LPR + sub), make_float4(gs[0], gs[1], gs[2], gs[3]));
+                if (kFull || dmb) nt_store16(dmb + (lrow[k] * LPR + sub), make_float4(gm[0], gm[1], gm[2], gm[3]));
+                if (!kStdVec && (kFull || dsb)) nt_store16(dsb + (lrow[k] * LPR + sub), make_float4(gs[0], gs[1], gs[2], gs[3]));
             } else {
                 if (kFull || dmb) dmb[lrow[k] * LPR + sub] = make_float4(gm[0], gm[1], gm[2], gm[3]);
                 if (!kStdVec && (kFull || dsb)) dsb[lrow[k] * LPR + sub] = make_float4(gs[0], gs[1], gs[2], gs[3]);
             }
-            if (!kWaveRows && sub == 0) {
-                if (kFull || lpo) lpo[lrow[k]] = logp;
-                if (kFull || eno) eno[lrow[k]] = entropy;
-                if (kFull || lro) lro[lrow[k]] = r.lr;
-                if (kFull || rao) rao[lrow[k]] = r.ratio;
-                if (D == 1 && (kFull || dvb)) dvb[lrow[k]] = v_grad;
-            }
         }
-        if (kWaveRows) {  // row groups -> row-major lanes: lane L collects row L of the run from the group that holds it
-            const int src = int((lane % G::kRowsPerWave) * LPR) & (kWave - 1);
-            const bool mine = lane / G::kRowsPerWave == unsigned(k);
-            const float c_logp = __shfl(logp, src, kWave), c_lr = __shfl(r.lr, src, kWave), c_ratio = __shfl(r.ratio, src, kWave);
-            if (mine) o_logp = c_logp, o_lr = c_lr, o_ratio = c_ratio;
-            if (!kStdVec) {
-                const float c_en = __shfl(entropy, src, kWave);
-                if (mine) o_entropy = c_en;
-            }
-            if (D == 1) {
-                const float c_vg = __shfl(v_grad, src, kWave);
-                if (mine) o_vgrad = c_vg;
-            }
+        // row groups -> row-major lanes: lane L collects row L of the run from the group that holds it
+        const int src = int((lane % G::kRowsPerWave) * LPR) & (kWave - 1);
+        const bool mine = lane / G::kRowsPerWave == unsigned(k);
+        const float c_logp = __shfl(logp, src, kWave), c_lr = __shfl(r.lr, src, kWave), c_ratio = __shfl(r.ratio, src, kWave);
+        if (mine) o_logp = c_logp, o_lr = c_lr, o_ratio = c_ratio;
+        if (!kStdVec) {
+            const float c_en = __shfl(entropy, src, kWave);
+            if (mine) o_entropy = c_en;
+        }
+        if (D == 1) {
+            const float c_vg = __shfl(v_grad, src, kWave);
+            if (mine) o_vgrad = c_vg;
         }
     }
-    if (kWaveRows) {
-        const unsigned orow = run_row0 + lane;
-        if (lane < kRunRows && orow < rows_here) {
-            if (kFull || lpo) lpo[orow] = o_logp;
-            if (kFull || eno) eno[orow] = kStdVec ? entropy : o_entropy;  // a std vector: the same entropy for every row
-            if (kFull || lro) lro[orow] = o_lr;
-            if (kFull || rao) rao[orow] = o_ratio;
-            if (D == 1 && (kFull || dvb)) dvb[orow] = o_vgrad;
-        }
+    const unsigned orow = run_row0 + lane;
+    if (lane < kRunRows && orow < rows_here) {
+        if (kFull || lpo) lpo[orow] = o_logp;
+        if (kFull || eno) eno[orow] = kStdVec ? entropy : o_entropy;  // a std vector: the same entropy for every row
+        if (kFull || lro) lro[orow] = o_lr;
+        if (kFull || rao) rao[orow] = o_ratio;
+        if (D == 1 && (kFull || dvb)) dvb[orow] = o_vgrad;
     }
     double acc[kLossSums];
 #pragma unroll
@@ -489,12 +412,13 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_rowwise_kernel(
             logp += -(diff * diff) / (2.0f * (sg * sg)) - ls - log_sqrt_2pi();
             entropy += entropy_const() + ls;
         }
-        float ratio, lr;
-        const float dlp = row_terms(logp, entropy, old_logp[row], advantage[row], p, acc[1], acc[2], acc[3], ratio, lr);
+        const RowScalars r = row_scalars(logp, old_logp[row], advantage[row], p);
+        add_row_sums(r, entropy, acc);
+        const float dlp = r.dlp;
         if (logp_out) logp_out[row] = logp;
         if (entropy_out) entropy_out[row] = entropy;
-        if (lr_out) lr_out[row] = lr;
-        if (ratio_out) ratio_out[row] = ratio;
+        if (lr_out) lr_out[row] = r.lr;
+        if (ratio_out) ratio_out[row] = r.ratio;
         for (int a = 0; a < A; ++a) {
             const int64_t i = row * A + a;
             const float diff = action[i] - mean[i], sg = std[i], var = sg * sg;
@@ -538,12 +462,13 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_categorical_kernel(
             entropy -= expf(lp) * fmaxf(lp, -FLT_MAX);  // -(probs * clamp(logits, min=finfo.min)).sum(-1)
         }
         const float logp = z[taken] - log_norm;
-        float ratio, lr;
-        const float dlp = row_terms(logp, entropy, old_logp[row], advantage[row], p, acc[1], acc[2], acc[3], ratio, lr);
+        const RowScalars r = row_scalars(logp, old_logp[row], advantage[row], p);
+        add_row_sums(r, entropy, acc);
+        const float dlp = r.dlp;
         if (logp_out) logp_out[row] = logp;
         if (entropy_out) entropy_out[row] = entropy;
-        if (lr_out) lr_out[row] = lr;
-        if (ratio_out) ratio_out[row] = ratio;
+        if (lr_out) lr_out[row] = r.lr;
+        if (ratio_out) ratio_out[row] = r.ratio;
         if (d_logits) {
             for (int j = 0; j < A; ++j) {
                 const float lp = z[j] - log_norm, pj = expf(lp);
@@ -613,11 +538,7 @@ __device__ __forceinline__ void finalize_losses(const double *partials, int64_t 
     if (d_std_partials) reduce_std_rows(d_std_partials, P, A, d_std_vector);  // std-vector mode, few blocks
     double sums[kLossSums];
 #pragma unroll
-    for (int k = 0; k < kLossSums; ++k) {
-        double s = 0.0;
-        for (int64_t i = threadIdx.x; i < P; i += kBlock) s += partials[i * kLossSums + k];
-        sums[k] = block_sum(s, scratch);
-    }
+    for (int k = 0; k < kLossSums; ++k) sums[k] = sum_partial_rows<kLossSums>(partials, P, k, scratch);
     if (threadIdx.x == 0) {
         // (D == 0: the value term is evaluated by cusrl_value_loss_fwd_bwd on the critic's stream — it contributes nothing here)
         losses_out[0] = D > 0 ? float(sums[0] / double(B * D)) * p.w_val : 0.0f;   // mean * weight   value.py:137
@@ -654,7 +575,6 @@ __global__ __launch_bounds__(kBlock) void value_loss_kernel(const float *__restr
                                                             const float *__restrict__ old_value, int64_t n, LossParams p,
                                                             float *__restrict__ d_value, double *__restrict__ partials,
                                                             int accumulate) {
-    __shared__ double scratch[kWavesPerBlock][kValueSums];
     const int64_t base = int64_t(blockIdx.x) * kValueElemsPerBlock + threadIdx.x;
     float cv[4], R[4], ov[4];
     bool live[4];
@@ -676,17 +596,8 @@ __global__ __launch_bounds__(kBlock) void value_loss_kernel(const float *__restr
             if (d_value) d_value[base + int64_t(k) * kBlock] = grad;
         }
     }
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const double l = wave_sum_to_last_lane(double(loss_sum)), v = wave_sum_to_last_lane(double(value_sum));
-    if (lane == kWave - 1) scratch[wave][0] = l, scratch[wave][1] = v;
-    __syncthreads();
-    if (threadIdx.x < kValueSums) {
-        double total = 0.0;
-#pragma unroll
-        for (int w = 0; w < kWavesPerBlock; ++w) total += scratch[w][threadIdx.x];
-        double *slot = partials + int64_t(blockIdx.x) * kValueSums + threadIdx.x;
-        *slot = accumulate ? *slot + total : total;
-    }
+    const double acc[kValueSums] = {double(loss_sum), double(value_sum)};
+    write_block_partials(acc, partials, accumulate != 0);
 }
 
 // losses_out[0] = weighted value loss, losses_out[1] = mean of curr_value.sum(-1)
@@ -694,9 +605,7 @@ __global__ __launch_bounds__(kBlock) void value_loss_finalize_kernel(const doubl
                                                                      int64_t D, float w_val, float *__restrict__ losses_out) {
     __shared__ double scratch[kWavesPerBlock];
     for (int k = 0; k < kValueSums; ++k) {
-        double s = 0.0;
-        for (int64_t i = threadIdx.x; i < P; i += kBlock) s += partials[i * kValueSums + k];
-        const double total = block_sum(s, scratch);
+        const double total = sum_partial_rows<kValueSums>(partials, P, k, scratch);
         if (threadIdx.x == 0) losses_out[k] = k == 0 ? float(total / double(B * D)) * w_val : float(total / double(B));
     }
 }
@@ -806,11 +715,10 @@ extern "C" int cusrl_ppo_loss_categorical_fwd_bwd(const float *advantage, const 
     return launch_finalize(partials, blocks, B, A, D, p, losses_out, nullptr, nullptr, s);
 }
 
-// The instantiated forms (round 6: what measured slower or neutral in rounds 4-5 is no longer compiled — the per-round scalar
-// streams, kWaveRows = false, profiles/r05/loss_layout_ab.txt): the scalar streams of a wave's rows always move as one access
-// per stream; the training step's launch (kFull) exists with and without the non-temporal [B, A] streams.
+// The instantiated forms: LPR 1..8 x {std vector, std matrix} x {every output wanted (the training step's launch, kFull) with
+// and without the non-temporal [B, A] streams, some outputs wanted}.
 #define CUSRL_LAUNCH_ROWGROUP_AS(LPR, VEC, FULL, STREAM)                                                                \
-    hipLaunchKernelGGL((ppo_loss_rowgroup_kernel<LPR, VEC, FULL, true, STREAM>), dim3(uint32_t(blocks)), dim3(kBlock), 0, s, \
+    hipLaunchKernelGGL((ppo_loss_rowgroup_kernel<LPR, VEC, FULL, STREAM>), dim3(uint32_t(blocks)), dim3(kBlock), 0, s, \
                        advantage, old_logp, action, mean, std, ret, curr_value, old_value, B, int(D), p, logp_out,          \
                        entropy_out, logp_ratio_out, ratio_out, d_mean, d_std, d_value, partials, d_std_partials, int(defer))
 #define CUSRL_LAUNCH_ROWGROUP_FULL(LPR, VEC)                                                                            \
@@ -849,7 +757,7 @@ extern "C" int cusrl_ppo_loss_fwd_bwd(const float *advantage, const float *old_l
     if (D == 0) value_clip = -1.0, d_value = nullptr;
     const LossParams p = loss_params(B, D, clip, value_clip, w_sur, w_val, w_ent);
     hipStream_t s = as_stream(stream);
-    const bool chunked = A % 4 == 0 && A / 4 <= 8 && aligned(action, 16) && aligned(mean, 16) && aligned(std, 16) &&
+    const bool chunked = A % 4 == 0 && A / 4 <= kMaxLpr && aligned(action, 16) && aligned(mean, 16) && aligned(std, 16) &&
                          (!d_mean || aligned(d_mean, 16)) && (!d_std || std_vector || aligned(d_std, 16)) &&
                          (!d_std_partials || aligned(d_std_partials, 16));
     if (std_vector && !chunked) return CUSRL_E_UNSUPPORTED;  // the row-vector form exists for the 16-byte-chunk layout

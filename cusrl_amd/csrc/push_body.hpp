@@ -39,12 +39,12 @@ __device__ __forceinline__ int find_leaf(const Table &tab, int blk) {
     return f;
 }
 
-typedef uint32_t native_u4 __attribute__((ext_vector_type(4)));
+// 16 opaque bytes: common.hpp's non-temporal pair moves them as a float4, the bits pass through untouched
 template <bool NT>
 __device__ __forceinline__ uint4 stream_load16(const char *p) {
     if constexpr (NT) {
-        const native_u4 v = __builtin_nontemporal_load(reinterpret_cast<const native_u4 *>(p));
-        return make_uint4(v.x, v.y, v.z, v.w);
+        const float4 v = nt_load16(reinterpret_cast<const float4 *>(p));
+        return make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w));
     } else {
         return *reinterpret_cast<const uint4 *>(p);
     }
@@ -52,8 +52,8 @@ __device__ __forceinline__ uint4 stream_load16(const char *p) {
 template <bool NT>
 __device__ __forceinline__ void stream_store16(char *p, const uint4 &v) {
     if constexpr (NT) {
-        const native_u4 n = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(n, reinterpret_cast<native_u4 *>(p));
+        nt_store16(reinterpret_cast<float4 *>(p),
+                   make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)));
     } else {
         *reinterpret_cast<uint4 *>(p) = v;
     }

@@ -515,7 +515,10 @@ def test_gae_bit_exact_vs_reference_goldens(ops, golden):
         np.testing.assert_allclose(host(mean2), host(mean), rtol=1e-6, atol=1e-7)
 
 
-@pytest.mark.parametrize("T,N,D", [(24, 4096, 1), (24, 4098, 1), (24, 1000, 2), (3, 5, 4), (1, 64, 1), (40, 256, 1)])
+# (5, 50, 3) and (40, 100, 3): D > 1 with a block size that is no multiple of D, so a block's first channel is not 0 — on the
+# one-wave-block path (T <= 32) and on the 256-thread path
+@pytest.mark.parametrize("T,N,D", [(24, 4096, 1), (24, 4098, 1), (24, 1000, 2), (3, 5, 4), (1, 64, 1), (40, 256, 1), (5, 50, 3),
+                                   (40, 100, 3)])
 @pytest.mark.parametrize("lamda_value", [None, 0.9])
 def test_gae_bit_exact_vs_oracle(ops, T, N, D, lamda_value):
     rng = np.random.default_rng(T + N + D)
@@ -584,6 +587,51 @@ def test_push_streaming_policy_moves_the_same_bytes(ops, option, policy):
             oracle.buffer_push(v, expect[k], cursor)
     for k in steps:
         assert np.array_equal(host(storage[k]), expect[k]), k
+
+
+@pytest.mark.parametrize("rows,D", [(1000, 7), (33, 256)])
+def test_col_stats_vs_float64(ops, rows, D):
+    """The per-channel block partials against float64 numpy: (1000, 7) is two blocks whose first element is not on channel 0
+    (4096 % 7 != 0), (33, 256) has D at the supported limit (one thread per channel, nothing to add up)."""
+    rng = np.random.default_rng(rows + D)
+    x = (rng.standard_normal((rows, D)) * 3 + 0.5).astype(np.float32)
+    partials = ops.col_stats(dev(x))
+    assert partials.shape == (2 if rows == 1000 else 3, D, 2)
+    x64 = x.astype(np.float64)
+    sums = host(partials).sum(0)
+    # fp64 sums of values (and squares) that are exact in fp64: n * 2^-53 of the absolute sum, 1e-12 with room to spare
+    np.testing.assert_allclose(sums[:, 0], x64.sum(0), rtol=0, atol=1e-12 * np.abs(x64).sum(0).max())
+    np.testing.assert_allclose(sums[:, 1], (x64 * x64).sum(0), rtol=1e-12)
+    var, mean = ops.adv_stats_finalize(partials, rows)
+    np.testing.assert_allclose(host(mean), x64.mean(0), rtol=1e-5, atol=1e-6)  # 1e-5 rel fp32
+    np.testing.assert_allclose(host(var), x64.var(0, ddof=1), rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_normalize_entry_points_agree_bit_for_bit(ops, offset):
+    """``normalize_``, ``normalize_from_partials_`` and ``normalize_from_gathered_`` (one rank: the merge is the identity) are one
+    normalisation behind three sources of the statistics: the same bits from all three, and ``oracle.normalize``'s given the
+    same statistics.  1001 rows of D = 1: 16-byte aligned storage takes the float4 body + tail, storage that starts 4 bytes
+    past a 16-byte boundary the scalar path."""
+    rows = 1001
+    data = torch.randn(rows, 1, generator=torch.Generator().manual_seed(rows)) * 3 + 0.5
+
+    def fresh():
+        x = torch.empty(rows + 4, device=DEV)[offset : offset + rows].view(rows, 1)
+        assert x.data_ptr() % 16 == 4 * offset and x.is_contiguous()
+        return x.copy_(data)
+
+    x = fresh()
+    partials = ops.col_stats(x)
+    var, mean = ops.adv_stats_finalize(partials, rows)
+    plain = ops.normalize_(fresh(), mean, var, 1e-8)
+    assert np.array_equal(host(plain), oracle.normalize(host(x), host(mean), host(var)))
+    single = fresh()
+    single_var, single_mean = ops.normalize_from_partials_(single, partials, rows, 1e-8)
+    assert torch.equal(single, plain) and torch.equal(single_mean, mean) and torch.equal(single_var, var)
+    ranked = fresh()
+    ranked_var, ranked_mean = ops.normalize_from_gathered_(ranked, ops.packed_mean_var(mean, var)[None], 1e-8)
+    assert torch.equal(ranked, plain) and torch.equal(ranked_mean, mean) and torch.equal(ranked_var, var)
 
 
 def test_gae_propagates_nonfinite_like_reference(ops):
@@ -1495,18 +1543,36 @@ def test_options_are_validated_and_readable(ops):
         assert _native.get_option(key) == 0
 
 
-@pytest.mark.parametrize("form", ["std_vector", "std_matrix", "categorical"])
+@pytest.mark.parametrize("form", ["std_vector", "std_matrix", "categorical", "value_only"])
 def test_ppo_loss_deferred_finalize_accumulates_block_rows(ops, form):
     """CUSRL_LOSS_DEFER (what a captured minibatch step runs): one launch, no finalize.  Two launches add their block sums
     into the caller's rows — drained, they are the two launches' losses and metric means; the per-sample outputs and
     gradients are bit-identical to the two-launch form; a std vector's d_std arrives as the blocks' column sums, which
-    ``assemble_gradients`` reduces to the same vector."""
+    ``assemble_gradients`` reduces to the same vector.  The value term's own launch: two launches leave exactly twice one
+    launch's block rows (doubling is exact), d_value is the non-deferred call's."""
     rng = np.random.default_rng(7)
     B, A, D = 24576, 12, 1
     f = lambda *s: rng.standard_normal(s).astype(np.float32)  # noqa: E731
     adv, ret = f(B, 1), f(B, D)
     curr_value = ret + 0.3 * f(B, D)
     kw = dict(clip=0.2, value_clip=None, w_sur=1.0, w_val=0.5, w_ent=0.01)
+    if form == "value_only":
+        old_value = ret + 0.3 * f(B, D)
+        for vclip in (None, 0.2):
+            value_args = (dev(ret), dev(curr_value), dev(old_value))
+            plain = ops.value_loss_fwd_bwd(*value_args, value_clip=vclip, w_val=0.5)
+            rows = ops.DeferredLoss(B, A, D, torch.device(DEV), categorical=False)
+            assert rows.value_rows.shape == (24, 2)  # 1024 elements per block
+            first = ops.value_loss_fwd_bwd(*value_args, value_clip=vclip, w_val=0.5, deferred=rows)
+            once = rows.value_rows.clone()
+            second = ops.value_loss_fwd_bwd(*value_args, value_clip=vclip, w_val=0.5, deferred=rows)
+            assert "losses" not in first and float(once.abs().sum()) > 0.0
+            assert torch.equal(rows.value_rows, 2 * once)
+            assert torch.equal(first["d_value"], plain["d_value"]) and torch.equal(second["d_value"], plain["d_value"])
+            sums = host(once).sum(0)  # the finalize launch's inputs, added up in another order: fp32 rounding of `losses`
+            np.testing.assert_allclose(sums[0] / (B * D) * 0.5, host(plain["losses"])[0], rtol=2e-7, atol=1e-12)
+            np.testing.assert_allclose(sums[1] / B, host(plain["losses"])[1], rtol=2e-7, atol=1e-9)
+        return
     if form == "categorical":
         logits = 2.0 * f(B, A)
         action = np.eye(A, dtype=np.float32)[rng.integers(0, A, B)]
