@@ -10,8 +10,12 @@
 //   cusrl_column_mse_fwd_bwd    weight * nn.MSELoss(prediction, leaf[..., columns]) of the privileged-information hooks
 //                               (estimation.py, representation.py, distillation.py): the same, the target read in place
 //   cusrl_normal_nll_fwd_bwd    nn.NormalNllLoss (cusrl/nn/layer/loss.py:62-141): the loss and both gradients in one pass
+//   cusrl_nan_to_num2           ObservationNanToNum.pre_act / post_step  cusrl/hook/mdp/observation.py:42-56: nan_to_num_ of
+//                               the observation AND the state in one launch, storing only what it replaced
 // All of these are a few hundred KB per launch at 4096 envs: latency-bound chains of tiny kernels in the reference's form,
 // so what counts is the NUMBER of dependent launches inside the captured step (>= 1.5 us each + their own latency).
+#include <string.h>
+
 #include "common.hpp"
 
 namespace cusrl {
@@ -28,6 +32,77 @@ __global__ __launch_bounds__(kBlock) void reward_shaping_kernel(float *__restric
     if (has_lower) r = (r != r) ? r : (r < lower ? lower : r);
     if (has_upper) r = (r != r) ? r : (r > upper ? upper : r);
     reward[i] = r;
+}
+
+// --------------------------------------------------------------------------------------------- observation sanitiser
+// tensor.nan_to_num_(nan, posinf, neginf) of up to TWO fp32 arrays in one launch, classified on the bit pattern: exponent all
+// ones and a mantissa -> `nan` (any sign, any payload), +Inf -> `posinf`, -Inf -> `neginf`; every other pattern (-0.0,
+// denormals, +-FLT_MAX) is never rewritten, so no floating-point mode can touch it.  STORE ON CHANGE: a lane writes its 16
+// bytes (or its scalar) back only when a value in it was replaced by a different pattern — on clean input, the common case, the
+// launch is a pure read stream of 4 B per element.  No element is touched by two threads: nothing to order.
+// Per array: a scalar head up to the first 16-byte boundary (<= 3 elements; observation tensors can be offset views, only
+// 4-byte alignment is guaranteed), a 16-byte body, a scalar tail (<= 3); the <= 6 scalars go to the first threads of the grid.
+// The body is a grid-stride loop over a capped grid with TWO independent 16-byte loads per lane in flight before the first
+// conditional store (the compiler cannot hoist a load of the same array over such a store by itself).
+constexpr int kSanitizeMaxBlocks = 2048;                      // 8 blocks per CU
+constexpr int64_t kSanitizeSpan = int64_t(kBlock) * 2 * 4;    // elements of one array one block covers per pass
+
+__device__ __forceinline__ bool sanitize_word(uint32_t &bits, uint32_t nan, uint32_t posinf, uint32_t neginf) {
+    if ((bits & 0x7f800000u) != 0x7f800000u) return false;  // finite
+    const uint32_t to = (bits & 0x007fffffu) ? nan : ((bits >> 31) ? neginf : posinf);
+    const bool changed = to != bits;  // (posinf = +Inf leaves an infinity alone: nothing to store)
+    bits = to;
+    return changed;
+}
+
+__device__ __forceinline__ bool sanitize_quad(uint4 &v, uint32_t nan, uint32_t posinf, uint32_t neginf) {
+    bool changed = sanitize_word(v.x, nan, posinf, neginf);
+    changed |= sanitize_word(v.y, nan, posinf, neginf);
+    changed |= sanitize_word(v.z, nan, posinf, neginf);
+    changed |= sanitize_word(v.w, nan, posinf, neginf);
+    return changed;
+}
+
+template <bool NT>
+__device__ __forceinline__ uint4 sanitize_load(const uint4 *p) {
+    if constexpr (NT) {
+        const float4 v = nt_load16(reinterpret_cast<const float4 *>(p));  // a move of 16 bytes: the bits pass untouched
+        return make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w));
+    } else {
+        return *p;
+    }
+}
+
+template <bool NT>
+__device__ __forceinline__ void sanitize_array(uint32_t *__restrict__ words, int64_t n, int64_t tid, int64_t stride, uint32_t nan,
+                                               uint32_t posinf, uint32_t neginf) {
+    int64_t head = int64_t((16 - (reinterpret_cast<uintptr_t>(words) & 15)) & 15) / 4;
+    if (head > n) head = n;
+    const int64_t quads = (n - head) / 4, tail = head + quads * 4;
+    if (tid < head + (n - tail)) {  // the <= 6 scalars in front of and behind the body
+        const int64_t i = tid < head ? tid : tail + (tid - head);
+        uint32_t w = words[i];
+        if (sanitize_word(w, nan, posinf, neginf)) words[i] = w;
+    }
+    uint4 *__restrict__ body = reinterpret_cast<uint4 *>(words + head);
+    for (int64_t q0 = tid; q0 < quads; q0 += 2 * stride) {
+        const int64_t q1 = q0 + stride;
+        const bool second = q1 < quads;
+        uint4 v0 = sanitize_load<NT>(body + q0), v1 = make_uint4(0u, 0u, 0u, 0u);
+        if (second) v1 = sanitize_load<NT>(body + q1);
+        if (sanitize_quad(v0, nan, posinf, neginf)) body[q0] = v0;
+        if (second && sanitize_quad(v1, nan, posinf, neginf)) body[q1] = v1;
+    }
+}
+
+// NT: non-temporal loads (chosen by the launch's footprint, cusrl_nan_to_num2).  The rare stores are plain: whoever reads the
+// tensor next (the actor's forward, the buffer append) wants them in L2.
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void nan_to_num2_kernel(uint32_t *__restrict__ a, int64_t na, uint32_t *__restrict__ b,
+                                                             int64_t nb, uint32_t nan, uint32_t posinf, uint32_t neginf) {
+    const int64_t tid = int64_t(blockIdx.x) * kBlock + threadIdx.x, stride = int64_t(gridDim.x) * kBlock;
+    if (na > 0) sanitize_array<NT>(a, na, tid, stride, nan, posinf, neginf);
+    if (nb > 0) sanitize_array<NT>(b, nb, tid, stride, nan, posinf, neginf);
 }
 
 // --------------------------------------------------------------------------------------------- AMP transition preparation
@@ -531,6 +606,35 @@ extern "C" int cusrl_reward_shaping(float *reward, float scale, float shift, flo
     if (!reward) return CUSRL_E_INVALID;
     hipLaunchKernelGGL(reward_shaping_kernel, dim3(uint32_t(ceil_div(n, kBlock))), dim3(kBlock), 0, as_stream(stream),
                        reward, scale, shift, lower, upper, has_lower, has_upper, n);
+    return launch_status();
+}
+
+static uint32_t float_bits(float value) {
+    uint32_t bits;
+    memcpy(&bits, &value, sizeof bits);
+    return bits;
+}
+
+extern "C" int cusrl_nan_to_num2(float *a, int64_t na, float *b, int64_t nb, float nan, float posinf, float neginf,
+                                 void *stream) {
+    if (na < 0 || nb < 0) return CUSRL_E_INVALID;
+    if ((na > 0 && !a) || (nb > 0 && !b)) return CUSRL_E_INVALID;
+    if (na + nb == 0) return 0;
+    if ((na > 0 && !aligned(a, 4)) || (nb > 0 && !aligned(b, 4))) return CUSRL_E_INVALID;
+    // the longer array decides the grid (every thread walks both); + 6: the head / tail scalars of an array too short for a body
+    const int64_t longest = na > nb ? na : nb;
+    int64_t blocks = ceil_div(longest + 6, kSanitizeSpan);
+    if (blocks > kSanitizeMaxBlocks) blocks = kSanitizeMaxBlocks;
+    // cache policy by footprint, like the push (push_body.hpp): a clean pass only READS its 4 B per element; once that does not
+    // fit the 256 MB Infinity Cache nobody finds the lines again, so they stream past the caches
+    const bool streaming = 4 * (na + nb) >= (int64_t(256) << 20);
+    uint32_t *wa = reinterpret_cast<uint32_t *>(a), *wb = reinterpret_cast<uint32_t *>(nb > 0 ? b : nullptr);
+    if (streaming)
+        hipLaunchKernelGGL(nan_to_num2_kernel<true>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), wa, na, wb, nb,
+                           float_bits(nan), float_bits(posinf), float_bits(neginf));
+    else
+        hipLaunchKernelGGL(nan_to_num2_kernel<false>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), wa, na, wb, nb,
+                           float_bits(nan), float_bits(posinf), float_bits(neginf));
     return launch_status();
 }
 

@@ -1,4 +1,11 @@
-from cusrl_amd.hook.mdp.observation import ObservationNormalization
+from cusrl_amd.hook.mdp.environment_spec import DynamicEnvironmentSpecOverride, EnvironmentSpecOverride
+from cusrl_amd.hook.mdp.observation import ObservationNanToNum, ObservationNormalization
 from cusrl_amd.hook.mdp.reward import RewardShaping
 
-__all__ = ["ObservationNormalization", "RewardShaping"]
+__all__ = [
+    "DynamicEnvironmentSpecOverride",
+    "EnvironmentSpecOverride",
+    "ObservationNanToNum",
+    "ObservationNormalization",
+    "RewardShaping",
+]

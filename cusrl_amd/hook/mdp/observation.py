@@ -1,4 +1,9 @@
-"""Online observation / state normalisation (counterpart of cusrl/hook/mdp/observation.py:59-255).
+"""Observation hooks (counterparts of cusrl/hook/mdp/observation.py): ``ObservationNanToNum`` (17-56) and the online
+observation / state normalisation ``ObservationNormalization`` (59-255).
+
+``ObservationNanToNum`` replaces NaN / +Inf / -Inf in the incoming tensors in place — ``observation`` and ``state`` in
+``pre_act``, ``next_observation`` and ``next_state`` in ``post_step`` — as ONE HIP launch per hook call
+(``cusrl_nan_to_num2`` takes both tensors), which reads every element and writes only the 16-byte lanes it changed.
 
 ``pre_act`` and ``post_step`` update running statistics with the incoming (next) observation and replace it by its
 normalised, clamped value, keeping the raw tensors under ``original_*`` (they become extra buffer leaves and ride
@@ -22,7 +27,7 @@ from cusrl_amd.nn.rms import RunningMeanStd, mean_var_count
 from cusrl_amd.template.hook import Hook
 from cusrl_amd.utils.misc import host_form
 
-__all__ = ["ObservationNormalization"]
+__all__ = ["ObservationNanToNum", "ObservationNormalization"]
 
 
 def _symmetric(stats, mirror):
@@ -42,6 +47,58 @@ def _symmetric(stats, mirror):
     var = (var + mirrored_var) / 2 + (mean - mirrored_mean) ** 2 / 4
     mean = (mean + mirrored_mean) / 2
     return mean, var, count
+
+
+class ObservationNanToNum(Hook):
+    """``tensor.nan_to_num_(nan=, posinf=, neginf=)`` on whatever of the four fields is present (missing or None: skipped)."""
+
+    # nothing random, no Python state per step: an env step with this hook may be replayed from a hipGraph.  Its post_step
+    # WRITES the transition on the device, so `post_step_device_free` stays False (the default of an overriding hook): the
+    # captured step keeps the step epilogue and the append as separate launches around it.
+    rollout_capture_safe = True
+
+    def __init__(self, nan: float = 0.0, posinf: float = 0.0, neginf: float = 0.0):
+        super().__init__()
+        self.nan = nan
+        self.posinf = posinf
+        self.neginf = neginf
+
+    def nan_to_num_(self, tensor: Tensor | None):
+        self._sanitize(tensor, None)
+
+    def pre_act(self, transition):
+        self._sanitize(transition.get("observation"), transition.get("state"))
+
+    def post_step(self, transition):
+        self._sanitize(transition.get("next_observation"), transition.get("next_state"))
+
+    def _sanitize(self, first: Tensor | None, second: Tensor | None):
+        tensors = [t for t in (first, second) if t is not None]
+        if not tensors:
+            return
+        if not all(isinstance(t, Tensor) and t.is_cuda for t in tensors):
+            host_form("ObservationNanToNum")  # test processes without a GPU only
+            for t in tensors:
+                t.nan_to_num_(nan=self.nan, posinf=self.posinf, neginf=self.neginf)
+            return
+        direct, staged = [], []
+        for t in tensors:
+            if t.dtype == torch.float32 and t.is_contiguous():
+                direct.append(t)
+            elif t.dtype in (torch.float32, torch.float16, torch.bfloat16):
+                # a layout / width the launch does not take goes through a contiguous fp32 copy (exact: every fp16 / bf16
+                # value, NaN payloads' class and the infinities included, is an fp32 value) and back
+                staged.append((t, t.float().contiguous()))
+            else:
+                # float64, integers, bool: the ONE place a torch element-wise op is acceptable — an fp32 copy would round a
+                # float64 observation, and on integers / bool the operation changes nothing
+                t.nan_to_num_(nan=self.nan, posinf=self.posinf, neginf=self.neginf)
+        work = direct + [copy for _, copy in staged]
+        for i in range(0, len(work), 2):  # both fields of a call in one launch
+            ops.nan_to_num_(work[i], work[i + 1] if i + 1 < len(work) else None, nan=self.nan, posinf=self.posinf,
+                            neginf=self.neginf)
+        for t, copy in staged:
+            t.copy_(copy)
 
 
 class ObservationNormalization(Hook):

@@ -158,6 +158,25 @@ def reward_shaping_(reward: torch.Tensor, scale: float, shift: float, lower: flo
     return reward
 
 
+def nan_to_num_(a: torch.Tensor, b: torch.Tensor | None = None, *, nan: float = 0.0, posinf: float = 0.0,
+                neginf: float = 0.0) -> torch.Tensor:
+    """``a.nan_to_num_(nan, posinf, neginf)`` — and the same of ``b`` when given — in place, ONE launch for both
+    (observation.py:42-56: the observation and the state of one hook call).  Finite values keep their bit patterns; only the
+    16-byte lanes that held a NaN or an infinity are written back.  Returns ``a``."""
+    for name, tensor in (("a", a), ("b", b)):
+        if tensor is None:
+            continue
+        require_device(tensor, name)
+        if tensor.dtype != torch.float32 or not tensor.is_contiguous():
+            raise TypeError(f"nan_to_num_: '{name}' must be a contiguous float32 tensor")
+    _checked.cusrl_nan_to_num2(a.data_ptr(), a.numel(), _ptr(b), 0 if b is None else b.numel(), float(nan), float(posinf),
+            float(neginf), _stream())
+    _modified_in_place(a)
+    if b is not None:
+        _modified_in_place(b)
+    return a
+
+
 def mse_loss_fwd_bwd(prediction: torch.Tensor, target: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """``(mean((prediction - target)^2), d loss / d prediction)`` from one pass (+ a one-block finalize)."""
     prediction, target = _f32(prediction, "prediction"), _f32(target, "target")

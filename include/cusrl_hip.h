@@ -685,6 +685,15 @@ int cusrl_accumulate_scalars(const float *const *values, int n, float *accumulat
 int cusrl_reward_shaping(float *reward, float scale, float shift, float lower, float upper, int has_lower, int has_upper,
                          int64_t n, void *stream);
 
+/* ---- ObservationNanToNum.pre_act / post_step — cusrl/hook/mdp/observation.py:42-56 ----
+ * tensor.nan_to_num_(nan, posinf, neginf) in place on up to TWO contiguous fp32 arrays (the observation and the state of one
+ * hook call) in ONE launch; b == NULL or nb == 0: only a.  Classified on the bit pattern: every NaN (any sign, any payload)
+ * becomes `nan`, +Inf `posinf`, -Inf `neginf`; every finite value keeps its bits (-0.0, denormals, +-FLT_MAX).  Only 4-byte
+ * alignment is required of a and b (offset views): scalar head up to a 16-byte boundary, 16-byte body, scalar tail, per array.
+ * A lane stores only where it replaced something: clean input is read, never written.  Both pointers travel by value: no
+ * device-side table, no staging copy, no memset — a plain kernel node under capture.  na + nb == 0: returns 0, no launch. */
+int cusrl_nan_to_num2(float *a, int64_t na, float *b, int64_t nb, float nan, float posinf, float neginf, void *stream);
+
 /* ---- nn.MSELoss(prediction, target) forward AND backward — RandomNetworkDistillation.objective, rnd.py:78-81 ----
  * loss_out[0] = mean((prediction - target)^2) over n elements (fp64 block partials, fixed order),
  * d_prediction = 2 (prediction - target) / n.  partials: double[cusrl_mse_loss_num_partials(n)]. */

@@ -226,6 +226,15 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
     logits3, race3 = f(N, 3), torch.rand(N, 3, device=DEV) + 0.1
     rows.measure(f"categorical sample + logp [B,3] (B={N})", lambda: ops.categorical_sample_logp(logits3, race3), N * (3 * 12 + 4))
 
+    # ---- observation sanitiser (ObservationNanToNum): one [N, obs] observation.  Clean input is read and never written (4 B per
+    # element, store on change); torch's in-place op reads and rewrites it (8 B).  All-NaN input is written back whole (8 B): it
+    # has to be refilled before every launch, so the refill is timed with it and alone — subtract.
+    sane, dirty = f(N, obs), torch.empty(N, obs, device=DEV)
+    rows.measure(f"nan_to_num clean [N,{obs}]", lambda: ops.nan_to_num_(sane), N * obs * 4)
+    rows.measure(f"torch nan_to_num_ clean [N,{obs}]", lambda: sane.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0), N * obs * 8)
+    rows.measure(f"nan_to_num all-NaN + refill [N,{obs}]", lambda: ops.nan_to_num_(dirty.fill_(float("nan"))), N * obs * 12)
+    rows.measure(f"refill alone (fill_) [N,{obs}]", lambda: dirty.fill_(float("nan")), N * obs * 4)
+
     # ---- reference points: a plain device copy of the same bytes (what the memory system gives a streaming kernel)
     big = torch.empty(max(S * 21 // 8, 1024), dtype=torch.float32, device=DEV)
     dst = torch.empty_like(big)
