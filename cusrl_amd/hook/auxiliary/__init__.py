@@ -3,6 +3,7 @@ from cusrl_amd.hook.auxiliary.distillation import PolicyDistillationLoss
 from cusrl_amd.hook.auxiliary.estimation import StateEstimation
 from cusrl_amd.hook.auxiliary.representation import NextStatePrediction, ReturnPrediction, StatePrediction
 from cusrl_amd.hook.auxiliary.rnd import RandomNetworkDistillation
+from cusrl_amd.hook.auxiliary.smoothness import ActionSmoothnessLoss
 from cusrl_amd.hook.auxiliary.symmetry import (
     MirrorDef,
     MirrorSymmetryLoss,
@@ -11,6 +12,7 @@ from cusrl_amd.hook.auxiliary.symmetry import (
 )
 
 __all__ = [
+    "ActionSmoothnessLoss",
     "AdversarialMotionPrior",
     "MirrorDef",
     "MirrorSymmetryLoss",

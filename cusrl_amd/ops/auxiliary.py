@@ -322,6 +322,42 @@ def normal_nll_fwd_bwd(mean: torch.Tensor, dist: torch.Tensor | None, target: to
     return loss, d_mean, d_dist
 
 
+def action_smoothness_fwd_bwd(mean: torch.Tensor, done: torch.Tensor, w1: torch.Tensor | None,
+                              w2: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``ActionSmoothnessLoss`` (cusrl/hook/auxiliary/smoothness.py:59-102) of ``mean [T, B, A]`` cut at ``done [T, B, 1]``, from
+    ONE C-ABI call: ``(losses fp32[2], counts int64[2], d_mean)``.  ``w1`` / ``w2``: fp32 device ``[A]`` weight vectors of the
+    first- / second-order term, None: that term is not evaluated (its loss slot is 0).  ``d_mean [planes, T, B, A]`` holds one
+    gradient plane per given weight, the first order's first — the terms' gradients stay apart.  ``counts``: the numbers of valid
+    pairs and triples, left on the device.  A non-contiguous ``mean`` is staged contiguously."""
+    mean, done = _f32(mean, "mean"), _flag(done, "done")
+    if mean.dim() != 3:
+        raise ValueError(f"action_smoothness_fwd_bwd: mean must be [T, B, A], got {tuple(mean.shape)}")
+    T, B, A = mean.shape
+    if T < 3 or B == 0 or A == 0:
+        raise ValueError(f"action_smoothness_fwd_bwd: mean {tuple(mean.shape)} needs at least 3 time steps and no empty dimension")
+    if done.numel() != T * B or tuple(done.shape[:2]) != (T, B):
+        raise ValueError(f"action_smoothness_fwd_bwd: done {tuple(done.shape)} is not [T, B, 1] of mean {tuple(mean.shape)}")
+    if w1 is None and w2 is None:
+        raise ValueError("action_smoothness_fwd_bwd: neither term has a weight")
+    for name, weight in (("w1", w1), ("w2", w2)):
+        if weight is None:
+            continue
+        require_device(weight, name)
+        if weight.dtype != torch.float32 or not weight.is_contiguous() or tuple(weight.shape) != (A,):
+            raise TypeError(f"action_smoothness_fwd_bwd: '{name}' must be a contiguous float32 [{A}] device vector")
+    words = int(_native.lib().cusrl_action_smoothness_workspace(T, B, A))
+    if words == 0:
+        raise ValueError(f"action_smoothness_fwd_bwd: mean {tuple(mean.shape)} is beyond a 32-bit element index")
+    dev = mean.device
+    losses = torch.empty(2, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    d_mean = torch.empty(((w1 is not None) + (w2 is not None), T, B, A), dtype=torch.float32, device=dev)
+    workspace = torch.empty(words, dtype=torch.float64, device=dev)
+    _checked.cusrl_action_smoothness_fwd_bwd(mean.data_ptr(), done.data_ptr(), _ptr(w1), _ptr(w2), T, B, A, losses.data_ptr(),
+            counts.data_ptr(), d_mean.data_ptr(), workspace.data_ptr(), _stream())
+    return losses, counts, d_mean
+
+
 def sumsq_fwd_bwd(x: torch.Tensor, loss_scale: float, grad_scale: float) -> tuple[torch.Tensor, torch.Tensor]:
     """``(loss_scale * sum(x^2), grad_scale * x)`` from one pass (AMP's gradient penalty and what it sends back)."""
     x = _f32(x, "x")

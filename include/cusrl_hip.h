@@ -743,6 +743,27 @@ int cusrl_normal_nll_fwd_bwd(const float *mean, int64_t mean_pitch, const float 
                              float *loss_out, float *d_mean, float *d_dist, int64_t grad_pitch, double *partials, void *stream);
 int64_t cusrl_normal_nll_num_partials(int64_t rows, int64_t K);
 
+/* ---- ActionSmoothnessLoss.objective forward AND backward — cusrl/hook/auxiliary/smoothness.py:59-102 ----
+ * mean [T, B, A] fp32 (the action mean of a temporal minibatch), done [T, B] 1-byte flags; an episode ends at a set flag,
+ * that step included (cusrl/nn/utils/recurrent.py:63-92, 215-252); done[T-1] is never read as a boundary.
+ *   first order,  1 <= t < T: pair (t-1, t) of env b valid iff !done[t-1, b];                d1 = mean[t] - mean[t-1]
+ *   second order, 2 <= t < T: triple valid iff !done[t-2, b] && !done[t-1, b];               d2 = -mean[t-2] + 2 mean[t-1] - mean[t]
+ *   losses_out[k-1] = sum_valid sum_a w_k[a] |d_k| / (n_k A);  counts_out[k-1] = n_k, the exact number of valid pairs / triples
+ *   gradient of term k: +-w_1[a] sign(d1) / (n_1 A) on rows t, t-1;  (-1, +2, -1) w_2[a] sign(d2) / (n_2 A) on rows t-2, t-1, t
+ * with sign(0) = 0.  n_k = 0: losses_out[k-1] = NaN (the mean of an empty selection) and the term's gradient is all zeros.
+ * w1 / w2: DEVICE fp32 [A] vectors, read by the launch (a changed weight needs no new capture); NULL: that term is not
+ * evaluated, its loss slot is 0; both NULL: CUSRL_E_INVALID.  d_mean holds one [T, B, A] plane PER NON-NULL WEIGHT, the first
+ * order's first: the terms' gradients stay apart so that each can be scaled by its own incoming gradient.  Every element of
+ * those planes is written exactly once (no zero-fill by the caller, no atomics).
+ * One thread walks one (b, a) column along t; fp32 per element, fp64 block sums finished in one fixed order
+ * (bit-reproducible).  Launches on `stream`: a count pass over `done`, the walk, and a one-block finalize beyond one block
+ * of 256 columns.  workspace: cusrl_action_smoothness_workspace(T, B, A) 8-byte words, not initialised by the caller.
+ * T < 3: CUSRL_E_INVALID;  T * B * A > INT32_MAX: CUSRL_E_UNSUPPORTED (the workspace query then returns 0). */
+int cusrl_action_smoothness_fwd_bwd(const float *mean, const uint8_t *done, const float *w1, const float *w2, int64_t T,
+                                    int64_t B, int64_t A, float *losses_out, int64_t *counts_out, float *d_mean,
+                                    void *workspace, void *stream);
+int64_t cusrl_action_smoothness_workspace(int64_t T, int64_t B, int64_t A);
+
 
 /* ---- Mirror symmetry — cusrl/hook/auxiliary/symmetry.py:30-62,155-356, cusrl/hook/mdp/observation.py:213-217 (ABI 7) ----
  * A mirror table (int32, device) describes MirrorDef(destination_indices, flipped_indices), out[j] = in[dest[j]] * (-1 if j is
