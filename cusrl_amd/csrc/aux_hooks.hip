@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "loss_reduce.hpp"
 
 namespace cusrl {
 
@@ -288,21 +289,12 @@ __global__ __launch_bounds__(kPrepThreads) void amp_style_reward_mean_kernel(con
         if (bonus_out) bonus_out[i] = bonus;
         total += double(bonus);
     }
-    total = wave_sum(total);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) scratch[wave] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kPrepThreads / kWave; ++w) s += scratch[w];
-        *mean_out = float(s / double(rows));
-    }
+    total = block_sum<double, kPrepThreads / kWave>(total, scratch);
+    if (threadIdx.x == 0) *mean_out = float(total / double(rows));
 }
 
 // --------------------------------------------------------------------------------------------- MSE loss, forward + backward
-constexpr int kMseMaxBlocks = 1024;
-
-// target == nullptr: zeros (a plain scaled sum of squares).  gridDim.x == 1: the block finalises itself (loss_out).
+// target == nullptr: zeros (a plain scaled sum of squares).  The sum leaves through publish_loss_sums (loss_reduce.hpp).
 __global__ __launch_bounds__(kBlock) void mse_fwd_bwd_kernel(const float *__restrict__ prediction,
                                                              const float *__restrict__ target, int64_t n, float grad_scale,
                                                              float *__restrict__ d_prediction,
@@ -327,22 +319,7 @@ __global__ __launch_bounds__(kBlock) void mse_fwd_bwd_kernel(const float *__rest
             d_prediction[i] = grad_scale * d;  // d mean((p - t)^2) / d p = 2 (p - t) / n
         }
     }
-    const double total = block_sum(acc, scratch);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1)
-            *loss_out = float(total * loss_scale);
-        else
-            partials[blockIdx.x] = total;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void mse_finalize_kernel(const double *__restrict__ partials, int blocks,
-                                                              double loss_scale, float *__restrict__ loss_out) {
-    __shared__ double scratch[kWavesPerBlock];
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += kBlock) acc += partials[b];
-    const double total = block_sum(acc, scratch);
-    if (threadIdx.x == 0) *loss_out = float(total * loss_scale);
+    publish_loss_sums<1>({acc}, scratch, partials, loss_out, ScaledLoss<1>{{loss_scale}});
 }
 
 // --------------------------------------------------------------------------------------------- column MSE, forward + backward
@@ -384,13 +361,7 @@ __global__ __launch_bounds__(kBlock) void column_mse_fwd_bwd_kernel(const float 
             d_prediction[i] = grad_scale * d;  // d (w mean((p - t)^2)) / d p = 2 w (p - t) / n
         }
     }
-    const double total = block_sum(acc, scratch);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1)
-            *loss_out = float(total * loss_scale);
-        else
-            partials[blockIdx.x] = total;
-    }
+    publish_loss_sums<1>({acc}, scratch, partials, loss_out, ScaledLoss<1>{{loss_scale}});
 }
 
 // --------------------------------------------------------------------------------------------- Normal NLL, forward + backward
@@ -459,13 +430,7 @@ __global__ __launch_bounds__(kBlock) void normal_nll_fwd_bwd_kernel(
             d_dist[int64_t(r) * grad_pitch + k] = gd;
         }
     }
-    const double total = block_sum(acc, scratch);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1)
-            *loss_out = float(total * loss_scale);
-        else
-            partials[blockIdx.x] = total;
-    }
+    publish_loss_sums<1>({acc}, scratch, partials, loss_out, ScaledLoss<1>{{loss_scale}});
 }
 
 // --------------------------------------------------------------------------------------------- BCE-with-logits of a joint batch
@@ -487,15 +452,8 @@ __global__ __launch_bounds__(kPrepThreads) void bce_pair_fwd_bwd_kernel(const fl
         total += double((1.0f - t) * x - log_sigmoid);
         d_logit[i] = (1.0f / (1.0f + expf(-x)) - t) * grad_scale;
     }
-    total = wave_sum(total);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) scratch[wave] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kPrepThreads / kWave; ++w) s += scratch[w];
-        *loss_out = float(s / double(n) * double(weight));
-    }
+    total = block_sum<double, kPrepThreads / kWave>(total, scratch);
+    if (threadIdx.x == 0) *loss_out = float(total / double(n) * double(weight));
 }
 
 // --------------------------------------------------------------------------------------------- synthetic benchmark env
@@ -681,22 +639,14 @@ extern "C" int cusrl_amp_style_reward_mean(const float *logit, float *reward, fl
     return launch_status();
 }
 
-extern "C" int64_t cusrl_mse_loss_num_partials(int64_t n) {
-    if (n <= 0) return 0;
-    if (n <= int64_t(kBlock) * 64) return 1;  // small batches (a discriminator batch: 6 K elements): one block finalises itself
-    const int64_t want = ceil_div(n, int64_t(kBlock) * 8);
-    return want > kMseMaxBlocks ? kMseMaxBlocks : want;
-}
+extern "C" int64_t cusrl_mse_loss_num_partials(int64_t n) { return loss_blocks(n); }
 
 static int launch_sumsq(const float *x, const float *target, int64_t n, double loss_scale, float grad_scale, float *loss_out,
                         float *grad_out, double *partials, hipStream_t s) {
-    const int64_t blocks = cusrl_mse_loss_num_partials(n);
+    const int64_t blocks = loss_blocks(n);
     hipLaunchKernelGGL(mse_fwd_bwd_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, x, target, n, grad_scale, grad_out,
                        partials, loss_scale, loss_out);
-    if (int rc = launch_status()) return rc;
-    if (blocks == 1) return 0;  // the one block finalised itself
-    hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), loss_scale, loss_out);
-    return launch_status();
+    return finish_scaled_loss<1>(blocks, partials, {{loss_scale}}, loss_out, s);
 }
 
 extern "C" int cusrl_mse_loss_fwd_bwd(const float *prediction, const float *target, int64_t n, float *loss_out,
@@ -716,7 +666,7 @@ extern "C" int cusrl_sumsq_fwd_bwd(const float *x, int64_t n, double loss_scale,
 
 extern "C" int64_t cusrl_column_mse_num_partials(int64_t rows, int64_t K) {
     if (rows <= 0 || K <= 0 || rows > INT32_MAX / K) return 0;
-    return cusrl_mse_loss_num_partials(rows * K);  // the launch rule of the contiguous loss: one block up to 16 K elements
+    return loss_blocks(rows * K);  // the launch rule of the contiguous loss
 }
 
 extern "C" int cusrl_column_mse_fwd_bwd(const float *prediction, const float *target, int64_t target_pitch,
@@ -734,10 +684,7 @@ extern "C" int cusrl_column_mse_fwd_bwd(const float *prediction, const float *ta
     hipLaunchKernelGGL(column_mse_fwd_bwd_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, prediction, target, target_pitch,
                        columns, uint32_t(n), uint32_t(K), vector, float(2.0 * loss_scale), d_prediction, partials, loss_scale,
                        loss_out);
-    if (int rc = launch_status()) return rc;
-    if (blocks == 1) return 0;  // the one block finalised itself
-    hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), loss_scale, loss_out);
-    return launch_status();
+    return finish_scaled_loss<1>(blocks, partials, {{loss_scale}}, loss_out, s);
 }
 
 extern "C" int64_t cusrl_normal_nll_num_partials(int64_t rows, int64_t K) { return cusrl_column_mse_num_partials(rows, K); }
@@ -762,10 +709,7 @@ extern "C" int cusrl_normal_nll_fwd_bwd(const float *mean, int64_t mean_pitch, c
     hipLaunchKernelGGL(normal_nll_fwd_bwd_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, mean, mean_pitch, dist, dist_pitch,
                        target, target_pitch, uint32_t(n), uint32_t(K), vector, mode, full, bound, half_g, d_mean, d_dist,
                        grad_pitch, partials, loss_scale, loss_out);
-    if (int rc = launch_status()) return rc;
-    if (blocks == 1) return 0;  // the one block finalised itself
-    hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), loss_scale, loss_out);
-    return launch_status();
+    return finish_scaled_loss<1>(blocks, partials, {{loss_scale}}, loss_out, s);
 }
 
 extern "C" int cusrl_bce_pair_fwd_bwd(const float *logit, int64_t rows, float weight, float *loss_out, float *d_logit,

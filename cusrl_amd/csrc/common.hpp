@@ -60,8 +60,9 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;  // valid in lane 0
 }
 
-// Sum over the block; result valid in thread 0.  `scratch` holds kWavesPerBlock entries.
-template <typename T>
+// Sum over a block of kWaves waves; result valid in thread 0.  `scratch` holds kWaves entries, which thread 0 adds in index
+// order.
+template <typename T, int kWaves = kWavesPerBlock>
 __device__ __forceinline__ T block_sum(T v, T *scratch) {
     v = wave_sum(v);
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -70,7 +71,7 @@ __device__ __forceinline__ T block_sum(T v, T *scratch) {
     T total = T(0);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int w = 0; w < kWavesPerBlock; ++w) total += scratch[w];
+        for (int w = 0; w < kWaves; ++w) total += scratch[w];
     }
     __syncthreads();
     return total;

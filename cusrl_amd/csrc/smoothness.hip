@@ -13,6 +13,7 @@
 // with sign(0) = 0 (torch's abs backward).  n_k = 0: the loss is 0 / 0 = NaN (the mean of an empty selection) and no pair or
 // triple exists that could add to the gradient, which is then all zeros — what the reference's autograd gives.
 #include "common.hpp"
+#include "loss_reduce.hpp"
 
 namespace cusrl {
 
@@ -120,32 +121,16 @@ __global__ __launch_bounds__(kBlock) void smoothness_walk_kernel(
         if (g1) g1[last] = p1;
         if (g2) g2[last - BA] = q2, g2[last] = q1;
     }
-    const double sum1 = block_sum(acc1, scratch), sum2 = block_sum(acc2, scratch);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1) {
-            losses_out[0] = g1 ? mean_loss(sum1, n1, A) : 0.0f;
-            losses_out[1] = g2 ? mean_loss(sum2, n2, A) : 0.0f;
-        } else {
-            loss_partials[2 * blockIdx.x] = sum1;
-            loss_partials[2 * blockIdx.x + 1] = sum2;
-        }
-    }
+    publish_loss_sums<2>({acc1, acc2}, scratch, loss_partials, losses_out,
+                         [&](int k, double sum) { return (k ? g2 : g1) ? mean_loss(sum, k ? n2 : n1, A) : 0.0f; });
 }
 
 __global__ __launch_bounds__(kBlock) void smoothness_finalize_kernel(const double *__restrict__ loss_partials, int blocks,
                                                                      const long long *__restrict__ counts, int A, int has1,
                                                                      int has2, float *__restrict__ losses_out) {
     __shared__ double scratch[kWavesPerBlock];
-    double acc1 = 0.0, acc2 = 0.0;
-    for (int block = threadIdx.x; block < blocks; block += kBlock) {
-        acc1 += loss_partials[2 * block];
-        acc2 += loss_partials[2 * block + 1];
-    }
-    const double sum1 = block_sum(acc1, scratch), sum2 = block_sum(acc2, scratch);
-    if (threadIdx.x == 0) {
-        losses_out[0] = has1 ? mean_loss(sum1, counts[0], A) : 0.0f;
-        losses_out[1] = has2 ? mean_loss(sum2, counts[1], A) : 0.0f;
-    }
+    finalize_loss_sums<2>(loss_partials, blocks, scratch, losses_out,
+                          [&](int k, double sum) { return (k ? has2 : has1) ? mean_loss(sum, counts[k], A) : 0.0f; });
 }
 
 static int64_t count_blocks_of(int64_t B) {

@@ -9,12 +9,12 @@
 // [C_out] inverse codes.  A code is a column index with bit 31 set when the value is negated.  A negation is a sign flip
 // (exact, signed zeros included), which is what `x * -1` is for every non-NaN x.
 #include "common.hpp"
+#include "loss_reduce.hpp"
 
 namespace cusrl {
 
 constexpr uint32_t kFlipBit = 0x80000000u;
 constexpr int kMirrorTile = 4096;  // elements per block of the row kernels (whole rows; a wider row takes a block alone)
-constexpr int kMirrorMaxBlocks = 1024;
 
 __device__ __forceinline__ float apply_code(float v, uint32_t code) { return (code & kFlipBit) ? -v : v; }
 __device__ __forceinline__ int code_column(uint32_t code) { return int(code & ~kFlipBit); }
@@ -85,8 +85,7 @@ __global__ __launch_bounds__(kBlock) void mirror_mse_kernel(const float *__restr
                                                             int A, float g_mean, float g_std, float *__restrict__ d_mu,
                                                             float *__restrict__ d_mu_m, float *__restrict__ d_sigma,
                                                             float *__restrict__ d_sigma_m, double *__restrict__ partials,
-                                                            double loss_mean_scale, double loss_std_scale,
-                                                            float *__restrict__ loss_out) {
+                                                            ScaledLoss<2> scales, float *__restrict__ loss_out) {
     __shared__ double scratch[kWavesPerBlock];
     const uint32_t *offsets = table + A, *inverse = table + 2 * A + 1;
     const int64_t n = B * A, stride = int64_t(gridDim.x) * kBlock;
@@ -135,34 +134,7 @@ __global__ __launch_bounds__(kBlock) void mirror_mse_kernel(const float *__restr
             d_sigma_m[j] = a2 * sign_of(sigma_m[j]);
         }
     }
-    const double total_mean = block_sum(acc_mean, scratch);
-    const double total_std = block_sum(acc_std, scratch);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1) {
-            loss_out[0] = float(total_mean * loss_mean_scale);
-            loss_out[1] = float(total_std * loss_std_scale);
-        } else {
-            partials[2 * blockIdx.x] = total_mean;
-            partials[2 * blockIdx.x + 1] = total_std;
-        }
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void mirror_mse_finalize_kernel(const double *__restrict__ partials, int blocks,
-                                                                     double loss_mean_scale, double loss_std_scale,
-                                                                     float *__restrict__ loss_out) {
-    __shared__ double scratch[kWavesPerBlock];
-    double acc_mean = 0.0, acc_std = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += kBlock) {
-        acc_mean += partials[2 * b];
-        acc_std += partials[2 * b + 1];
-    }
-    const double total_mean = block_sum(acc_mean, scratch);
-    const double total_std = block_sum(acc_std, scratch);
-    if (threadIdx.x == 0) {
-        loss_out[0] = float(total_mean * loss_mean_scale);
-        loss_out[1] = float(total_std * loss_std_scale);
-    }
+    publish_loss_sums<2>({acc_mean, acc_std}, scratch, partials, loss_out, scales);
 }
 
 // observation.py:213-217 in fp32, one rounding per operation and in the reference's order:
@@ -228,12 +200,7 @@ extern "C" int cusrl_mirror_rows_bwd(const float *grad_out, int64_t go_stride, f
     return launch_status();
 }
 
-extern "C" int64_t cusrl_mirror_mse_num_partials(int64_t n) {
-    if (n <= 0) return 0;
-    if (n <= int64_t(kBlock) * 64) return 1;  // one block finalises itself
-    const int64_t want = ceil_div(n, int64_t(kBlock) * 8);
-    return want > kMirrorMaxBlocks ? kMirrorMaxBlocks : want;
-}
+extern "C" int64_t cusrl_mirror_mse_num_partials(int64_t n) { return loss_blocks(n); }
 
 extern "C" int cusrl_mirror_mse_fwd_bwd(const float *mu, const float *mu_m, const float *sigma, const float *sigma_m,
                                         int std_vector, const int32_t *table, int64_t B, int64_t A, double weight,
@@ -244,19 +211,15 @@ extern "C" int cusrl_mirror_mse_fwd_bwd(const float *mu, const float *mu_m, cons
     if ((sigma == nullptr) != (sigma_m == nullptr)) return CUSRL_E_INVALID;
     if (sigma && (!d_sigma || !d_sigma_m)) return CUSRL_E_INVALID;
     if (A > 65536 || B > (int64_t(1) << 40) / A) return CUSRL_E_UNSUPPORTED;
-    const int64_t n = B * A, blocks = cusrl_mirror_mse_num_partials(n);
+    const int64_t n = B * A, blocks = loss_blocks(n);
     const double std_count = sigma ? double(std_vector ? A : n) : 1.0;
     const float g_mean = float(2.0 * weight / double(n)), g_std = float(2.0 * weight / std_count);
-    const double mean_scale = weight / double(n), std_scale = weight / std_count;
+    const ScaledLoss<2> scales{{weight / double(n), weight / std_count}};
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(mirror_mse_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, s, mu, mu_m, sigma, sigma_m, std_vector,
                        reinterpret_cast<const uint32_t *>(table), B, int(A), g_mean, g_std, d_mu, d_mu_m, d_sigma, d_sigma_m,
-                       partials, mean_scale, std_scale, loss_out);
-    if (int rc = launch_status()) return rc;
-    if (blocks == 1) return 0;
-    hipLaunchKernelGGL(mirror_mse_finalize_kernel, dim3(1), dim3(kBlock), 0, s, partials, int(blocks), mean_scale, std_scale,
-                       loss_out);
-    return launch_status();
+                       partials, scales, loss_out);
+    return finish_scaled_loss<2>(blocks, partials, scales, loss_out, s);
 }
 
 extern "C" int cusrl_symmetrize_mean_var(float *mean, float *var, const int32_t *table, int64_t C, void *stream) {

@@ -139,11 +139,11 @@ class _ReluDiscriminatorObjective(torch.autograd.Function):
         logit, target, ones, input_gradient, *saved = ctx.saved_tensors  # ones: [1, 2N], column sums as GEMMs
         hidden, units, weights = saved[:layers], saved[layers:2 * layers - 1], saved[2 * layers - 1:]
         # --- penalty: d/dW_k of mean || u_1 W_1 ||^2, the masks being constants
-        from cusrl_amd.nn.module import is_unit_gradient
+        from cusrl_amd.nn.module import saved_gradients
 
         if ctx.on_device:  # `input_gradient` already is 2 g pw lw / rows, `logit` already d loss / d logit (forward kernels):
             # used as they are when the incoming gradient IS the agent's unit scalar (the summands as separate roots), else scaled
-            d_input = input_gradient if is_unit_gradient(grad_penalty) else input_gradient * grad_penalty
+            (d_input,) = saved_gradients((input_gradient,), grad_penalty)
         else:
             d_input = input_gradient * (grad_penalty * (2.0 * ctx.penalty_weight * ctx.loss_weight / rows))
         penalty_grads = [units[0].t() @ d_input]
@@ -155,7 +155,7 @@ class _ReluDiscriminatorObjective(torch.autograd.Function):
         penalty_grads.append(ones[:, :rows] @ _masked(d_units, hidden[layers - 1][rows:], 0))
         # --- discrimination: an ordinary MLP backward over the joint batch, the penalty's share added by the GEMM
         if ctx.on_device:
-            d_out = logit if is_unit_gradient(grad_discrimination) else logit * grad_discrimination
+            (d_out,) = saved_gradients((logit,), grad_discrimination)
         else:
             d_out = (torch.sigmoid(logit) - target) * (grad_discrimination * (ctx.loss_weight / logit.shape[0]))
         gradients: list[Tensor | None] = []

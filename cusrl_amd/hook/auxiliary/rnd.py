@@ -32,11 +32,9 @@ class _MseLossFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
-        from cusrl_amd.nn.module import is_unit_gradient
+        from cusrl_amd.nn.module import saved_gradients
 
-        (grad,) = ctx.saved_tensors
-        if not is_unit_gradient(grad_loss):  # GradScaler, or a caller that rescales the loss: anything but the agent's unit scalar
-            grad = grad * grad_loss
+        (grad,) = saved_gradients(ctx.saved_tensors, grad_loss)
         return grad.view(ctx.shape), None
 
 

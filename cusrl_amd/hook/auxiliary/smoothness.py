@@ -48,14 +48,14 @@ class _ActionSmoothnessFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_1st, g_2nd):
-        from cusrl_amd.nn.module import is_unit_gradient
+        from cusrl_amd.nn.module import saved_gradients
 
         (d_mean,) = ctx.saved_tensors
         total = None
         for plane, incoming in zip(ctx.planes, (g_1st, g_2nd)):
             if plane is None or incoming is None:
                 continue
-            share = d_mean[plane] if is_unit_gradient(incoming) else d_mean[plane] * incoming
+            (share,) = saved_gradients((d_mean[plane],), incoming)
             total = share if total is None else total + share
         return (None if total is None else total.view(ctx.shape)), None, None, None
 

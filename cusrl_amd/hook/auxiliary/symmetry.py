@@ -156,20 +156,14 @@ class _MirrorSymmetryLossFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_mean, g_std):
-        from cusrl_amd.nn.module import is_unit_gradient
+        from cusrl_amd.nn.module import saved_gradients
 
         saved = ctx.saved_tensors
         d_mean = d_mirrored = d_std = d_mirrored_std = None
         if g_mean is not None:
-            d_mean, d_mirrored = saved[0], saved[1]
-            if not is_unit_gradient(g_mean):
-                d_mean, d_mirrored = d_mean * g_mean, d_mirrored * g_mean
-            d_mean, d_mirrored = d_mean.view(ctx.shapes[0]), d_mirrored.view(ctx.shapes[0])
+            d_mean, d_mirrored = (g.view(ctx.shapes[0]) for g in saved_gradients(saved[:2], g_mean))
         if ctx.has_std and g_std is not None:
-            d_std, d_mirrored_std = saved[2], saved[3]
-            if not is_unit_gradient(g_std):
-                d_std, d_mirrored_std = d_std * g_std, d_mirrored_std * g_std
-            d_std, d_mirrored_std = d_std.view(ctx.shapes[1]), d_mirrored_std.view(ctx.shapes[1])
+            d_std, d_mirrored_std = (g.view(ctx.shapes[1]) for g in saved_gradients(saved[2:4], g_std))
         return d_mean, d_mirrored, d_std, d_mirrored_std, None, None
 
 

@@ -15,20 +15,12 @@ from typing import Literal
 import torch
 from torch import Tensor, nn
 
+from cusrl_amd.nn.module import saved_gradients
+
 __all__ = ["L2RegularizationLoss", "NormalNllLoss"]
 
 LOG_SQRT_2PI = math.log(2 * math.pi) / 2
 _MODES = ("log_var", "log_std", "var", "std")
-
-
-def _scaled(gradients, grad_loss):
-    """The saved gradients as they are under the agent's unit scalar, times the incoming gradient under anything else
-    (GradScaler, a caller that rescales the loss)."""
-    from cusrl_amd.nn.module import is_unit_gradient
-
-    if is_unit_gradient(grad_loss):
-        return list(gradients)
-    return [gradient * grad_loss for gradient in gradients]
 
 
 class _NormalNllFunction(torch.autograd.Function):
@@ -49,7 +41,7 @@ class _NormalNllFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
-        gradients = _scaled(ctx.saved_tensors, grad_loss)
+        gradients = saved_gradients(ctx.saved_tensors, grad_loss)
         return gradients[0], (gradients[1] if len(gradients) == 2 else None), None, None, None, None, None
 
 
@@ -149,7 +141,7 @@ class _SumsqFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
-        return _scaled(ctx.saved_tensors, grad_loss)[0], None, None
+        return saved_gradients(ctx.saved_tensors, grad_loss)[0], None, None
 
 
 class L2RegularizationLoss(nn.Module):

@@ -18,7 +18,7 @@ from cusrl_amd.utils import switches
 from cusrl_amd.utils.nest import iterate_nested
 
 __all__ = ["Linear", "LinearFp32", "fused_inference_layers", "linear_act", "Mlp", "Module", "ModuleFactory", "disable_autocast",
-           "double_differentiable", "is_unit_gradient", "register_unit_gradient", "resolve_activation_fn"]
+           "double_differentiable", "is_unit_gradient", "register_unit_gradient", "resolve_activation_fn", "saved_gradients"]
 
 
 def disable_autocast(device_type: str):
@@ -81,6 +81,15 @@ def is_unit_gradient(grad: torch.Tensor | None) -> bool:
         return False
     ref = _unit_gradients.get(grad.data_ptr())
     return ref is not None and ref() is not None
+
+
+def saved_gradients(gradients, grad_loss) -> list:
+    """What the backward of a loss whose forward launch already wrote its ``gradients`` hands out: the saved tensors as they
+    are under the agent's unit scalar, times the incoming gradient under anything else (GradScaler, a caller that rescales
+    the loss).  A Function with several loss terms applies it per term, each with that term's own incoming gradient."""
+    if is_unit_gradient(grad_loss):
+        return list(gradients)
+    return [gradient * grad_loss for gradient in gradients]
 
 
 @contextmanager

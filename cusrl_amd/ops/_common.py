@@ -89,6 +89,16 @@ def _ptr(tensor: torch.Tensor | None) -> int | None:
     return None if tensor is None else tensor.data_ptr()
 
 
+def _loss_outputs(device, partials_needed: int | None = None, terms: int | None = None):
+    """What a loss pass writes besides its gradients (``csrc/loss_reduce.hpp``): the fp32 loss — a scalar, or one entry per
+    term — and the float64 partial sums of its blocks, one row per block the library asks for (at least one) times the terms;
+    ``partials_needed`` None: a single-workgroup pass, no partials."""
+    loss = torch.empty(() if terms is None else terms, dtype=torch.float32, device=device)
+    if partials_needed is None:
+        return loss, None
+    return loss, torch.empty(max(int(partials_needed), 1) * (terms or 1), dtype=torch.float64, device=device)
+
+
 class _Checked:
     """``_checked.cusrl_x(..., _stream())``: the status-returning entry point ``cusrl_x`` of the loaded library with ``check`` as
     its ctypes ``errcheck``, so the call itself reports under the symbol's name (``_native.launch_counts["cusrl_x"]`` moves) and

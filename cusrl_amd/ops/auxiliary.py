@@ -10,7 +10,7 @@ from collections.abc import Sequence
 import torch
 
 from cusrl_amd import _native
-from cusrl_amd.ops._common import _checked, _f32, _flag, _modified_in_place, _ptr, _stream, require_device
+from cusrl_amd.ops._common import _checked, _f32, _flag, _loss_outputs, _modified_in_place, _ptr, _stream, require_device
 
 
 def masked_col_stats(x: torch.Tensor, mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -182,11 +182,9 @@ def mse_loss_fwd_bwd(prediction: torch.Tensor, target: torch.Tensor) -> tuple[to
     prediction, target = _f32(prediction, "prediction"), _f32(target, "target")
     if prediction.shape != target.shape or prediction.numel() == 0:
         raise ValueError("mse_loss_fwd_bwd: shapes differ or are empty")
-    lib = _native.lib()
     n = prediction.numel()
-    loss = torch.empty((), dtype=torch.float32, device=prediction.device)
+    loss, partials = _loss_outputs(prediction.device, _native.lib().cusrl_mse_loss_num_partials(n))
     grad = torch.empty_like(prediction)
-    partials = torch.empty(max(int(lib.cusrl_mse_loss_num_partials(n)), 1), dtype=torch.float64, device=prediction.device)
     _checked.cusrl_mse_loss_fwd_bwd(prediction.data_ptr(), target.data_ptr(), n, loss.data_ptr(), grad.data_ptr(), partials.data_ptr(), _stream())
     return loss, grad
 
@@ -260,10 +258,8 @@ def column_mse_fwd_bwd(prediction: torch.Tensor, target: torch.Tensor, columns: 
             raise IndexError(f"column_mse_fwd_bwd: columns {low}..{high} out of range for a {W}-wide target")
     target, pitch = _target_rows(target)
     rows = prediction.numel() // K
-    partials_needed = int(_native.lib().cusrl_column_mse_num_partials(rows, K))
-    loss = torch.empty((), dtype=torch.float32, device=prediction.device)
+    loss, partials = _loss_outputs(prediction.device, _native.lib().cusrl_column_mse_num_partials(rows, K))
     grad = torch.empty_like(prediction)
-    partials = torch.empty(max(partials_needed, 1), dtype=torch.float64, device=prediction.device)
     _checked.cusrl_column_mse_fwd_bwd(prediction.data_ptr(), target.data_ptr(), pitch, _ptr(columns), rows, K, float(weight),
             loss.data_ptr(), grad.data_ptr(), partials.data_ptr(), _stream())
     return loss, grad
@@ -313,9 +309,7 @@ def normal_nll_fwd_bwd(mean: torch.Tensor, dist: torch.Tensor | None, target: to
                          "are empty")
     target, target_pitch = _target_rows(target)
     rows = d_mean.numel() // K
-    partials_needed = int(_native.lib().cusrl_normal_nll_num_partials(rows, K))
-    loss = torch.empty((), dtype=torch.float32, device=mean.device)
-    partials = torch.empty(max(partials_needed, 1), dtype=torch.float64, device=mean.device)
+    loss, partials = _loss_outputs(mean.device, _native.lib().cusrl_normal_nll_num_partials(rows, K))
     _checked.cusrl_normal_nll_fwd_bwd(mean.data_ptr(), pitch, dist_ptr, pitch, target.data_ptr(), target_pitch, rows, K,
             NORMAL_NLL_MODES[mode], int(bool(full)), normal_nll_bound(mode, eps), _REDUCTIONS[reduction], loss.data_ptr(),
             d_mean.data_ptr(), d_dist.data_ptr(), pitch, partials.data_ptr(), _stream())
@@ -361,11 +355,9 @@ def action_smoothness_fwd_bwd(mean: torch.Tensor, done: torch.Tensor, w1: torch.
 def sumsq_fwd_bwd(x: torch.Tensor, loss_scale: float, grad_scale: float) -> tuple[torch.Tensor, torch.Tensor]:
     """``(loss_scale * sum(x^2), grad_scale * x)`` from one pass (AMP's gradient penalty and what it sends back)."""
     x = _f32(x, "x")
-    lib = _native.lib()
     n = x.numel()
-    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    loss, partials = _loss_outputs(x.device, _native.lib().cusrl_mse_loss_num_partials(n))
     grad = torch.empty_like(x)
-    partials = torch.empty(max(int(lib.cusrl_mse_loss_num_partials(n)), 1), dtype=torch.float64, device=x.device)
     _checked.cusrl_sumsq_fwd_bwd(x.data_ptr(), n, float(loss_scale), float(grad_scale), loss.data_ptr(), grad.data_ptr(),
             partials.data_ptr(), _stream())
     return loss, grad
@@ -377,7 +369,7 @@ def bce_pair_fwd_bwd(logit: torch.Tensor, weight: float) -> tuple[torch.Tensor, 
     logit = _f32(logit, "logit")
     if logit.numel() % 2:
         raise ValueError("bce_pair_fwd_bwd: the joint batch holds as many expert as agent rows")
-    loss = torch.empty((), dtype=torch.float32, device=logit.device)
+    loss, _ = _loss_outputs(logit.device)
     grad = torch.empty_like(logit)
     _checked.cusrl_bce_pair_fwd_bwd(logit.data_ptr(), logit.numel() // 2, float(weight), loss.data_ptr(), grad.data_ptr(), _stream())
     return loss, grad

@@ -8,7 +8,7 @@ import torch
 
 from cusrl_amd import _native
 from cusrl_amd._native import MirrorField
-from cusrl_amd.ops._common import _checked, _f32, _modified_in_place, _ptr, _stream, require_device
+from cusrl_amd.ops._common import _checked, _f32, _loss_outputs, _modified_in_place, _ptr, _stream, require_device
 
 
 def _mirror_table(table: torch.Tensor, device: torch.device, c_in: int, c_out: int) -> torch.Tensor:
@@ -92,12 +92,10 @@ def mirror_mse_fwd_bwd(mean: torch.Tensor, mirrored_mean: torch.Tensor, table: t
         vector = std.dim() == 1
         if (std.shape != (A,)) if vector else (std.shape != mean.shape):
             raise ValueError(f"mirror_mse_fwd_bwd: std must be [A] or shaped like the mean, got {tuple(std.shape)}")
-    lib = _native.lib()
-    losses = torch.empty(2, dtype=torch.float32, device=mean.device)
+    losses, partials = _loss_outputs(mean.device, _native.lib().cusrl_mirror_mse_num_partials(B * A), terms=2)
     d_mean, d_mirrored = torch.empty_like(mean), torch.empty_like(mean)
     d_std = None if std is None else torch.empty_like(std)
     d_mirrored_std = None if std is None else torch.empty_like(std)
-    partials = torch.empty(2 * max(int(lib.cusrl_mirror_mse_num_partials(B * A)), 1), dtype=torch.float64, device=mean.device)
     _checked.cusrl_mirror_mse_fwd_bwd(mean.data_ptr(), mirrored_mean.data_ptr(), _ptr(std), _ptr(mirrored_std), int(vector),
             table.data_ptr(), B, A, float(weight), losses.data_ptr(), d_mean.data_ptr(), d_mirrored.data_ptr(), _ptr(d_std),
             _ptr(d_mirrored_std), partials.data_ptr(), _stream())
