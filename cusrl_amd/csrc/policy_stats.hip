@@ -78,16 +78,18 @@ __global__ __launch_bounds__(kBlock) void categorical_policy_stats_kernel(const 
             sp += expf(zp[j] - mp), sq += expf(zq[j] - mq);
             if (a[j] > best) best = a[j], taken = j;
         }
-        const float np = mp + logf(sp), nq = mq + logf(sq);
+        // log p_j = (z_j - max) - log sum: the difference first, so that a constant added to a row of logits (|z| ~ 1e4: one ulp
+        // is 1e-3) cancels exactly and never reaches the normaliser
+        const float lsp = logf(sp), lsq = logf(sq);
         float kl = 0.f;
         for (int j = 0; j < A; ++j) {
-            const float lp = zp[j] - np, lq = zq[j] - nq, pj = expf(lp);
+            const float lp = (zp[j] - mp) - lsp, lq = (zq[j] - mq) - lsq, pj = expf(lp);
             float t = pj * (lp - lq);
             if (expf(lq) == 0.0f) t = INFINITY;  // t[(q.probs == 0)] = inf
             if (pj == 0.0f) t = 0.0f;            // t[(p.probs == 0)] = 0
             kl += t;
         }
-        const float weight = expf((zq[taken] - nq) - old_logp[row]);
+        const float weight = expf(((zq[taken] - mq) - lsq) - old_logp[row]);
         float iw = 0.f;
         for (int d = 0; d < D; ++d) iw += advantage[row * D + d] * weight;
         acc[0] = double(kl), acc[1] = double(iw);

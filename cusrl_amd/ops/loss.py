@@ -385,10 +385,10 @@ def policy_stats(old_mean: torch.Tensor, old_std: torch.Tensor, new_mean: torch.
     over a batch (cusrl/hook/on_policy/stats.py:28-40) — a 3-element device tensor from one pass."""
     tensors = [_f32(t, n) for t, n in ((old_mean, "old_mean"), (old_std, "old_std"), (new_mean, "new_mean"), (new_std, "new_std"),
                                        (action, "action"), (old_logp, "old_logp"), (advantage, "advantage"))]
-    A = new_mean.shape[-1]
-    B = new_mean.numel() // A
-    D = advantage.numel() // B
-    if any(t.numel() != B * A for t in tensors[:5]) or tensors[5].numel() != B or tensors[6].numel() != B * D:
+    A = new_mean.shape[-1] if new_mean.dim() else 0
+    B = new_mean.numel() // max(A, 1)
+    D = advantage.numel() // max(B, 1)
+    if min(A, B, D) == 0 or any(t.numel() != B * A for t in tensors[:5]) or tensors[5].numel() != B or tensors[6].numel() != B * D:
         raise ValueError("policy_stats: inconsistent shapes")
     lib = _native.lib()
     dev = new_mean.device
@@ -404,10 +404,10 @@ def categorical_policy_stats(old_logits: torch.Tensor, new_logits: torch.Tensor,
     a batch — the discrete-action form of :func:`policy_stats`."""
     tensors = [_f32(t, n) for t, n in ((old_logits, "old_logits"), (new_logits, "new_logits"), (action, "action"),
                                        (old_logp, "old_logp"), (advantage, "advantage"))]
-    A = new_logits.shape[-1]
-    B = new_logits.numel() // A
-    D = advantage.numel() // B
-    if any(t.numel() != B * A for t in tensors[:3]) or tensors[3].numel() != B or tensors[4].numel() != B * D:
+    A = new_logits.shape[-1] if new_logits.dim() else 0
+    B = new_logits.numel() // max(A, 1)
+    D = advantage.numel() // max(B, 1)
+    if min(A, B, D) == 0 or any(t.numel() != B * A for t in tensors[:3]) or tensors[3].numel() != B or tensors[4].numel() != B * D:
         raise ValueError("categorical_policy_stats: inconsistent shapes")
     lib = _native.lib()
     dev = new_logits.device

@@ -123,16 +123,59 @@ def merge_mean_var(means, vars_):
 
 
 # ------------------------------------------------------------------------------------------ policy statistics
-def policy_stats(old_mean, old_std, new_mean, new_std, action, old_logp, advantage):
+def policy_stats(old_mean, old_std, new_mean, new_std, action, old_logp, advantage, return_mass=False):
     """cusrl/hook/on_policy/stats.py:28-40 for a Normal policy: (mean KL(old || new) summed over action dims,
-    mean advantage * exp(logp_new(action) - old_logp), mean new_std), computed in float64."""
+    mean advantage * exp(logp_new(action) - old_logp), mean new_std), computed in float64.
+
+    ``return_mass=True``: ``(statistics, mass)`` — per statistic the float64 mean, over the same divisor, of the absolute values
+    of every term that enters its sum (KL: 0.5 (|r| + |t1| + 1 + |log r|); weighted advantage: |adv| * weight; std: |s_q|):
+    what an fp32 evaluation's error is proportional to, also where the terms cancel."""
     mp, sp, mq, sq, x = (np.asarray(a, np.float64) for a in (old_mean, old_std, new_mean, new_std, action))
     var_ratio = (sp / sq) ** 2  # torch.distributions.kl._kl_normal_normal
-    kl = (0.5 * (var_ratio + ((mp - mq) / sq) ** 2 - 1.0 - np.log(var_ratio))).sum(-1)
+    t1 = ((mp - mq) / sq) ** 2
+    kl = (0.5 * (var_ratio + t1 - 1.0 - np.log(var_ratio))).sum(-1)
     logp = (-((x - mq) ** 2) / (2.0 * sq**2) - np.log(sq) - 0.5 * np.log(2.0 * np.pi)).sum(-1)
-    weight = np.exp(logp - np.asarray(old_logp, np.float64).reshape(-1))
+    weight = np.exp(logp.reshape(-1) - np.asarray(old_logp, np.float64).reshape(-1))
     advantage = np.asarray(advantage, np.float64).reshape(weight.size, -1)
-    return float(kl.mean()), float((advantage * weight[:, None]).mean()), float(sq.mean())
+    stats = float(kl.mean()), float((advantage * weight[:, None]).mean()), float(sq.mean())
+    if not return_mass:
+        return stats
+    kl_mass = (0.5 * (np.abs(var_ratio) + np.abs(t1) + 1.0 + np.abs(np.log(var_ratio)))).sum(-1)
+    return stats, (float(kl_mass.mean()), float((np.abs(advantage) * weight[:, None]).mean()), float(np.abs(sq).mean()))
+
+
+def categorical_policy_stats(old_logits, new_logits, action, old_logp, advantage, return_mass=False):
+    """cusrl/hook/on_policy/stats.py:28-40 for a one-hot categorical actor, in float64.  ``compute_kl_div`` ends in
+    torch.distributions.kl._kl_categorical_categorical: per row ``sum_j p_j (log p_j - log q_j)`` whose elements are set to
+    +inf where ``q_j == 0`` and THEN to 0 where ``p_j == 0`` (a masked action of the old policy contributes nothing, one only
+    the new policy masks makes the row infinite); ``compute_logp`` ends in OneHotCategorical.log_prob: ``log q`` at the
+    arg-max of the one-hot action.  Returns (mean KL, mean over [B, D] of advantage * exp(log q_taken - old_logp), 0.0): this
+    family has no ``action_std``.  ``return_mass`` as in :func:`policy_stats` (KL: p_j (|log p_j| + |log q_j|))."""
+    zp, zq = np.asarray(old_logits, np.float64), np.asarray(new_logits, np.float64)
+    A = zp.shape[-1]
+    zp, zq = zp.reshape(-1, A), zq.reshape(-1, A)
+
+    def log_softmax(z):
+        m = z.max(-1, keepdims=True)  # (the difference first: a constant added to a row cancels exactly)
+        return (z - m) - np.log(np.exp(z - m).sum(-1, keepdims=True))
+
+    lp, lq = log_softmax(zp), log_softmax(zq)
+    p, q = np.exp(lp), np.exp(lq)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = p * (lp - lq)
+        t[q == 0.0] = np.inf
+        t[p == 0.0] = 0.0
+        kl = t.sum(-1)
+    taken = np.asarray(action).reshape(-1, A).argmax(-1)  # first maximum, like value.max(-1)[1]
+    weight = np.exp(lq[np.arange(zq.shape[0]), taken] - np.asarray(old_logp, np.float64).reshape(-1))
+    advantage = np.asarray(advantage, np.float64).reshape(weight.size, -1)
+    stats = float(kl.mean()), float((advantage * weight[:, None]).mean()), 0.0
+    if not return_mass:
+        return stats
+    with np.errstate(invalid="ignore", over="ignore"):
+        m = p * (np.abs(lp) + np.abs(lq))
+        m[p == 0.0] = 0.0
+    return stats, (float(m.sum(-1).mean()), float((np.abs(advantage) * weight[:, None]).mean()), 0.0)
 
 
 # ------------------------------------------------------------------------------------------ gradient clipping
