@@ -5,6 +5,7 @@
 //   cusrl_mirror_rows_bwd      its gradient, through the inverse table (fixed-order sums per input column)
 //   cusrl_mirror_mse_fwd_bwd   MirrorSymmetryLoss: both weighted terms and the gradients wrt both actor outputs in one pass
 //   cusrl_symmetrize_mean_var  the symmetric running-statistics update of ObservationNormalization, in place
+//   cusrl_symmetric_head_fwd / _bwd / _sample   the head of SymmetricActor over the stacked [2B, A] rows of ONE wrapped pass
 // Table (int32, built once on the host, cusrl_amd/hook/auxiliary/symmetry.py): [C_out] forward codes, [C_in + 1] offsets,
 // [C_out] inverse codes.  A code is a column index with bit 31 set when the value is negated.  A negation is a sign flip
 // (exact, signed zeros included), which is what `x * -1` is for every non-NaN x.
@@ -159,6 +160,153 @@ __global__ __launch_bounds__(kBlock) void symmetrize_mean_var_kernel(float *__re
     }
 }
 
+// ---- the head of a symmetric actor (SymmetricActor, symmetry.py:396-456): the wrapped actor ran ONCE over the stacked rows
+// [2B, A] (original rows first, mirrored rows second); these combine the two halves.  A std vector ([A], NormalDist) is one
+// row that is both halves.  Every operation is one fp32 rounding in torch's order: (o + M(m)) / 2 as add, then * 0.5 (exact).
+__device__ __forceinline__ float head_mean(const float *o, const float *m, int j, uint32_t code) {
+    return __fmul_rn(__fadd_rn(o[j], apply_code(m[code_column(code)], code)), 0.5f);
+}
+__device__ __forceinline__ float head_std(const float *o, const float *m, int j, uint32_t code) {
+    return __fmul_rn(__fadd_rn(o[j], fabsf(m[code_column(code)])), 0.5f);  // |M(x)| = |x|: the flip does not matter
+}
+
+// Element (b, j) per thread, grid-strided: coalesced stores, the gather stays inside the mirrored row.
+__global__ __launch_bounds__(kBlock) void symmetric_head_fwd_kernel(const float *__restrict__ mean2, const float *__restrict__ std2,
+                                                                    int std_vector, const uint32_t *__restrict__ table, int64_t B,
+                                                                    int A, float *__restrict__ mean_out,
+                                                                    float *__restrict__ std_out) {
+    const uint32_t n = uint32_t(B * A), w = uint32_t(A), stride = gridDim.x * kBlock;
+    for (uint32_t e = blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
+        const uint32_t b = e / w, j = e - b * w;
+        const uint32_t code = table[j];
+        const float *mo = mean2 + size_t(b) * w;
+        mean_out[e] = head_mean(mo, mo + n, int(j), code);
+        const float *so = std_vector ? std2 : std2 + size_t(b) * w;
+        std_out[e] = head_std(so, std_vector ? so : so + n, int(j), code);
+    }
+}
+
+// The combine + Normal.rsample with the caller's eps + Normal.log_prob summed over A.  One lane per row (rollout.hip's shape:
+// rows are short and the batch is one env step); the row's log-prob accumulates in fp64, nothing else stays live across columns.
+__global__ __launch_bounds__(kBlock) void symmetric_head_sample_kernel(const float *__restrict__ mean2, const float *__restrict__ std2,
+                                                                       int std_vector, const float *__restrict__ eps,
+                                                                       const uint32_t *__restrict__ table, int64_t B, int A,
+                                                                       float *__restrict__ action, float *__restrict__ logp,
+                                                                       float *__restrict__ mean_out, float *__restrict__ std_out) {
+    const int64_t b = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (b >= B) return;
+    const int64_t row = b * A, half = B * A;
+    const float *mo = mean2 + row, *so = std_vector ? std2 : std2 + row;
+    const float *mm = mo + half, *sm = std_vector ? so : so + half;
+    double acc = 0.0;
+    for (int j = 0; j < A; ++j) {
+        const uint32_t code = table[j];
+        const float m = head_mean(mo, mm, j, code), s = head_std(so, sm, j, code);
+        const float a = __fadd_rn(m, __fmul_rn(s, eps[row + j]));
+        const double d = double(a) - double(m), sd = double(s);
+        acc += -(d * d) / (2.0 * sd * sd) - log(sd) - 0.918938533204672741780329736406;
+        mean_out[row + j] = m;
+        std_out[row + j] = s;
+        action[row + j] = a;
+    }
+    logp[b] = float(acc);
+}
+
+// One term of d std_m[i]: output column (code) read input column i whose value is s.  torch's order: g / 2, times sign(M(s)), times
+// the mirror's multiplier; the sign as torch evaluates it, (0 < x) - (x < 0): +0 for either zero.
+__device__ __forceinline__ float head_std_term(float g, float s, uint32_t code) {
+    const float m = apply_code(s, code), sgn = float(0.0f < m) - float(m < 0.0f);
+    return apply_code(__fmul_rn(__fmul_rn(g, 0.5f), sgn), code);
+}
+
+// blockIdx.y < elementwise_planes: element (b, i) per thread over those planes' blocks — d_o[b, i] = g / 2 and d_m[b, i], the
+// inverse list's terms in increasing output column (the order of mirror_rows_bwd_kernel).  The planes behind them take one
+// column sum each — the head's bias gradient (d_bias != NULL: A planes), then a std vector's gradient (A planes): a column's
+// blocks add d_o + d_m ROW BY ROW in fp64 and publish like a loss pass (loss_reduce.hpp).  Pairing the halves per row is what
+// makes the bias gradient of a column that mirrors onto itself with a flip exactly 0 (g / 2 - g / 2 in every row), as the
+// reference's two passes have it; one fp32 column sum over the 2B stacked rows leaves a rounding residue there.
+__global__ __launch_bounds__(kBlock) void symmetric_head_bwd_kernel(const float *__restrict__ g_mean, const float *__restrict__ g_std,
+                                                                    const float *__restrict__ std2, int std_vector,
+                                                                    const uint32_t *__restrict__ table, int64_t B, int A,
+                                                                    int elementwise_planes, float *__restrict__ d_mean2,
+                                                                    float *__restrict__ d_std2, float *__restrict__ d_bias,
+                                                                    double *__restrict__ partials) {
+    __shared__ double scratch[kWavesPerBlock];
+    const uint32_t *offsets = table + A, *inverse = table + 2 * A + 1;
+    const uint32_t w = uint32_t(A);
+    if (int(blockIdx.y) < elementwise_planes) {
+        const uint32_t n = uint32_t(B * A), stride = uint32_t(elementwise_planes) * gridDim.x * kBlock;
+        const bool std_matrix = g_std != nullptr && !std_vector;
+        for (uint32_t e = (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x; e < n; e += stride) {
+            const uint32_t b = e / w, i = e - b * w;
+            const uint32_t first = offsets[i], last = offsets[i + 1];
+            if (g_mean != nullptr) {
+                const float *g = g_mean + size_t(b) * w;
+                d_mean2[e] = __fmul_rn(g[i], 0.5f);
+                float acc = 0.0f;
+                for (uint32_t k = first; k < last; ++k) {
+                    const uint32_t c = inverse[k];
+                    acc += apply_code(__fmul_rn(g[code_column(c)], 0.5f), c);
+                }
+                d_mean2[n + e] = acc;
+            }
+            if (std_matrix) {
+                const float *g = g_std + size_t(b) * w;
+                const float s = std2[n + e];
+                d_std2[e] = __fmul_rn(g[i], 0.5f);
+                float acc = 0.0f;
+                for (uint32_t k = first; k < last; ++k) {
+                    const uint32_t c = inverse[k];
+                    acc += head_std_term(g[code_column(c)], s, c);
+                }
+                d_std2[n + e] = acc;
+            }
+        }
+        return;
+    }
+    const int column = int(blockIdx.y) - elementwise_planes;
+    const bool of_bias = d_bias != nullptr && column < A;
+    const int i = of_bias || d_bias == nullptr ? column : column - A;
+    const uint32_t first = offsets[i], last = offsets[i + 1];
+    const float *g0 = of_bias ? g_mean : g_std;
+    const float s = of_bias ? 0.0f : std2[i];
+    double acc[1] = {0.0};
+    for (int64_t b = int64_t(blockIdx.x) * kBlock + threadIdx.x; b < B; b += int64_t(gridDim.x) * kBlock) {
+        const float *g = g0 + b * A;
+        double row = double(__fmul_rn(g[i], 0.5f));
+        for (uint32_t k = first; k < last; ++k) {
+            const uint32_t c = inverse[k];
+            const int jj = code_column(c);
+            row += double(of_bias ? apply_code(__fmul_rn(g[jj], 0.5f), c) : head_std_term(g[jj], s, c));
+        }
+        acc[0] += row;
+    }
+    publish_loss_sums<1>(acc, scratch, partials + size_t(column) * gridDim.x, of_bias ? d_bias + i : d_std2 + i,
+                         ScaledLoss<1>{{1.0}});
+}
+
+// One block per column over the `blocks` partial sums its column's blocks left.
+__global__ __launch_bounds__(kBlock) void symmetric_head_columns_finalize_kernel(const double *__restrict__ partials, int blocks,
+                                                                                 float *__restrict__ d_bias, int bias_columns,
+                                                                                 float *__restrict__ d_std) {
+    __shared__ double scratch[kWavesPerBlock];
+    const int column = int(blockIdx.x);
+    float *out = column < bias_columns ? d_bias + column : d_std + (column - bias_columns);
+    finalize_loss_sums<1>(partials + size_t(column) * blocks, blocks, scratch, out, ScaledLoss<1>{{1.0}});
+}
+
+// The shape limits of the three entries (include/cusrl_hip.h): 0 invalid, 1 unsupported, 2 fine.
+inline int symmetric_head_shape(int64_t B, int64_t A) {
+    if (B < 0 || A <= 0) return 0;
+    if (A > CUSRL_MAX_SYMMETRIC_HEAD_ACTIONS || B > (int64_t(INT32_MAX) / 2) / A) return 1;
+    return 2;
+}
+
+inline int64_t elementwise_blocks(int64_t n) {
+    const int64_t want = ceil_div(n, kBlock);
+    return want > 4096 ? 4096 : want;
+}
+
 }  // namespace cusrl
 
 using namespace cusrl;
@@ -227,5 +375,61 @@ extern "C" int cusrl_symmetrize_mean_var(float *mean, float *var, const int32_t 
     if (C > CUSRL_MAX_SYMMETRIZE_CHANNELS) return CUSRL_E_UNSUPPORTED;
     hipLaunchKernelGGL(symmetrize_mean_var_kernel, dim3(1), dim3(kBlock), size_t(2 * C) * sizeof(float), as_stream(stream),
                        mean, var, reinterpret_cast<const uint32_t *>(table), int(C));
+    return launch_status();
+}
+
+extern "C" int cusrl_symmetric_head_fwd(const float *mean2, const float *std2, int std_vector, const int32_t *table, int64_t B,
+                                        int64_t A, float *mean_out, float *std_out, void *stream) {
+    const int shape = symmetric_head_shape(B, A);
+    if (shape == 0 || !table) return CUSRL_E_INVALID;
+    if (shape == 1) return CUSRL_E_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (!mean2 || !std2 || !mean_out || !std_out) return CUSRL_E_INVALID;
+    hipLaunchKernelGGL(symmetric_head_fwd_kernel, dim3(uint32_t(elementwise_blocks(B * A))), dim3(kBlock), 0, as_stream(stream),
+                       mean2, std2, std_vector, reinterpret_cast<const uint32_t *>(table), B, int(A), mean_out, std_out);
+    return launch_status();
+}
+
+extern "C" int cusrl_symmetric_head_sample(const float *mean2, const float *std2, int std_vector, const float *eps,
+                                           const int32_t *table, int64_t B, int64_t A, float *action, float *logp,
+                                           float *mean_out, float *std_out, void *stream) {
+    const int shape = symmetric_head_shape(B, A);
+    if (shape == 0 || !table) return CUSRL_E_INVALID;
+    if (shape == 1) return CUSRL_E_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (!mean2 || !std2 || !eps || !action || !logp || !mean_out || !std_out) return CUSRL_E_INVALID;
+    hipLaunchKernelGGL(symmetric_head_sample_kernel, dim3(uint32_t(ceil_div(B, kBlock))), dim3(kBlock), 0, as_stream(stream),
+                       mean2, std2, std_vector, eps, reinterpret_cast<const uint32_t *>(table), B, int(A), action, logp,
+                       mean_out, std_out);
+    return launch_status();
+}
+
+extern "C" int64_t cusrl_symmetric_head_num_partials(int64_t B, int64_t A) {
+    return symmetric_head_shape(B, A) == 2 ? 2 * A * loss_blocks(B) : 0;  // (the bias columns and a std vector's)
+}
+
+extern "C" int cusrl_symmetric_head_bwd(const float *g_mean, const float *g_std, const float *std2, int std_vector,
+                                        const int32_t *table, int64_t B, int64_t A, float *d_mean2, float *d_std2, float *d_bias,
+                                        double *partials, void *stream) {
+    const int shape = symmetric_head_shape(B, A);
+    if (shape == 0 || !table) return CUSRL_E_INVALID;
+    if (shape == 1) return CUSRL_E_UNSUPPORTED;
+    if (B == 0) return 0;  // (an empty tensor may have no storage)
+    if ((!g_mean && !g_std) || (g_mean && !d_mean2) || (g_std && (!std2 || !d_std2)) || (d_bias && !g_mean)) return CUSRL_E_INVALID;
+    const bool std_columns = g_std && std_vector;
+    const int64_t columns = (d_bias ? A : 0) + (std_columns ? A : 0);
+    if (columns && !partials) return CUSRL_E_INVALID;
+    // with column sums the grid's x extent is their block count; the element-wise part gets as many planes of it as its own
+    // block count asks for
+    const int64_t want = elementwise_blocks(B * A), blocks = columns ? loss_blocks(B) : want;
+    const int64_t planes = g_mean || (g_std && !std_vector) ? ceil_div(want, blocks) : 0;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(symmetric_head_bwd_kernel, dim3(uint32_t(blocks), uint32_t(planes + columns)), dim3(kBlock), 0, s, g_mean,
+                       g_std, std2, std_vector, reinterpret_cast<const uint32_t *>(table), B, int(A), int(planes), d_mean2, d_std2,
+                       d_bias, partials);
+    if (int rc = launch_status()) return rc;
+    if (!columns || blocks == 1) return 0;  // each column's one block finalised itself
+    hipLaunchKernelGGL(symmetric_head_columns_finalize_kernel, dim3(uint32_t(columns)), dim3(kBlock), 0, s, partials, int(blocks),
+                       d_bias, int(d_bias ? A : 0), d_std2);
     return launch_status();
 }

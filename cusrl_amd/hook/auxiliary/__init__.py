@@ -7,6 +7,9 @@ from cusrl_amd.hook.auxiliary.smoothness import ActionSmoothnessLoss
 from cusrl_amd.hook.auxiliary.symmetry import (
     MirrorDef,
     MirrorSymmetryLoss,
+    SymmetricActor,
+    SymmetricActorFactory,
+    SymmetricArchitecture,
     SymmetricDataAugmentation,
     TransitionMirroring,
 )
@@ -22,6 +25,9 @@ __all__ = [
     "ReturnPrediction",
     "StateEstimation",
     "StatePrediction",
+    "SymmetricActor",
+    "SymmetricActorFactory",
+    "SymmetricArchitecture",
     "SymmetricDataAugmentation",
     "TransitionMirroring",
 ]

@@ -15,7 +15,7 @@ import torch
 from torch import Tensor, distributions, nn
 from torch.nn.functional import one_hot
 
-from cusrl_amd.nn.module import LinearFp32, Module, ModuleFactory, disable_autocast
+from cusrl_amd.nn.module import LinearFp32, Module, ModuleFactory, disable_autocast, linear_act
 
 __all__ = ["AdaptiveNormalDist", "Distribution", "NormalDist", "OneHotCategoricalDist", "make_bijector"]
 
@@ -119,6 +119,17 @@ class _Normal(Distribution):
     """Diagonal Gaussian over ``{"mean", "std"}`` parameter dicts; reductions keep a trailing size-1 dim."""
 
     is_normal = True
+
+    def _mean(self, backbone_feat: Tensor, kwargs) -> Tensor:
+        """The mean head's output.  ``detach_mean_bias=True`` (SymmetricActor): the same values with the bias as a constant —
+        the caller differentiates the bias itself (its two halves cancel exactly only when they are added row by row)."""
+        head = self.mean_head
+        if not kwargs.get("detach_mean_bias") or head.bias is None:
+            return head(backbone_feat)
+        if not torch.is_autocast_enabled(backbone_feat.device.type) and backbone_feat.dtype == torch.float32:
+            return linear_act(backbone_feat, head.weight, head.bias.detach())
+        with disable_autocast(backbone_feat.device.type):
+            return torch.nn.functional.linear(backbone_feat.float(), head.weight.float(), head.bias.detach().float())
 
     @staticmethod
     def _ms(dist_params):
@@ -225,7 +236,7 @@ class NormalDist(_Normal):
         self.std = StddevVector(output_dim, init_std=init_std, bijector=bijector)
 
     def forward(self, backbone_feat: Tensor, **kwargs):
-        return {"mean": self.mean_head(backbone_feat), "std": self.std(backbone_feat)}
+        return {"mean": self._mean(backbone_feat, kwargs), "std": self.std(backbone_feat)}
 
     def std_vector(self) -> Tensor:
         """The fp32 ``[A]`` std behind the bijector, detached (what every row of the ``std`` parameter repeats)."""
@@ -285,7 +296,7 @@ class AdaptiveNormalDist(_Normal):
         self.std_head.bias.data[:] = self.bijector.inverse(_resolve_init_std(init_std))
 
     def forward(self, backbone_feat: Tensor, **kwargs):
-        mean = self.mean_head(backbone_feat)
+        mean = self._mean(backbone_feat, kwargs)
         std = self.std_head(backbone_feat if self.backward else backbone_feat.detach())
         with disable_autocast(std.device.type):
             return {"mean": mean, "std": self.bijector(std).float()}

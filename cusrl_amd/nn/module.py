@@ -191,7 +191,9 @@ class _WideBatchLinear(torch.autograd.Function):
                     grad_output.contiguous(), input, weight, need_input_grad=ctx.needs_input_grad[0], relu_input=fuse_relu,
                     defer=sink is not None)
                 grad_weight = _hand_over(sink, weight.data_ptr(), grad_weight)
-                grad_bias = _hand_over(sink, ctx.bias_key, grad_bias) if ctx.has_bias else None
+                # (a bias nobody differentiates here — SymmetricActor's head, whose bias gradient its combine computes — leaves
+                # nothing in the sink either: the sink is keyed by the parameter's address, not by who asked)
+                grad_bias = _hand_over(sink, ctx.bias_key, grad_bias) if ctx.has_bias and ctx.needs_input_grad[2] else None
                 if fuse_relu:
                     # The input is a ReLU output, so masking dX by (input > 0) here IS that ReLU's backward (it is
                     # idempotent, so the producer may safely repeat it).  Tell the producer — through the tensor it

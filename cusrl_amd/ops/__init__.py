@@ -56,5 +56,6 @@ from cusrl_amd.ops.rollout import (
     PendingStepEpilogue, categorical_sample_logp, episode_stats, normal_sample_logp, step_epilogue, synthetic_env_step,
 )
 from cusrl_amd.ops.symmetry import (
-    _mirror_table, _rows_2d, mirror_mse_fwd_bwd, mirror_rows, mirror_rows_bwd, symmetrize_mean_var_,
+    _mirror_table, _rows_2d, mirror_mse_fwd_bwd, mirror_rows, mirror_rows_bwd, symmetric_head_bwd, symmetric_head_fwd,
+    symmetric_head_sample, symmetric_head_supported, symmetrize_mean_var_,
 )

@@ -1,4 +1,5 @@
-"""Mirror symmetry: mirrored rows, their gradient, the symmetry loss and symmetric statistics (``csrc/symmetry.hip``)."""
+"""Mirror symmetry: mirrored rows, their gradient, the symmetry loss, symmetric statistics and the head of a symmetric actor
+(``csrc/symmetry.hip``)."""
 
 from __future__ import annotations
 
@@ -115,3 +116,81 @@ def symmetrize_mean_var_(mean: torch.Tensor, var: torch.Tensor, table: torch.Ten
     _checked.cusrl_symmetrize_mean_var(mean.data_ptr(), var.data_ptr(), table.data_ptr(), C, _stream())
     _modified_in_place(mean)
     _modified_in_place(var)
+
+
+def symmetric_head_supported(rows: int, actions: int) -> bool:
+    """The shape limits of the ``cusrl_symmetric_head_*`` entries (include/cusrl_hip.h) for ``rows`` combined rows."""
+    return 1 <= actions <= _native.MAX_SYMMETRIC_HEAD_ACTIONS and 0 <= 2 * rows * actions <= 2**31 - 1
+
+
+def _stacked_head(mean2: torch.Tensor, std2: torch.Tensor, table: torch.Tensor, who: str):
+    """``(mean2, std2, std is a vector, B, A)`` of the stacked head outputs: ``mean2 [2B, A]``, ``std2`` like it or ``[A]``."""
+    if mean2.dim() != 2 or mean2.shape[0] % 2:
+        raise ValueError(f"{who}: the stacked mean must be [2B, A], got {tuple(mean2.shape)}")
+    A = mean2.shape[1]
+    vector = std2.dim() == 1
+    if (std2.shape != (A,)) if vector else (std2.shape != mean2.shape):
+        raise ValueError(f"{who}: std must be [A] or shaped like the stacked mean, got {tuple(std2.shape)}")
+    _mirror_table(table, mean2.device, A, A)  # (the action mirror maps A columns onto A; checked before anything is launched)
+    return _f32(mean2, "mean2"), _f32(std2, "std2"), vector, mean2.shape[0] // 2, A
+
+
+def symmetric_head_fwd(mean2: torch.Tensor, std2: torch.Tensor, table: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(mean, std) [B, A]`` of a symmetric actor from the stacked head outputs (original rows first, mirrored rows second):
+    ``(mean_o + M(mean_m)) / 2`` and ``(std_o + |M(std_m)|) / 2``, one launch, bit-identical to the torch expression."""
+    mean2, std2, vector, B, A = _stacked_head(mean2, std2, table, "symmetric_head_fwd")
+    mean, std = (torch.empty(B, A, dtype=torch.float32, device=mean2.device) for _ in range(2))
+    _checked.cusrl_symmetric_head_fwd(mean2.data_ptr(), std2.data_ptr(), int(vector), table.data_ptr(), B, A, mean.data_ptr(),
+            std.data_ptr(), _stream())
+    return mean, std
+
+
+def symmetric_head_sample(mean2: torch.Tensor, std2: torch.Tensor, table: torch.Tensor, eps: torch.Tensor):
+    """The acting step behind the stacked pass, one launch: ``(action, logp [B, 1], mean, std)`` with ``action = mean + std * eps``
+    and the Normal log-probability of it summed over the action."""
+    mean2, std2, vector, B, A = _stacked_head(mean2, std2, table, "symmetric_head_sample")
+    eps = _f32(eps, "eps")
+    if eps.shape != (B, A):
+        raise ValueError(f"symmetric_head_sample: eps must be {(B, A)}, got {tuple(eps.shape)}")
+    action, mean, std = (torch.empty(B, A, dtype=torch.float32, device=mean2.device) for _ in range(3))
+    logp = torch.empty(B, 1, dtype=torch.float32, device=mean2.device)
+    _checked.cusrl_symmetric_head_sample(mean2.data_ptr(), std2.data_ptr(), int(vector), eps.data_ptr(), table.data_ptr(), B, A,
+            action.data_ptr(), logp.data_ptr(), mean.data_ptr(), std.data_ptr(), _stream())
+    return action, logp, mean, std
+
+
+def symmetric_head_bwd(g_mean: torch.Tensor | None, g_std: torch.Tensor | None, std2: torch.Tensor, table: torch.Tensor,
+                       want_bias: bool = False):
+    """Gradient of :func:`symmetric_head_fwd`: ``(d_mean2 [2B, A] | None, d_std2 shaped like std2 | None, d_bias [A] | None)``
+    from ``g_mean`` / ``g_std [B, A]`` (None: that gradient is not asked for).  ``want_bias``: also the gradient of a head bias
+    inside ``mean2`` (the column sums of ``d_mean2``, the two halves paired row by row: exactly 0 where they cancel).
+    Fixed-order sums, no atomics: the same bits every time."""
+    given = g_mean if g_mean is not None else g_std
+    if given is None:
+        raise ValueError("symmetric_head_bwd: neither gradient is given")
+    if given.dim() != 2 or any(g is not None and g.shape != given.shape for g in (g_mean, g_std)):
+        raise ValueError("symmetric_head_bwd: the incoming gradients must be [B, A]")
+    B, A = given.shape
+    vector = std2.dim() == 1
+    if (std2.shape != (A,)) if vector else (std2.shape != (2 * B, A)):
+        raise ValueError(f"symmetric_head_bwd: std must be [A] or [2B, A], got {tuple(std2.shape)}")
+    _mirror_table(table, given.device, A, A)
+    g_mean = None if g_mean is None else _f32(g_mean, "g_mean")
+    g_std = None if g_std is None else _f32(g_std, "g_std")
+    std2 = _f32(std2, "std2")
+    d_mean2 = None if g_mean is None else torch.empty(2 * B, A, dtype=torch.float32, device=given.device)
+    d_std2 = None if g_std is None else torch.empty_like(std2)
+    want_bias = want_bias and g_mean is not None
+    d_bias = torch.empty(A, dtype=torch.float32, device=given.device) if want_bias else None
+    partials = None
+    if want_bias or (vector and g_std is not None):
+        needed = _native.lib().cusrl_symmetric_head_num_partials(B, A)
+        partials = torch.empty(max(int(needed), 1), dtype=torch.float64, device=given.device)
+    _checked.cusrl_symmetric_head_bwd(_ptr(g_mean), _ptr(g_std), std2.data_ptr(), int(vector), table.data_ptr(), B, A,
+            _ptr(d_mean2), _ptr(d_std2), _ptr(d_bias), _ptr(partials), _stream())
+    if B == 0:  # (no rows: the launch is a no-op, the column sums are empty)
+        if vector and d_std2 is not None:
+            d_std2.zero_()
+        if d_bias is not None:
+            d_bias.zero_()
+    return d_mean2, d_std2, d_bias

@@ -218,9 +218,10 @@ class ActorCritic(Agent):
 
         self.hook = HookComposite(hooks)
         self.hook.pre_init(self)
-        self.actor: Actor = actor_factory(self.observation_dim, self.action_dim)
-        action_aware = getattr(critic_factory, "action_aware", False)
-        self.critic: Value = critic_factory(self.state_dim + self.action_dim * action_aware, self.value_dim)
+        # (the factories as `pre_init` left them: a hook may have replaced one — SymmetricArchitecture wraps the actor's)
+        self.actor: Actor = self.actor_factory(self.observation_dim, self.action_dim)
+        action_aware = getattr(self.critic_factory, "action_aware", False)
+        self.critic: Value = self.critic_factory(self.state_dim + self.action_dim * action_aware, self.value_dim)
         self.buffer = Buffer(self.buffer_capacity, self.parallelism, device=self.device)
         self.sampler = sampler
         self.grad_scaler = torch.GradScaler(device=self.device.type, enabled=self.grad_scaler_enabled)

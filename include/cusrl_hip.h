@@ -31,6 +31,7 @@ extern "C" {
 #define CUSRL_MAX_RECORD_BYTES 1024
 #define CUSRL_MAX_MIRROR_FIELDS 24 /* fields per cusrl_mirror_rows launch */
 #define CUSRL_MAX_SYMMETRIZE_CHANNELS 4096 /* channels of cusrl_symmetrize_mean_var (one workgroup, LDS-staged) */
+#define CUSRL_MAX_SYMMETRIC_HEAD_ACTIONS 64 /* widest action row of the cusrl_symmetric_head_* entries */
 
 #define CUSRL_E_INVALID (-1)     /* NULL pointer, negative size, inconsistent arguments */
 #define CUSRL_E_TOO_MANY (-2)    /* n_fields > CUSRL_MAX_FIELDS */
@@ -817,6 +818,39 @@ int64_t cusrl_mirror_mse_num_partials(int64_t n);
  * [C] (C_in == C_out == C <= CUSRL_MAX_SYMMETRIZE_CHANNELS), one rounding per operation in the reference's order:
  *   var = (var + |M(var)|) / 2 + (mean - M(mean))^2 / 4,  then  mean = (mean + M(mean)) / 2.  One workgroup. */
 int cusrl_symmetrize_mean_var(float *mean, float *var, const int32_t *table, int64_t C, void *stream);
+
+/* The head of a symmetric actor (SymmetricActor, symmetry.py:396-487; additive entries of ABI 7).  The wrapped actor ran ONCE
+ * over the stacked rows: mean2 [2B, A] contiguous, rows [0, B) for the observations and rows [B, 2B) for the mirrored
+ * observations; std2 is [2B, A] in the same layout (AdaptiveNormalDist) or, with std_vector != 0, the [A] vector NormalDist
+ * repeats, which is one row that is both halves.  `table`: the action mirror's table above for C_in == C_out == A;
+ * M = "gather by destination_indices, then flip the listed outputs".
+ * SHAPE LIMITS of all three: 1 <= A <= CUSRL_MAX_SYMMETRIC_HEAD_ACTIONS and 0 <= B with 2 B A <= INT32_MAX; outside them
+ * CUSRL_E_UNSUPPORTED (the host then evaluates the torch expression).  B == 0 launches nothing.
+ *
+ * cusrl_symmetric_head_fwd, ONE launch:  mean_out[b] = (mean_o[b] + M(mean_m[b])) / 2,  std_out[b] = (std_o[b] + |M(std_m[b])|) / 2,
+ * both [B, A]; one fp32 add, exact mirror and halving: bit-identical to the torch expression on the same operands.
+ *
+ * cusrl_symmetric_head_sample, ONE launch: the same combine, action = mean + std * eps (eps [B, A] from the caller, one fp32
+ * multiply and one add) and logp [B, 1] = the Normal log-probability of `action` summed over A (accumulated in fp64).
+ *
+ * cusrl_symmetric_head_bwd, ONE launch (+ the finalize below): from g_mean / g_std [B, A] (either may be NULL: that gradient
+ * is neither read nor written) the gradients of the stacked operands, d_mean2 [2B, A] and d_std2 ([2B, A], or [A] for a vector):
+ *   d_o[b, i] = g[b, i] / 2
+ *   d_m[b, i] = sum over the output columns j that read i, in increasing j, of sign_j * g[b, j] / 2   (0 when nobody reads i)
+ * and for the std every term times sgn(M(std_m)[b, j]), sgn(0) = 0 (torch's abs).  A std vector's gradient is the sum over b
+ * of d_o + d_m per column: fp64 partial sums per block in a fixed order, no atomics.  d_bias (optional, needs g_mean): [A], the
+ * gradient of the head's bias b when mean2 = raw2 + b and the head itself treats b as a constant — the same column sums for the
+ * mean, the two halves added ROW BY ROW, so that a column that mirrors onto itself with a flip gets exactly 0 as in the
+ * reference's two passes.  partials: double[cusrl_symmetric_head_num_partials(B, A)] (only read and written with column sums);
+ * beyond one block of rows per column a finalize launch of one block per column follows.  std2 is only read when g_std != NULL. */
+int cusrl_symmetric_head_fwd(const float *mean2, const float *std2, int std_vector, const int32_t *table, int64_t B, int64_t A,
+                             float *mean_out, float *std_out, void *stream);
+int cusrl_symmetric_head_sample(const float *mean2, const float *std2, int std_vector, const float *eps, const int32_t *table,
+                                int64_t B, int64_t A, float *action, float *logp, float *mean_out, float *std_out, void *stream);
+int cusrl_symmetric_head_bwd(const float *g_mean, const float *g_std, const float *std2, int std_vector, const int32_t *table,
+                             int64_t B, int64_t A, float *d_mean2, float *d_std2, float *d_bias, double *partials,
+                             void *stream);
+int64_t cusrl_symmetric_head_num_partials(int64_t B, int64_t A);
 
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
