@@ -9,7 +9,7 @@ from cusrl_amd import hook, nn, preset, sampler, template, testing, utils
 from cusrl_amd.hook import NextStatePrediction, PolicyDistillationLoss, ReturnPrediction, StateEstimation, StatePrediction
 from cusrl_amd.nn import (
     Actor, AdaptiveNormalDist, Distribution, GradientPenaltyLoss, Gru, L2RegularizationLoss, LinearFp32, Lstm, Mlp, Module,
-    ModuleFactory, NormalDist, NormalNllLoss, OneHotCategoricalDist, Rnn, RunningMeanStd, Value,
+    ModuleFactory, NormalDist, NormalNllLoss, OneHotCategoricalDist, Rnn, RunningMeanStd, Simba, SimbaBlock, SimbaFactory, Value,
 )
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
@@ -63,6 +63,9 @@ __all__ = [
     "Rnn",
     "RunningMeanStd",
     "Sampler",
+    "Simba",
+    "SimbaBlock",
+    "SimbaFactory",
     "StateEstimation",
     "StatePrediction",
     "TemporalMiniBatchSampler",

@@ -104,6 +104,7 @@ MAX_PACKED = _CONSTANTS["MAX_PACKED"]
 MAX_MIRROR_FIELDS = _CONSTANTS["MAX_MIRROR_FIELDS"]
 MAX_SYMMETRIZE_CHANNELS = _CONSTANTS["MAX_SYMMETRIZE_CHANNELS"]
 MAX_SYMMETRIC_HEAD_ACTIONS = _CONSTANTS["MAX_SYMMETRIC_HEAD_ACTIONS"]
+MAX_LAYER_NORM_WIDTH = _CONSTANTS["MAX_LAYER_NORM_WIDTH"]
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
 

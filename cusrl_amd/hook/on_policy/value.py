@@ -195,6 +195,15 @@ class ValueComputation(Hook):
         k = counter.wait()
         if k == 0:
             return
+        if not getattr(getattr(critic, "backbone", None), "batch_invariant", True):
+            # a backbone whose no-grad pass gives a row other bits when other rows share its batch (Module.batch_invariant)
+            # bootstraps exactly its k rows, as the host-driven pass does: the host knows k here, and the padded bucket
+            # below would put the rows through library GEMMs chosen for another row count
+            (rows,) = ops.gather_rows([next_state], slots[:k], T, N)
+            with autocast():
+                bootstrap = critic.evaluate(rows)
+            ops.scatter_rows(bootstrap.float(), slots[:k], next_value)
+            return
         bucket = scratch.get("bucket", 0)
         if k > bucket:  # capacities only grow, with headroom: a count hovering around a power of two must not re-capture
             bucket = scratch["bucket"] = min(max(self._MIN_BUCKET, 1 << (2 * k - 1).bit_length()), T * N)

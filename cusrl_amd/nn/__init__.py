@@ -4,6 +4,7 @@ from cusrl_amd.nn.loss import L2RegularizationLoss, NormalNllLoss
 from cusrl_amd.nn.module import LinearFp32, Mlp, Module, ModuleFactory
 from cusrl_amd.nn.rms import RunningMeanStd
 from cusrl_amd.nn.rnn import Gru, Lstm, Rnn
+from cusrl_amd.nn.simba import Simba, SimbaBlock, SimbaFactory
 
 __all__ = [
     "Actor",
@@ -22,6 +23,9 @@ __all__ = [
     "Lstm",
     "Rnn",
     "RunningMeanStd",
+    "Simba",
+    "SimbaBlock",
+    "SimbaFactory",
     "Value",
 ]
 

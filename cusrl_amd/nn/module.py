@@ -323,6 +323,9 @@ class Module(nn.Module):
     (module/module.py:35-163)."""
 
     Factory = ModuleFactory
+    # Does a no-grad pass give a row the same bits whatever other rows share its batch?  The replayed value bootstrap
+    # (hook/on_policy/value.py) evaluates a padded bucket of rows only then; a module that says False gets exactly its rows.
+    batch_invariant = True
 
     def __init__(self, input_dim: int | None = None, output_dim: int | None = None, is_recurrent: bool = False,
                  like: "Module | None" = None, intermediate_repr: dict[str, Any] | None = None):

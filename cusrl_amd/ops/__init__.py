@@ -39,6 +39,7 @@ from cusrl_amd.ops.gradient import (
     grad_sumsq, sum_slabs,
 )
 from cusrl_amd.ops.graph import graph_census, graph_replace_memsets
+from cusrl_amd.ops.layer_norm import AddLayerNorm, add_layer_norm, add_layer_norm_bwd, add_layer_norm_fwd, add_layer_norm_supported
 from cusrl_amd.ops.loss import (
     LOSS_DEFER, DeferredLoss, _optional_rows, categorical_policy_stats, categorical_terms_bwd, categorical_terms_fwd, policy_stats,
     policy_terms_bwd, policy_terms_fwd, ppo_loss_accepts_std_vector, ppo_loss_categorical_fwd_bwd, ppo_loss_fwd_bwd,

@@ -852,6 +852,34 @@ int cusrl_symmetric_head_bwd(const float *g_mean, const float *g_std, const floa
                              void *stream);
 int64_t cusrl_symmetric_head_num_partials(int64_t B, int64_t A);
 
+/* ---- residual add + LayerNorm — the row-wise work of cusrl/nn/module/simba.py:28-73 (`input + block(input)`, nn.LayerNorm)
+ * (additive entries of ABI 7; csrc/layer_norm.hip).  Every residual add of a pre-LayerNorm backbone is followed by a LayerNorm
+ * (the next block's, or the final one), so the two are one pass over the row.  x, residual, sum_out, y, dy, ds, s, d_s: [B, H]
+ * contiguous fp32; gamma, beta, d_gamma, d_beta: [H]; mean, rstd: fp32 [B].  1 <= H <= CUSRL_MAX_LAYER_NORM_WIDTH (a row is at
+ * most 16 values per lane of the wavefront that owns it), any B >= 0 (B == 0 launches nothing); CUSRL_E_UNSUPPORTED outside.
+ * Pointers need 4-byte alignment only: 16-byte aligned operands with H % 4 == 0 move as 16-byte accesses, anything else as
+ * 4-byte accesses, with the same lane-to-column assignment and therefore the same bits.  No atomics: the same bits every run.
+ *
+ * cusrl_add_layer_norm_fwd, ONE launch, one wavefront per row, the row read once:
+ *   s = x + residual (one fp32 add, torch's bits), stored to sum_out;  residual == NULL: s = x, sum_out is not written;
+ *   y = (s - mean) * rstd * gamma + beta with torch's statistics: mean and the biased variance of the row accumulated in
+ *   float64 in two passes over the register-resident row, rstd = 1 / sqrt(var + eps), each rounded to fp32 once;
+ *   mean / rstd (both or neither): the statistics for the backward, NULL in passes nobody differentiates.
+ *
+ * cusrl_add_layer_norm_bwd, ONE launch (+ a one-block finalize when more than one block ran):
+ *   d_s = rstd * (g - mean_H(g) - xhat * mean_H(g * xhat)) + ds,  g = dy * gamma,  xhat = (s - mean) * rstd;
+ *   ds (optional): the gradient that reaches s directly (the residual path behind this LayerNorm).  d_s is the gradient of
+ *   x and of residual alike.  d_gamma = sum_rows dy * xhat, d_beta = sum_rows dy: float64 column sums per block, laid down in
+ *   `partials` (double[cusrl_add_layer_norm_num_partials(B, H)], 0 when one block does it all: may be NULL then) and summed in
+ *   block order by the finalize; the grid is capped (256 blocks) so that this stays one block's work. */
+#define CUSRL_MAX_LAYER_NORM_WIDTH 1024
+int cusrl_add_layer_norm_fwd(const float *x, const float *residual, const float *gamma, const float *beta, float eps,
+                             float *sum_out, float *y, float *mean, float *rstd, int64_t B, int64_t H, void *stream);
+int cusrl_add_layer_norm_bwd(const float *dy, const float *ds, const float *s, const float *mean, const float *rstd,
+                             const float *gamma, float *d_s, float *d_gamma, float *d_beta, double *partials, int64_t B,
+                             int64_t H, void *stream);
+int64_t cusrl_add_layer_norm_num_partials(int64_t B, int64_t H);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
