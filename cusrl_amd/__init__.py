@@ -8,8 +8,9 @@ gather, PPO objective forward+backward) runs as hand-written HIP kernels for gfx
 from cusrl_amd import hook, nn, preset, sampler, template, testing, utils
 from cusrl_amd.hook import NextStatePrediction, PolicyDistillationLoss, ReturnPrediction, StateEstimation, StatePrediction
 from cusrl_amd.nn import (
-    Actor, AdaptiveNormalDist, Distribution, GradientPenaltyLoss, Gru, L2RegularizationLoss, LinearFp32, Lstm, Mlp, Module,
-    ModuleFactory, NormalDist, NormalNllLoss, OneHotCategoricalDist, Rnn, RunningMeanStd, Simba, SimbaBlock, SimbaFactory, Value,
+    Actor, AdaptiveNormalDist, Denormalization, DenormalizationFactory, Distribution, GradientPenaltyLoss, Gru, L2RegularizationLoss,
+    LinearFp32, Lstm, Mlp, Module, ModuleFactory, NormalDist, NormalNllLoss, Normalization, NormalizationFactory,
+    OneHotCategoricalDist, Rnn, RunningMeanStd, Sequential, SequentialFactory, Simba, SimbaBlock, SimbaFactory, Value,
 )
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
@@ -39,6 +40,8 @@ __all__ = [
     "AutoMiniBatchSampler",
     "AutoRandomSampler",
     "Buffer",
+    "Denormalization",
+    "DenormalizationFactory",
     "Distribution",
     "Environment",
     "EnvironmentSpec",
@@ -55,6 +58,8 @@ __all__ = [
     "NextStatePrediction",
     "NormalDist",
     "NormalNllLoss",
+    "Normalization",
+    "NormalizationFactory",
     "OneHotCategoricalDist",
     "OptimizerFactory",
     "PolicyDistillationLoss",
@@ -63,6 +68,8 @@ __all__ = [
     "Rnn",
     "RunningMeanStd",
     "Sampler",
+    "Sequential",
+    "SequentialFactory",
     "Simba",
     "SimbaBlock",
     "SimbaFactory",

@@ -2,13 +2,17 @@ from cusrl_amd.nn.actor import Actor, Value
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
 from cusrl_amd.nn.loss import L2RegularizationLoss, NormalNllLoss
 from cusrl_amd.nn.module import LinearFp32, Mlp, Module, ModuleFactory
+from cusrl_amd.nn.normalization import Denormalization, DenormalizationFactory, Normalization, NormalizationFactory
 from cusrl_amd.nn.rms import RunningMeanStd
 from cusrl_amd.nn.rnn import Gru, Lstm, Rnn
+from cusrl_amd.nn.sequential import Sequential, SequentialFactory
 from cusrl_amd.nn.simba import Simba, SimbaBlock, SimbaFactory
 
 __all__ = [
     "Actor",
     "AdaptiveNormalDist",
+    "Denormalization",
+    "DenormalizationFactory",
     "Distribution",
     "GradientPenaltyLoss",
     "L2RegularizationLoss",
@@ -21,8 +25,12 @@ __all__ = [
     "OneHotCategoricalDist",
     "Gru",
     "Lstm",
+    "Normalization",
+    "NormalizationFactory",
     "Rnn",
     "RunningMeanStd",
+    "Sequential",
+    "SequentialFactory",
     "Simba",
     "SimbaBlock",
     "SimbaFactory",

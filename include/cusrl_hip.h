@@ -880,6 +880,23 @@ int cusrl_add_layer_norm_bwd(const float *dy, const float *ds, const float *s, c
                              int64_t H, void *stream);
 int64_t cusrl_add_layer_norm_num_partials(int64_t B, int64_t H);
 
+/* ---- per-column affine map with fixed statistics — `Normalization.forward` cusrl/nn/module/normalization.py:52 and
+ * `Denormalization.forward` :89, the layers at the two ends of a `Sequential` backbone (additive entries of ABI 7;
+ * csrc/column_affine.hip).  x, out, dy, dx: [rows, C] contiguous fp32; mean, std: [C].  ONE launch each; 4-byte aligned
+ * pointers work (16-byte lanes when C % 4 == 0 and every pointer is 16-byte aligned, 4-byte lanes otherwise: the same bits).
+ * out may be x and dx may be dy.  rows == 0 launches nothing and writes nothing.  CUSRL_E_INVALID: a NULL pointer, rows < 0,
+ * C < 1, inverse outside {0, 1}; CUSRL_E_UNSUPPORTED: C > INT32_MAX or rows * C beyond int64.
+ *
+ * cusrl_column_affine_fwd — each step one correctly rounded fp32 operation, i.e. torch's bits for the reference's expression:
+ *   inverse == 0 (normalization.py:52): out[r, c] = (x[r, c] - mean[c]) / std[c]   a subtraction, then a DIVISION (no reciprocal)
+ *   inverse == 1 (normalization.py:89): out[r, c] = x[r, c] * std[c] + mean[c]     a multiplication, then an addition (no fma)
+ * cusrl_column_affine_bwd — what torch's autograd gives for those expressions; mean and std are not trainable in the
+ * reference (`requires_grad=False`), so there is no column reduction:
+ *   inverse == 0 (normalization.py:52): dx = dy / std          inverse == 1 (normalization.py:89): dx = dy * std */
+int cusrl_column_affine_fwd(const float *x, const float *mean, const float *std, float *out, int64_t rows, int64_t C,
+                            int inverse, void *stream);
+int cusrl_column_affine_bwd(const float *dy, const float *std, float *dx, int64_t rows, int64_t C, int inverse, void *stream);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
