@@ -223,6 +223,17 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
     hstate, hout, hprev, dh, dout = f(N, Hs), f(N, Hs), f(N, Hs), f(N, Hs), f(N, Hs)
     rows.measure(f"gru gates fwd [B,256] (B={N})", lambda: ops.gru_gates_forward(gi, gh, bh, hstate, hout, None, 0), N * Hs * 36)
     rows.measure(f"gru gates bwd [B,256] (B={N})", lambda: ops.gru_gates_backward(gi, gh, bh, hprev, dout, dh, None, 0), N * Hs * 64)
+    if ops.gru_bias_partials_supported(Hs, gi, gh, bh, hprev, dout, dh):  # + one [4H] partial row per block of rows
+        partials = torch.empty(ops.gru_bias_partial_rows(N), 4 * Hs, device=DEV)
+        rows.measure(f"gru gates bwd + bias sums [B,256] (B={N})",
+                     lambda: ops.gru_gates_backward(gi, gh, bh, hprev, dout, dh, None, 0, partials), N * Hs * 64 + partials.numel() * 4)
+    else:
+        print(f"gru gates bwd + bias sums [B,256] (B={N}): skipped, the library does not fold the bias sums at this width and option")
+    # the LSTM time step (the default recurrent core): training forward (c_saved given, `pre` stored over gi) and backward
+    pre, gh4, bh4, cstate, csaved, dc = f(N, 4 * Hs), f(N, 4 * Hs), f(4 * Hs), f(N, Hs), f(N, Hs), f(N, Hs)
+    rows.measure(f"lstm gates fwd [B,256] (B={N})", lambda: ops.lstm_gates_forward(pre, gh4, bh4, hstate, cstate, hout, csaved, None, 0),
+                 N * Hs * 68)
+    rows.measure(f"lstm gates bwd [B,256] (B={N})", lambda: ops.lstm_gates_backward(pre, hprev, csaved, dout, dh, dc, None, 0), N * Hs * 56)
     logits3, race3 = f(N, 3), torch.rand(N, 3, device=DEV) + 0.1
     rows.measure(f"categorical sample + logp [B,3] (B={N})", lambda: ops.categorical_sample_logp(logits3, race3), N * (3 * 12 + 4))
 

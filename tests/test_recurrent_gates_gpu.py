@@ -5,6 +5,7 @@ those of tests/_recurrent_gates.py; tests/test_recurrent_gates.py runs the same 
 assertions without a GPU.  Bounds (the project's standing ones): forward 1e-5 relative + 2e-6; every gradient tensor 1e-5 of its
 largest entry (``gradient_parity``); saturated cases finite and within 1e-5 * max(1, largest entry); ended rows bitwise."""
 
+import dataclasses
 import zlib
 
 import numpy as np
@@ -236,6 +237,29 @@ def test_bias_folding_pass_against_float64(ops, option, rows, gradient_parity):
     assert cases
     for case in cases:
         G.exercise(case, Device(ops, offset=_scalar_offset(case) if case.form == "scalar" else None), gradient_parity)
+
+
+@pytest.mark.parametrize("form,H", [("vec", 64), ("scalar", 16)])
+def test_plain_and_bias_folding_backward_give_the_same_bits(ops, form, H):
+    """``gru_gates_backward`` on the same operands with and without ``bias_partials``: two kernels, one backward row — ``gi``,
+    ``gh`` and ``dh`` bit for bit.  B = 17 under the default 16 rows per block: one full block and a block that owns a single
+    row; 16-byte lanes at H = 64, scalars at H = 16 with ``dh`` one float off alignment; lengths that end rows (NaN in what
+    an ended row may not read), with and without ``b_hh`` and ``d_out``."""
+    from cusrl_amd import _native
+
+    B, entries = 17, ("cusrl_gru_gates_bwd", "cusrl_gru_gates_bwd_bias")
+    offset = "dh" if form == "scalar" else None
+    for b_hh in (True, False):
+        for d_out in (True, False):
+            plain = G.Case(f"gru/same_bits_{form}_b{int(b_hh)}d{int(d_out)}/B{B}H{H}", "gru", B, H, lengths="mixed", garbage=True,
+                           b_hh=b_hh, d_out=d_out, form=form)
+            operands = G.backward_operands(G.inputs(plain))
+            before = [_native.launch_counts.get(name, 0) for name in entries]
+            alone = Device(ops, offset).backward(plain, operands)
+            folded = Device(ops, offset).backward(dataclasses.replace(plain, rows=16), operands)
+            assert [_native.launch_counts.get(name, 0) for name in entries] == [count + 1 for count in before]
+            for name in ("gi", "gh", "dh"):
+                assert G.same_bits(alone[name], folded[name]), (plain.name, name)
 
 
 @pytest.mark.parametrize("rows,H", [(32, 32), (8, 128), (4, 256)])
