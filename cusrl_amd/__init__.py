@@ -12,6 +12,10 @@ from cusrl_amd.nn import (
     LinearFp32, Lstm, Mlp, Module, ModuleFactory, NormalDist, NormalNllLoss, Normalization, NormalizationFactory,
     OneHotCategoricalDist, Rnn, RunningMeanStd, Sequential, SequentialFactory, Simba, SimbaBlock, SimbaFactory, Value,
 )
+from cusrl_amd.nn import (
+    FeedForward, Gate, GeGlu, GruGate, HighwayGate, InputGate, OutputGate, PassthroughGate, ResidualGate, SigmoidTanhGate, SwiGlu,
+    get_gate_cls,
+)
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
 )
@@ -90,4 +94,16 @@ __all__ = [
     "template",
     "testing",
     "utils",
+    "FeedForward",
+    "Gate",
+    "GeGlu",
+    "GruGate",
+    "HighwayGate",
+    "InputGate",
+    "OutputGate",
+    "PassthroughGate",
+    "ResidualGate",
+    "SigmoidTanhGate",
+    "SwiGlu",
+    "get_gate_cls",
 ]

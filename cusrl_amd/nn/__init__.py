@@ -1,5 +1,10 @@
 from cusrl_amd.nn.actor import Actor, Value
+from cusrl_amd.nn.activation import GeGlu, SwiGlu
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
+from cusrl_amd.nn.feedforward import FeedForward
+from cusrl_amd.nn.gate import (
+    Gate, GruGate, HighwayGate, InputGate, OutputGate, PassthroughGate, ResidualGate, SigmoidTanhGate, gate_map, get_gate_cls,
+)
 from cusrl_amd.nn.loss import L2RegularizationLoss, NormalNllLoss
 from cusrl_amd.nn.module import LinearFp32, Mlp, Module, ModuleFactory
 from cusrl_amd.nn.normalization import Denormalization, DenormalizationFactory, Normalization, NormalizationFactory
@@ -35,6 +40,19 @@ __all__ = [
     "SimbaBlock",
     "SimbaFactory",
     "Value",
+    "FeedForward",
+    "Gate",
+    "GeGlu",
+    "GruGate",
+    "HighwayGate",
+    "InputGate",
+    "OutputGate",
+    "PassthroughGate",
+    "ResidualGate",
+    "SigmoidTanhGate",
+    "SwiGlu",
+    "get_gate_cls",
+    "gate_map",
 ]
 
 

@@ -35,6 +35,7 @@ from cusrl_amd.ops.buffer import (
     HostCounter, RecordPack, _row_elems, assign_rows, buffer_push, compact_flags, gather_rows, gather_rows_packed, make_push_table,
     push_table, scatter_rows, splice_rows, window_indices,
 )
+from cusrl_amd.ops.gate import GateCombine, Glu, gate_backward, gate_combine, gate_supported, glu, glu_backward, glu_supported
 from cusrl_amd.ops.gradient import (
     DeferredColumns, adam_norm_workspace, adam_step, adam_step_normed, adam_step_window, assemble_gradients, clip_grad_norm_,
     grad_sumsq, sum_slabs,

@@ -897,6 +897,54 @@ int cusrl_column_affine_fwd(const float *x, const float *mean, const float *std,
                             int inverse, void *stream);
 int cusrl_column_affine_bwd(const float *dy, const float *std, float *dx, int64_t rows, int64_t C, int inverse, void *stream);
 
+/* ---- gates and GLU activations — the element-wise work between the GEMMs of cusrl/nn/layer/gate.py:36-136 and
+ * cusrl/nn/layer/activation.py:7-26 (additive entries of ABI 7; csrc/gate.hip).  Every operand is [rows, C] contiguous fp32
+ * (the GLU input and its gradient [rows, 2 H]).  ONE launch each; the launch shape of cusrl_column_affine_*: 4-byte aligned
+ * pointers work (16-byte lanes when C % 4 == 0 — H % 4 == 0 for the GLU — and every non-NULL pointer is 16-byte aligned,
+ * 4-byte lanes otherwise: the same bits), grid capped with a stride over the rest, 64-bit element indices.  rows == 0 launches
+ * nothing and writes nothing.  No output may alias an input or another output.  CUSRL_E_INVALID: a NULL pointer among the
+ * operands the kind uses (listed below), rows < 0, C < 1, an unknown kind; CUSRL_E_UNSUPPORTED: C > INT32_MAX or the element
+ * count beyond int64.  An operand the kind does not use is never read or written and may be NULL.
+ *
+ * s(v) = 1 / (1 + expf(-v)), t(v) = tanhf(v), one rounded fp32 operation per step (no fma).  p and q are PRE-activations, bias
+ * included (the outputs of the gate's linear layers); p2 / q2 (each NULL or present) are second addends, P = p + p2 and
+ * Q = q + q2 in that order, so that `r_y(y) + r_x(x)` (gate.py:130-134) needs no add launch of its own.
+ *
+ *   kind            cusrl_gate_fwd: out =               uses        cusrl_gate_bwd, from dout (g = s(P), h = t(Q))       reads / writes
+ *   GATE_INPUT      g x + y                 (:47-48)    x y p       dx = dout g, dp = dout x g (1 - g)                   x p / dx dp
+ *   GATE_OUTPUT     x + g y                 (:63-64)    x y p       dy = dout g, dp = dout y g (1 - g)                   y p / dy dp
+ *   GATE_HIGHWAY    g x + (1 - g) y         (:80-81)    x y p       dx = dout g, dy = dout (1 - g), dp = dout (x - y) g (1 - g)   x y p / dx dy dp
+ *   GATE_SIGMOID_TANH  x + g h              (:97-99)    x p q       dp = dout h g (1 - g), dq = dout g (1 - h h)         p q / dp dq
+ *   GATE_GRU_RESET  g x                     (:130,134)  x p         dx = dout g, dp = dout x g (1 - g)                   x p / dx dp
+ *   GATE_GRU_OUT    (1 - g) x + g h         (:132-136)  x p q       dx = dout (1 - g), dp = dout (h - x) g (1 - g), dq = dout g (1 - h h)   x p q / dx dp dq
+ * The gradient of an operand that enters `out` as itself (y of INPUT; x of OUTPUT and SIGMOID_TANH) is dout and is not written;
+ * dp is the gradient of p and of p2 alike, dq of q and q2.  The backward recomputes g and h from the pre-activations: no
+ * activation is saved.  Its 1 - g, g (1 - g) and 1 - h h are evaluated without the cancellation of the fp32 differences, as
+ * e / (1 + e), e / (1 + e)^2 with e = expf(-|P|) and 4 u / (1 + u)^2 with u = expf(-2 |Q|), so that a gradient tensor keeps
+ * 1e-5 of its largest entry even when that entry sits at |P| = 8.  A saturated pre-activation gives g in {0, 1} or h in
+ * {-1, 1} exactly, a finite `out`, and g (1 - g) or 1 - h h EXACTLY zero there (the fp32 forward is constant); nothing divides
+ * by a quantity that can vanish.
+ *
+ * cusrl_glu_fwd: out[r, c] = a act(b) with a = input[r, c], b = input[r, H + c], the halves read in place;
+ *   GLU_GEGLU (:13-15): act(b) = b Phi(b), Phi(b) = erfcf(-b / sqrt 2) / 2 — the exact (erf) GELU, torch's default;
+ *   GLU_SWIGLU (:24-26): act(b) = b s(b).
+ * cusrl_glu_bwd writes both halves of dinput [rows, 2 H]: dinput[r, c] = dout act(b), dinput[r, H + c] = dout a act'(b);
+ *   GELU' = Phi(b) + b phi(b), phi(b) = expf(-b b / 2) / sqrt(2 pi);  SiLU' = s + b s (1 - s). */
+#define CUSRL_GATE_INPUT 0
+#define CUSRL_GATE_OUTPUT 1
+#define CUSRL_GATE_HIGHWAY 2
+#define CUSRL_GATE_SIGMOID_TANH 3
+#define CUSRL_GATE_GRU_RESET 4
+#define CUSRL_GATE_GRU_OUT 5
+#define CUSRL_GLU_GEGLU 0
+#define CUSRL_GLU_SWIGLU 1
+int cusrl_gate_fwd(int kind, const float *x, const float *y, const float *p, const float *p2, const float *q, const float *q2,
+                   float *out, int64_t rows, int64_t C, void *stream);
+int cusrl_gate_bwd(int kind, const float *x, const float *y, const float *p, const float *p2, const float *q, const float *q2,
+                   const float *dout, float *dx, float *dy, float *dp, float *dq, int64_t rows, int64_t C, void *stream);
+int cusrl_glu_fwd(int kind, const float *input, float *out, int64_t rows, int64_t H, void *stream);
+int cusrl_glu_bwd(int kind, const float *input, const float *dout, float *dinput, int64_t rows, int64_t H, void *stream);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the

@@ -237,6 +237,23 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
     logits3, race3 = f(N, 3), torch.rand(N, 3, device=DEV) + 0.1
     rows.measure(f"categorical sample + logp [B,3] (B={N})", lambda: ops.categorical_sample_logp(logits3, race3), N * (3 * 12 + 4))
 
+    # ---- gates and GLU activations (csrc/gate.hip) over a [N, 256] latent: the two launches of a GruGate (both with their
+    # second addends), a HighwayGate, and the GLUs on a [N, 2 x 256] feed-forward activation.  The launches themselves, as the
+    # other rows (no autograd inside the captured region).  Bytes: operands read + results written, in floats per element
+    Hg = 256
+    gx, gy, gp, gp2, gq, gq2, gd = (f(N, Hg) for _ in range(7))
+    for kind, (y_, q_, q2_), fwd_floats, bwd_floats in (("highway", (gy, None, None), 4, 7), ("gru_reset", (None, None, None), 4, 6),
+                                                        ("gru_out", (None, gq, gq2), 6, 9)):
+        p2_ = None if kind == "highway" else gp2
+        rows.measure(f"gate {kind} fwd [B,{Hg}] (B={N})",
+                     lambda kind=kind, y_=y_, q_=q_, p2_=p2_, q2_=q2_: ops.gate_combine(kind, gx, y_, gp, q_, p2_, q2_), N * Hg * 4 * fwd_floats)
+        rows.measure(f"gate {kind} bwd [B,{Hg}] (B={N})",
+                     lambda kind=kind, y_=y_, q_=q_, p2_=p2_, q2_=q2_: ops.gate_backward(kind, gx, y_, gp, q_, p2_, q2_, gd), N * Hg * 4 * bwd_floats)
+    glu_in = f(N, 2 * Hg)
+    for kind in ("geglu", "swiglu"):
+        rows.measure(f"glu {kind} fwd [B,2x{Hg}] (B={N})", lambda kind=kind: ops.glu(kind, glu_in), N * Hg * 12)
+        rows.measure(f"glu {kind} bwd [B,2x{Hg}] (B={N})", lambda kind=kind: ops.glu_backward(kind, glu_in, gd), N * Hg * 20)
+
     # ---- observation sanitiser (ObservationNanToNum): one [N, obs] observation.  Clean input is read and never written (4 B per
     # element, store on change); torch's in-place op reads and rewrites it (8 B).  All-NaN input is written back whole (8 B): it
     # has to be refilled before every launch, so the refill is timed with it and alone — subtract.
