@@ -16,6 +16,10 @@ from cusrl_amd.nn import (
     FeedForward, Gate, GeGlu, GruGate, HighwayGate, InputGate, OutputGate, PassthroughGate, ResidualGate, SigmoidTanhGate, SwiGlu,
     get_gate_cls,
 )
+from cusrl_amd.nn import (
+    MultiheadAttention, MultiheadCrossAttention, MultiheadSelfAttention, RotaryEmbedding, TransformerDecoderLayer,
+    TransformerEncoderLayer, make_norm,
+)
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
 )
@@ -106,4 +110,11 @@ __all__ = [
     "SigmoidTanhGate",
     "SwiGlu",
     "get_gate_cls",
+    "MultiheadAttention",
+    "MultiheadCrossAttention",
+    "MultiheadSelfAttention",
+    "RotaryEmbedding",
+    "TransformerDecoderLayer",
+    "TransformerEncoderLayer",
+    "make_norm",
 ]

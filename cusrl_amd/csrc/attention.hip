@@ -1,0 +1,463 @@
+// Scaled dot-product attention, forward and backward, and the rotary embedding ("Attention"): what
+// cusrl/nn/layer/mha.py hands to F.scaled_dot_product_attention and cusrl/nn/layer/encoding.py:112-125, with the scores never
+// written to memory.  Formulas, layouts and error codes: include/cusrl_hip.h.
+//
+// One body shape for the three attention kernels.  A workgroup of 256 threads owns kOwn = 16 rows of one (batch, head) and
+// streams the other side in tiles of kTile = 32; 16 lanes share a row.  Per tile: (a) lane g of row r computes the scores of
+// r against tile entries g and g + 16 as ordered fmaf chains over the head dimension out of LDS, (b) the row's statistics go
+// round its 16 lanes by xor shuffles, (c) the probabilities (or dS) cross LDS once, (d) lane g accumulates columns g, g + 16,
+// ... of the row's output as ordered fmaf chains over the tile.  Rows are queries in the forward and in the dQ pass (keys
+// stream), keys in the dK / dV pass (queries stream): every output element has exactly one owner, which adds its terms in
+// index order — no atomics, no sums across workgroups, the same bits on every call.  The products are VALU fmaf chains, not
+// MFMA: the tiles a 16-lane row group needs are narrower than an MFMA fragment, and the layers this serves are short
+// sequences of small heads.
+//
+// LDS rows are padded to an odd stride (head_dim | 1): lanes that walk different rows at one column hit different banks.
+// The region is dynamic and nothing static sits in front of it.
+#include <math.h>
+
+#include "common.hpp"
+
+namespace cusrl {
+namespace {
+
+constexpr int kOwn = 16;    // rows a workgroup owns
+constexpr int kTile = 32;   // rows of the streamed side per step
+constexpr int kGroup = 16;  // lanes per owned row (kOwn * kGroup == kBlock)
+constexpr int kPerLane = kTile / kGroup;                    // scores per lane and tile
+constexpr int kAcc = CUSRL_MAX_SDPA_HEAD_DIM / kGroup;      // output columns per lane
+constexpr int64_t kSdpaMaxBlocks = 1 << 16;                 // the grid strides over what is left
+static_assert(kOwn * kGroup == kBlock, "one lane group per owned row");
+
+struct Rows {  // [N, L, H, D] with element (n, l, h, d) at p + n * sn + l * sl + h * D + d
+    const float *p;
+    int64_t sn, sl;
+};
+
+struct Mask {  // element strides (n, h, q, k) of the keep-mask or of the bias; at most one of the two is present
+    const uint8_t *keep;
+    const float *bias;
+    int64_t sn, sh, sq, sk;
+    int causal;
+};
+
+struct Shape {
+    int64_t N, H, Lq, Lk;
+    int D;
+    float scale;
+};
+
+__device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+    for (int off = kGroup / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kGroup));
+    return v;
+}
+
+__device__ __forceinline__ float group_sum(float v) {  // (a + b on both partners: every lane ends with the same bits)
+#pragma unroll
+    for (int off = kGroup / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kGroup);
+    return v;
+}
+
+// `rows` rows of a tensor starting at l0 into dst[r * ld + c]; rows at or past L are zeros.
+template <int kWidth>
+__device__ __forceinline__ void load_rows(float *dst, int ld, const Rows &t, int64_t n, int64_t h, int64_t l0, int rows, int64_t L,
+                                          int D) {
+    const int per_row = D / kWidth;
+    const float *base = t.p + n * t.sn + h * D;
+    for (int i = threadIdx.x; i < rows * per_row; i += kBlock) {
+        const int r = i / per_row, c = (i - r * per_row) * kWidth;
+        float v[kWidth];
+#pragma unroll
+        for (int k = 0; k < kWidth; ++k) v[k] = 0.0f;
+        if (l0 + r < L) {
+            const float *src = base + (l0 + r) * t.sl + c;
+            if constexpr (kWidth == 4) {
+                const float4 q = *reinterpret_cast<const float4 *>(src);
+                v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+            } else {
+                v[0] = *src;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kWidth; ++k) dst[r * ld + c + k] = v[k];
+    }
+}
+
+__device__ __forceinline__ float dot(const float *a, const float *b, int D) {
+    float s = 0.0f;
+    for (int d = 0; d < D; ++d) s = fmaf(a[d], b[d], s);
+    return s;
+}
+
+// scale * (q . k) + bias, or -inf where query i must not see key j.  i < Lq and j < Lk.
+__device__ __forceinline__ float visible_score(const Mask &m, float qk, float scale, int64_t n, int64_t h, int64_t i, int64_t j) {
+    if (m.causal && j > i) return -INFINITY;
+    float s = qk * scale;
+    if (m.keep || m.bias) {
+        const int64_t at = n * m.sn + h * m.sh + i * m.sq + j * m.sk;
+        if (m.keep && !m.keep[at]) return -INFINITY;
+        if (m.bias) s = s + m.bias[at];
+    }
+    return s;
+}
+
+// exp(s - lse) for a visible score of a row with a visible key, exactly 0 otherwise (never exp(-inf - (-inf))).
+__device__ __forceinline__ float probability(float s, float lse) { return (s == -INFINITY || lse == -INFINITY) ? 0.0f : expf(s - lse); }
+
+// Store a lane's output columns of one owned row: dst row `row` of a contiguous [N, L, H, D] tensor.
+__device__ __forceinline__ void store_columns(float *dst, const float (&acc)[kAcc], int g, int D) {
+#pragma unroll
+    for (int e = 0; e < kAcc; ++e)
+        if (g + e * kGroup < D) dst[g + e * kGroup] = acc[e];
+}
+
+// ------------------------------------------------------------------------------------------------------------ forward
+template <int kWidth>
+__global__ __launch_bounds__(kBlock) void sdpa_fwd_kernel(Rows q, Rows k, Rows v, Mask mask, float *out, float *lse, Shape s,
+                                                          int64_t q_tiles, int64_t items) {
+    extern __shared__ float lds[];
+    const int D = s.D, ld = D | 1;
+    float *sq = lds, *sk = sq + kOwn * ld, *sv = sk + kTile * ld, *sp = sv + kTile * ld;  // sp: [kOwn][kTile]
+    const int r = threadIdx.x / kGroup, g = threadIdx.x % kGroup;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t tile = item % q_tiles, nh = item / q_tiles, h = nh % s.H, n = nh / s.H;
+        const int64_t q0 = tile * kOwn, i = q0 + r;
+        load_rows<kWidth>(sq, ld, q, n, h, q0, kOwn, s.Lq, D);
+        float m = -INFINITY, l = 0.0f, acc[kAcc];
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc[e] = 0.0f;
+        // (top-left causal: keys past the tile's last query are masked for every row of it)
+        const int64_t k_end = mask.causal ? min(s.Lk, q0 + kOwn) : s.Lk;
+        for (int64_t k0 = 0; k0 < k_end; k0 += kTile) {
+            __syncthreads();  // the previous tile's readers are done (and sq is not being written over a reader)
+            load_rows<kWidth>(sk, ld, k, n, h, k0, kTile, s.Lk, D);
+            load_rows<kWidth>(sv, ld, v, n, h, k0, kTile, s.Lk, D);
+            __syncthreads();
+            float score[kPerLane], top = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < kPerLane; ++c) {
+                const int64_t j = k0 + g + c * kGroup;
+                score[c] = (i < s.Lq && j < s.Lk) ? visible_score(mask, dot(sq + r * ld, sk + (g + c * kGroup) * ld, D), s.scale, n, h, i, j)
+                                                  : -INFINITY;
+                top = fmaxf(top, score[c]);
+            }
+            const float m_new = fmaxf(m, group_max(top));
+            float alpha = 1.0f, part = 0.0f;
+            if (m_new != -INFINITY) {  // (a row that has seen no key yet keeps m = -inf, l = 0 and p = 0)
+                alpha = (m == -INFINITY) ? 0.0f : expf(m - m_new);
+#pragma unroll
+                for (int c = 0; c < kPerLane; ++c) {
+                    const float p = (score[c] == -INFINITY) ? 0.0f : expf(score[c] - m_new);
+                    sp[r * kTile + g + c * kGroup] = p;
+                    part += p;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < kPerLane; ++c) sp[r * kTile + g + c * kGroup] = 0.0f;
+            }
+            l = l * alpha + group_sum(part);
+            m = m_new;
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) {
+                const int d = g + e * kGroup;
+                if (d < D) {
+                    float a = acc[e] * alpha;
+                    for (int j = 0; j < kTile; ++j) a = fmaf(sp[r * kTile + j], sv[j * ld + d], a);
+                    acc[e] = a;
+                }
+            }
+        }
+        if (i < s.Lq) {
+            const float inv = l > 0.0f ? 1.0f / l : 0.0f;  // a row with every key masked: zeros and lse = -inf
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) acc[e] = acc[e] * inv;
+            store_columns(out + ((n * s.Lq + i) * s.H + h) * D, acc, g, D);
+            if (g == 0) lse[(n * s.H + h) * s.Lq + i] = l > 0.0f ? m + logf(l) : -INFINITY;
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------- backward, query-major: dQ
+// Owns 16 queries; also lays down delta[n, h, i] = sum_d dout * out for the key-major pass that follows on the stream.
+template <int kWidth>
+__global__ __launch_bounds__(kBlock) void sdpa_bwd_dq_kernel(Rows q, Rows k, Rows v, Rows o, Rows dout, const float *lse, Mask mask,
+                                                             float *dq, float *delta, Shape s, int64_t q_tiles, int64_t items) {
+    extern __shared__ float lds[];
+    const int D = s.D, ld = D | 1;
+    float *sq = lds, *sdo = sq + kOwn * ld, *sk = sdo + kOwn * ld, *sv = sk + kTile * ld, *sds = sv + kTile * ld;  // sds: [kOwn][kTile]
+    const int r = threadIdx.x / kGroup, g = threadIdx.x % kGroup;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t tile = item % q_tiles, nh = item / q_tiles, h = nh % s.H, n = nh / s.H;
+        const int64_t q0 = tile * kOwn, i = q0 + r;
+        load_rows<kWidth>(sq, ld, q, n, h, q0, kOwn, s.Lq, D);
+        load_rows<kWidth>(sdo, ld, dout, n, h, q0, kOwn, s.Lq, D);
+        load_rows<kWidth>(sk, ld, o, n, h, q0, kOwn, s.Lq, D);  // (out passes through the key tile's place once)
+        __syncthreads();
+        float part = 0.0f;
+        for (int d = g; d < D; d += kGroup) part = fmaf(sdo[r * ld + d], sk[r * ld + d], part);
+        const float row_delta = group_sum(part);
+        const float row_lse = i < s.Lq ? lse[(n * s.H + h) * s.Lq + i] : -INFINITY;
+        if (i < s.Lq && g == 0) delta[(n * s.H + h) * s.Lq + i] = row_delta;
+        float acc[kAcc];
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc[e] = 0.0f;
+        const int64_t k_end = mask.causal ? min(s.Lk, q0 + kOwn) : s.Lk;
+        for (int64_t k0 = 0; k0 < k_end; k0 += kTile) {
+            __syncthreads();
+            load_rows<kWidth>(sk, ld, k, n, h, k0, kTile, s.Lk, D);
+            load_rows<kWidth>(sv, ld, v, n, h, k0, kTile, s.Lk, D);
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < kPerLane; ++c) {
+                const int t = g + c * kGroup;
+                const int64_t j = k0 + t;
+                float ds = 0.0f;
+                if (i < s.Lq && j < s.Lk) {
+                    const float sc = visible_score(mask, dot(sq + r * ld, sk + t * ld, D), s.scale, n, h, i, j);
+                    const float p = probability(sc, row_lse);
+                    if (p != 0.0f) ds = p * (dot(sdo + r * ld, sv + t * ld, D) - row_delta) * s.scale;
+                }
+                sds[r * kTile + t] = ds;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) {
+                const int d = g + e * kGroup;
+                if (d < D) {
+                    float a = acc[e];
+                    for (int j = 0; j < kTile; ++j) a = fmaf(sds[r * kTile + j], sk[j * ld + d], a);
+                    acc[e] = a;
+                }
+            }
+        }
+        if (i < s.Lq) store_columns(dq + ((n * s.Lq + i) * s.H + h) * D, acc, g, D);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------- backward, key-major: dK and dV
+// Owns 16 keys; streams the queries with their dout, lse and delta.
+template <int kWidth>
+__global__ __launch_bounds__(kBlock) void sdpa_bwd_dkv_kernel(Rows q, Rows k, Rows v, Rows dout, const float *lse, const float *delta,
+                                                              Mask mask, float *dk, float *dv, Shape s, int64_t k_tiles, int64_t items) {
+    extern __shared__ float lds[];
+    const int D = s.D, ld = D | 1;
+    float *sk = lds, *sv = sk + kOwn * ld, *sq = sv + kOwn * ld, *sdo = sq + kTile * ld;
+    float *sp = sdo + kTile * ld, *sds = sp + kOwn * kTile, *slse = sds + kOwn * kTile, *sdelta = slse + kTile;  // sp, sds: [kOwn][kTile]
+    const int r = threadIdx.x / kGroup, g = threadIdx.x % kGroup;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t tile = item % k_tiles, nh = item / k_tiles, h = nh % s.H, n = nh / s.H;
+        const int64_t k0 = tile * kOwn, j = k0 + r;
+        load_rows<kWidth>(sk, ld, k, n, h, k0, kOwn, s.Lk, D);
+        load_rows<kWidth>(sv, ld, v, n, h, k0, kOwn, s.Lk, D);
+        float acc_k[kAcc], acc_v[kAcc];
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc_k[e] = acc_v[e] = 0.0f;
+        // (top-left causal: queries in front of the tile's first key see none of its keys)
+        const int64_t q_begin = mask.causal ? k0 / kTile * kTile : 0;
+        for (int64_t q0 = q_begin; q0 < s.Lq; q0 += kTile) {
+            __syncthreads();
+            load_rows<kWidth>(sq, ld, q, n, h, q0, kTile, s.Lq, D);
+            load_rows<kWidth>(sdo, ld, dout, n, h, q0, kTile, s.Lq, D);
+            if (threadIdx.x < kTile) {
+                const int64_t i = q0 + threadIdx.x;
+                slse[threadIdx.x] = i < s.Lq ? lse[(n * s.H + h) * s.Lq + i] : -INFINITY;
+                sdelta[threadIdx.x] = i < s.Lq ? delta[(n * s.H + h) * s.Lq + i] : 0.0f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < kPerLane; ++c) {
+                const int t = g + c * kGroup;
+                const int64_t i = q0 + t;
+                float p = 0.0f, ds = 0.0f;
+                if (i < s.Lq && j < s.Lk) {
+                    const float sc = visible_score(mask, dot(sq + t * ld, sk + r * ld, D), s.scale, n, h, i, j);
+                    p = probability(sc, slse[t]);
+                    if (p != 0.0f) ds = p * (dot(sdo + t * ld, sv + r * ld, D) - sdelta[t]) * s.scale;
+                }
+                sp[r * kTile + t] = p;
+                sds[r * kTile + t] = ds;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) {
+                const int d = g + e * kGroup;
+                if (d < D) {
+                    float a = acc_v[e], b = acc_k[e];
+                    for (int t = 0; t < kTile; ++t) {
+                        a = fmaf(sp[r * kTile + t], sdo[t * ld + d], a);
+                        b = fmaf(sds[r * kTile + t], sq[t * ld + d], b);
+                    }
+                    acc_v[e] = a, acc_k[e] = b;
+                }
+            }
+        }
+        if (j < s.Lk) {
+            store_columns(dk + ((n * s.Lk + j) * s.H + h) * D, acc_k, g, D);
+            store_columns(dv + ((n * s.Lk + j) * s.H + h) * D, acc_v, g, D);
+        }
+        __syncthreads();
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------- host
+bool rows_vectorise(const Rows &t, int D) { return D % 4 == 0 && aligned(t.p, 16) && t.sn % 4 == 0 && t.sl % 4 == 0; }
+
+bool sizes_fit(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {  // every contiguous extent within int64
+    const int64_t L = Lq > Lk ? Lq : Lk;
+    if (H > INT64_MAX / D) return false;
+    if (L > INT64_MAX / (H * D)) return false;
+    return N == 0 || L * H * D <= INT64_MAX / N;
+}
+
+uint32_t grid_for(int64_t items) { return uint32_t(items < kSdpaMaxBlocks ? items : kSdpaMaxBlocks); }
+
+size_t lds_bytes(int rows, int extra, int D) { return (size_t(rows) * (D | 1) + extra) * sizeof(float); }
+
+bool valid_sizes(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {
+    return N >= 0 && H >= 1 && Lq >= 1 && Lk >= 1 && D >= 1 && D <= CUSRL_MAX_SDPA_HEAD_DIM;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- RoPE
+// One lane per kWidth adjacent pairs (x[d], x[d + D / 2]) of one (n, l, h).
+template <int kWidth, bool kTranspose>
+__global__ __launch_bounds__(kBlock) void rope_kernel(const float *x, int64_t sn, int64_t sl, const float *cos_rows, const float *sin_rows,
+                                                      float *out, int64_t L, int64_t H, int half, int64_t lanes) {
+    const int per_head = half / kWidth;
+    const int64_t stride = int64_t(gridDim.x) * kBlock;
+    for (int64_t at = int64_t(blockIdx.x) * kBlock + threadIdx.x; at < lanes; at += stride) {
+        const int c = int(at % per_head) * kWidth;
+        const int64_t nlh = at / per_head, h = nlh % H, nl = nlh / H, l = nl % L, n = nl / L;
+        const float *src = x + n * sn + l * sl + h * (2 * half) + c;
+        float *dst = out + nlh * (2 * half) + c;
+        float a[kWidth], b[kWidth], co[kWidth], si[kWidth];
+        if constexpr (kWidth == 4) {
+            const float4 va = *reinterpret_cast<const float4 *>(src), vb = *reinterpret_cast<const float4 *>(src + half);
+            const float4 vc = *reinterpret_cast<const float4 *>(cos_rows + l * half + c), vs = *reinterpret_cast<const float4 *>(sin_rows + l * half + c);
+            a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w, b[0] = vb.x, b[1] = vb.y, b[2] = vb.z, b[3] = vb.w;
+            co[0] = vc.x, co[1] = vc.y, co[2] = vc.z, co[3] = vc.w, si[0] = vs.x, si[1] = vs.y, si[2] = vs.z, si[3] = vs.w;
+        } else {
+            a[0] = src[0], b[0] = src[half], co[0] = cos_rows[l * half + c], si[0] = sin_rows[l * half + c];
+        }
+        float first[kWidth], second[kWidth];
+#pragma unroll
+        for (int k = 0; k < kWidth; ++k) {
+            if (kTranspose) {
+                first[k] = a[k] * co[k] + b[k] * si[k];
+                second[k] = b[k] * co[k] - a[k] * si[k];
+            } else {
+                first[k] = a[k] * co[k] + (-b[k]) * si[k];  // x cos + rotate_half(x) sin, as the reference rounds it
+                second[k] = b[k] * co[k] + a[k] * si[k];
+            }
+        }
+        if constexpr (kWidth == 4) {
+            *reinterpret_cast<float4 *>(dst) = make_float4(first[0], first[1], first[2], first[3]);
+            *reinterpret_cast<float4 *>(dst + half) = make_float4(second[0], second[1], second[2], second[3]);
+        } else {
+            dst[0] = first[0], dst[half] = second[0];
+        }
+    }
+}
+
+}  // namespace
+}  // namespace cusrl
+
+using namespace cusrl;
+
+extern "C" int cusrl_sdpa_fwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                              int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *keep_mask,
+                              const float *bias, int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q,
+                              int64_t mask_stride_k, int causal, float scale, float *out, float *lse, int64_t N, int64_t H, int64_t Lq,
+                              int64_t Lk, int64_t D, void *stream) {
+    if (!q || !k || !v || !out || !lse || (keep_mask && bias) || !valid_sizes(N, H, Lq, Lk, D)) return CUSRL_E_INVALID;
+    if (!sizes_fit(N, H, Lq, Lk, D)) return CUSRL_E_UNSUPPORTED;
+    if (N == 0) return 0;
+    const Rows rq{q, q_stride_n, q_stride_l}, rk{k, k_stride_n, k_stride_l}, rv{v, v_stride_n, v_stride_l};
+    const Mask mask{keep_mask, bias, mask_stride_n, mask_stride_h, mask_stride_q, mask_stride_k, causal != 0};
+    const Shape shape{N, H, Lq, Lk, int(D), scale};
+    const int64_t q_tiles = ceil_div(Lq, kOwn);
+    if (N * H > INT64_MAX / q_tiles) return CUSRL_E_UNSUPPORTED;
+    const int64_t items = N * H * q_tiles;
+    const dim3 grid{grid_for(items)}, block{kBlock};
+    const size_t lds = lds_bytes(kOwn + 2 * kTile, kOwn * kTile, int(D));
+    if (rows_vectorise(rq, int(D)) && rows_vectorise(rk, int(D)) && rows_vectorise(rv, int(D)))
+        hipLaunchKernelGGL((sdpa_fwd_kernel<4>), grid, block, lds, as_stream(stream), rq, rk, rv, mask, out, lse, shape, q_tiles, items);
+    else
+        hipLaunchKernelGGL((sdpa_fwd_kernel<1>), grid, block, lds, as_stream(stream), rq, rk, rv, mask, out, lse, shape, q_tiles, items);
+    return launch_status();
+}
+
+extern "C" int64_t cusrl_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {
+    if (!valid_sizes(N, H, Lq, Lk, D) || !sizes_fit(N, H, Lq, Lk, D)) return -1;
+    return N * H * Lq;  // delta, one fp32 per query row and head
+}
+
+extern "C" int cusrl_sdpa_bwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                              int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const float *out,
+                              const float *lse, const float *dout, int64_t dout_stride_n, int64_t dout_stride_l,
+                              const uint8_t *keep_mask, const float *bias, int64_t mask_stride_n, int64_t mask_stride_h,
+                              int64_t mask_stride_q, int64_t mask_stride_k, int causal, float scale, float *dq, float *dk, float *dv,
+                              float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D, void *stream) {
+    if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || (keep_mask && bias) || !valid_sizes(N, H, Lq, Lk, D))
+        return CUSRL_E_INVALID;
+    if (!sizes_fit(N, H, Lq, Lk, D)) return CUSRL_E_UNSUPPORTED;
+    if (N == 0) return 0;
+    if (!workspace) return CUSRL_E_INVALID;
+    const Rows rq{q, q_stride_n, q_stride_l}, rk{k, k_stride_n, k_stride_l}, rv{v, v_stride_n, v_stride_l};
+    const Rows ro{out, Lq * H * D, H * D}, rdo{dout, dout_stride_n, dout_stride_l};
+    const Mask mask{keep_mask, bias, mask_stride_n, mask_stride_h, mask_stride_q, mask_stride_k, causal != 0};
+    const Shape shape{N, H, Lq, Lk, int(D), scale};
+    const int64_t q_tiles = ceil_div(Lq, kOwn), k_tiles = ceil_div(Lk, kOwn);
+    if (N * H > INT64_MAX / q_tiles || N * H > INT64_MAX / k_tiles) return CUSRL_E_UNSUPPORTED;
+    const bool vec = rows_vectorise(rq, int(D)) && rows_vectorise(rk, int(D)) && rows_vectorise(rv, int(D)) &&
+                     rows_vectorise(ro, int(D)) && rows_vectorise(rdo, int(D));
+    const dim3 block{kBlock};
+    {
+        const int64_t items = N * H * q_tiles;
+        const dim3 grid{grid_for(items)};
+        const size_t lds = lds_bytes(2 * kOwn + 2 * kTile, kOwn * kTile, int(D));
+        if (vec)
+            hipLaunchKernelGGL((sdpa_bwd_dq_kernel<4>), grid, block, lds, as_stream(stream), rq, rk, rv, ro, rdo, lse, mask, dq, workspace,
+                               shape, q_tiles, items);
+        else
+            hipLaunchKernelGGL((sdpa_bwd_dq_kernel<1>), grid, block, lds, as_stream(stream), rq, rk, rv, ro, rdo, lse, mask, dq, workspace,
+                               shape, q_tiles, items);
+        if (const int status = launch_status()) return status;
+    }
+    const int64_t items = N * H * k_tiles;
+    const dim3 grid{grid_for(items)};
+    const size_t lds = lds_bytes(2 * kOwn + 2 * kTile, 2 * kOwn * kTile + 2 * kTile, int(D));
+    if (vec)
+        hipLaunchKernelGGL((sdpa_bwd_dkv_kernel<4>), grid, block, lds, as_stream(stream), rq, rk, rv, rdo, lse, workspace, mask, dk, dv,
+                           shape, k_tiles, items);
+    else
+        hipLaunchKernelGGL((sdpa_bwd_dkv_kernel<1>), grid, block, lds, as_stream(stream), rq, rk, rv, rdo, lse, workspace, mask, dk, dv,
+                           shape, k_tiles, items);
+    return launch_status();
+}
+
+extern "C" int cusrl_rope_apply(const float *x, int64_t x_stride_n, int64_t x_stride_l, const float *cos_rows, const float *sin_rows,
+                                float *out, int64_t N, int64_t L, int64_t H, int64_t D, int transpose, void *stream) {
+    if (!x || !cos_rows || !sin_rows || !out || N < 0 || L < 1 || H < 1 || D < 2 || D % 2 || (transpose != 0 && transpose != 1))
+        return CUSRL_E_INVALID;
+    if (D > INT32_MAX || !sizes_fit(N, H, L, L, D)) return CUSRL_E_UNSUPPORTED;
+    if (N == 0) return 0;
+    const int half = int(D / 2);
+    const bool vec = half % 4 == 0 && aligned(x, 16) && aligned(cos_rows, 16) && aligned(sin_rows, 16) && aligned(out, 16) &&
+                     x_stride_n % 4 == 0 && x_stride_l % 4 == 0;
+    const int64_t lanes = N * L * H * (half / (vec ? 4 : 1));
+    int64_t blocks = ceil_div(lanes, kBlock);
+    if (blocks > 2048) blocks = 2048;
+    const dim3 grid{uint32_t(blocks)}, block{kBlock};
+#define CUSRL_ROPE_LAUNCH(W, T) \
+    hipLaunchKernelGGL((rope_kernel<W, T>), grid, block, 0, as_stream(stream), x, x_stride_n, x_stride_l, cos_rows, sin_rows, out, L, H, half, lanes)
+    if (vec && transpose) CUSRL_ROPE_LAUNCH(4, true);
+    else if (vec) CUSRL_ROPE_LAUNCH(4, false);
+    else if (transpose) CUSRL_ROPE_LAUNCH(1, true);
+    else CUSRL_ROPE_LAUNCH(1, false);
+#undef CUSRL_ROPE_LAUNCH
+    return launch_status();
+}

@@ -1,6 +1,8 @@
 from cusrl_amd.nn.actor import Actor, Value
 from cusrl_amd.nn.activation import GeGlu, SwiGlu
+from cusrl_amd.nn.attention import MultiheadAttention, MultiheadCrossAttention, MultiheadSelfAttention, make_norm
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
+from cusrl_amd.nn.encoding import RotaryEmbedding
 from cusrl_amd.nn.feedforward import FeedForward
 from cusrl_amd.nn.gate import (
     Gate, GruGate, HighwayGate, InputGate, OutputGate, PassthroughGate, ResidualGate, SigmoidTanhGate, gate_map, get_gate_cls,
@@ -12,6 +14,7 @@ from cusrl_amd.nn.rms import RunningMeanStd
 from cusrl_amd.nn.rnn import Gru, Lstm, Rnn
 from cusrl_amd.nn.sequential import Sequential, SequentialFactory
 from cusrl_amd.nn.simba import Simba, SimbaBlock, SimbaFactory
+from cusrl_amd.nn.transformer import TransformerDecoderLayer, TransformerEncoderLayer
 
 __all__ = [
     "Actor",
@@ -53,6 +56,13 @@ __all__ = [
     "SwiGlu",
     "get_gate_cls",
     "gate_map",
+    "MultiheadAttention",
+    "MultiheadCrossAttention",
+    "MultiheadSelfAttention",
+    "RotaryEmbedding",
+    "TransformerDecoderLayer",
+    "TransformerEncoderLayer",
+    "make_norm",
 ]
 
 

@@ -945,6 +945,56 @@ int cusrl_gate_bwd(int kind, const float *x, const float *y, const float *p, con
 int cusrl_glu_fwd(int kind, const float *input, float *out, int64_t rows, int64_t H, void *stream);
 int cusrl_glu_bwd(int kind, const float *input, const float *dout, float *dinput, int64_t rows, int64_t H, void *stream);
 
+/* ---- scaled dot-product attention and the rotary embedding — what cusrl/nn/layer/mha.py:133-140 hands to
+ * F.scaled_dot_product_attention, and cusrl/nn/layer/encoding.py:107-125 (additive entries of ABI 7; csrc/attention.hip).
+ * fp32 throughout; the [N, H, Lq, Lk] scores are never written to memory.
+ *
+ * Layout: q [N, Lq, H, D], k and v [N, Lk, H, D] with element (n, l, h, d) at base + n * stride_n + l * stride_l + h * D + d
+ * (strides in elements, per tensor): the slices of a packed [N, L, 3, H, D] or [N, L, 2, H, D] projection and a
+ * batch_first=False transposition are read where they are.  dout is read the same way.  out, dq [N, Lq, H, D] and dk, dv
+ * [N, Lk, H, D] are written contiguous; lse is [N, H, Lq].  A lane moves 16 bytes where D % 4 == 0 and every strided base is
+ * 16-byte aligned with strides that are multiples of 4, and 4 bytes otherwise: the same arithmetic per element, the same bits.
+ *
+ * Masks: `causal` (top-left aligned: key j is visible to query i iff j <= i, whatever Lq and Lk), OR-ed with at most one of
+ * keep_mask (uint8, nonzero = attend) and bias (fp32, added to the scaled score; -inf = a masked key), either read at
+ * n * mask_stride_n + h * mask_stride_h + i * mask_stride_q + j * mask_stride_k (element strides; 0 for a broadcast dimension).
+ *
+ * cusrl_sdpa_fwd, ONE launch:  s_ij = scale * sum_d q_id k_jd (+ bias_ij), -inf where masked;
+ *   out_i = sum_j softmax_j(s_i.) v_j  by online softmax over key tiles;  lse_i = ln sum_j exp(s_ij) (the row maximum included).
+ * cusrl_sdpa_bwd, TWO launches on the stream (query-major, then key-major), from q, k, v, out, lse, dout:
+ *   p_ij = exp(s_ij - lse_i),  delta_i = sum_d dout_id out_id,  ds_ij = p_ij (sum_d dout_id v_jd - delta_i) scale;
+ *   dq_i = sum_j ds_ij k_j (the query-major pass, which also writes delta into `workspace`);
+ *   dk_j = sum_i ds_ij q_i,  dv_j = sum_i p_ij dout_i (the key-major pass).
+ *   workspace: float[cusrl_sdpa_bwd_workspace(N, H, Lq, Lk, D)] (-1 for sizes the entries refuse).
+ * Every output element has one owning lane that adds its terms in index order: no atomics, the same bits on every call.
+ * A query row with every key masked: out_i = 0, lse_i = -inf, p_i. = 0 exactly, so it adds exactly zero to dq, dk and dv;
+ * exp(-inf - (-inf)) is never evaluated and nothing is NaN.
+ *
+ * 1 <= D <= CUSRL_MAX_SDPA_HEAD_DIM; H, Lq, Lk >= 1 otherwise unbounded (64-bit indices, the key tiles loop); N == 0 is a
+ * successful no-op.  CUSRL_E_INVALID, nothing launched: a NULL operand the call needs (the masks are optional), a negative
+ * size, H, Lq or Lk < 1, D out of range, keep_mask and bias together.  CUSRL_E_UNSUPPORTED: an extent beyond int64.
+ *
+ * cusrl_rope_apply, ONE launch: x [N, L, H, D] read at n * x_stride_n + l * x_stride_l + h * D + d, out [N, L, H, D]
+ * contiguous, cos_rows / sin_rows [L, D / 2] contiguous (the cache rows offset .. offset + L), D even.  With x = (x1, x2) the
+ * two halves of the last dimension and c, s the row l of cos_rows, sin_rows:
+ *   transpose == 0 (encoding.py:112-125, x cos + rotate_half(x) sin):  out = (x1 c + (-x2) s,  x2 c + x1 s)
+ *   transpose == 1 (its backward, dx = dout cos - rotate_half(dout sin)):  out = (x1 c + x2 s,  x2 c - x1 s)
+ * CUSRL_E_INVALID: a NULL pointer, N < 0, L or H < 1, D < 2 or odd, transpose outside {0, 1}. */
+#define CUSRL_MAX_SDPA_HEAD_DIM 128
+int cusrl_sdpa_fwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n, int64_t k_stride_l,
+                   const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *keep_mask, const float *bias,
+                   int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q, int64_t mask_stride_k, int causal,
+                   float scale, float *out, float *lse, int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D, void *stream);
+int cusrl_sdpa_bwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n, int64_t k_stride_l,
+                   const float *v, int64_t v_stride_n, int64_t v_stride_l, const float *out, const float *lse, const float *dout,
+                   int64_t dout_stride_n, int64_t dout_stride_l, const uint8_t *keep_mask, const float *bias,
+                   int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q, int64_t mask_stride_k, int causal,
+                   float scale, float *dq, float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t Lk,
+                   int64_t D, void *stream);
+int64_t cusrl_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D);
+int cusrl_rope_apply(const float *x, int64_t x_stride_n, int64_t x_stride_l, const float *cos_rows, const float *sin_rows,
+                     float *out, int64_t N, int64_t L, int64_t H, int64_t D, int transpose, void *stream);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the

@@ -254,6 +254,25 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
         rows.measure(f"glu {kind} fwd [B,2x{Hg}] (B={N})", lambda kind=kind: ops.glu(kind, glu_in), N * Hg * 12)
         rows.measure(f"glu {kind} bwd [B,2x{Hg}] (B={N})", lambda kind=kind: ops.glu_backward(kind, glu_in, gd), N * Hg * 20)
 
+    # ---- attention (csrc/attention.hip): N / 16 sequences of 16 tokens, 4 heads of 16 — the three entries through the ops' launch
+    # functions (no autograd), q / k / v read as the slices of a packed [Na, 16, 3, 4, 16] projection; beside them torch's SDPA on
+    # the transposed views of the same tensors, same run.  Bytes: operands read + results written
+    from cusrl_amd.ops.attention import _launch_rope, _launch_sdpa_fwd
+
+    Na, La, Ha, Da = max(N // 16, 1), 16, 4, 16
+    aq, ak, av = f(Na, La, 3, Ha, Da).unbind(dim=2)
+    adout = f(Na, La, Ha, Da)
+    aout, alse = _launch_sdpa_fwd(aq, ak, av, None, True)
+    tokens = Na * La * Ha * Da * 4
+    rows.measure(f"sdpa fwd causal [B,{La},{Ha},{Da}] (B={Na})", lambda: _launch_sdpa_fwd(aq, ak, av, None, True), 4 * tokens + Na * Ha * La * 4)
+    rows.measure(f"sdpa bwd causal [B,{La},{Ha},{Da}] (B={Na})", lambda: ops.sdpa_backward(aq, ak, av, aout, alse, adout, None, True),
+                 8 * tokens + Na * Ha * La * 12)
+    rows.measure(f"torch sdpa fwd causal [B,{La},{Ha},{Da}] (B={Na})",
+                 lambda: torch.nn.functional.scaled_dot_product_attention(aq.transpose(1, 2), ak.transpose(1, 2), av.transpose(1, 2), is_causal=True),
+                 4 * tokens)
+    acos, asin = f(La, Da // 2), f(La, Da // 2)
+    rows.measure(f"rope apply [B,{La},{Ha},{Da}] (B={Na})", lambda: _launch_rope(aq, acos, asin, False), 2 * tokens)
+
     # ---- observation sanitiser (ObservationNanToNum): one [N, obs] observation.  Clean input is read and never written (4 B per
     # element, store on change); torch's in-place op reads and rewrites it (8 B).  All-NaN input is written back whole (8 B): it
     # has to be refilled before every launch, so the refill is timed with it and alone — subtract.
