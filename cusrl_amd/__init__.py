@@ -20,6 +20,7 @@ from cusrl_amd.nn import (
     MultiheadAttention, MultiheadCrossAttention, MultiheadSelfAttention, RotaryEmbedding, TransformerDecoderLayer,
     TransformerEncoderLayer, make_norm,
 )
+from cusrl_amd.nn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
 )
@@ -117,4 +118,8 @@ __all__ = [
     "TransformerDecoderLayer",
     "TransformerEncoderLayer",
     "make_norm",
+    "CausalMultiheadSelfAttention",
+    "CausalTransformerEncoderLayer",
+    "compute_segment_ids",
+    "get_alibi_slopes",
 ]

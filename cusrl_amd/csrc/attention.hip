@@ -461,3 +461,378 @@ extern "C" int cusrl_rope_apply(const float *x, int64_t x_stride_n, int64_t x_st
 #undef CUSRL_ROPE_LAUNCH
     return launch_status();
 }
+
+// ================================================================================================ band (sliding window)
+// Causal sliding-window attention ("Causal sliding-window attention"; cusrl/nn/module/causal_attn.py:135-258 with
+// cusrl/nn/utils/attention.py:117-124, 158-159 in flex_attention's place).  Lk = Lq + W, the first W keys are the cache, and
+// query i sees keys i ... i + W.  The three kernels are the bodies above with the mask's place taken by the band's structure,
+// and they stream only the tiles the band touches: keys q0 ... q0 + 15 + W for a workgroup's queries, queries
+// j0 - W ... j0 + 15 for a workgroup's keys.
+namespace cusrl {
+namespace {
+
+struct Band {
+    const uint8_t *valid;  // [N, Lq + W] contiguous, nonzero = a key that exists; or NULL
+    const int32_t *seg;    // [N, Lq] contiguous segment id of every query; the cache is segment 0; or NULL
+    const float *slopes;   // [H] ALiBi slopes; or NULL
+    int64_t W;
+};
+
+// scale * (q . k) - slope[h] * (i + W - j), or -inf where query i must not see key j.  i < Lq and j < Lq + W.
+__device__ __forceinline__ float band_score(const Band &b, float qk, float scale, int64_t n, int64_t h, int64_t i, int64_t j, int64_t Lq) {
+    if (j < i || j > i + b.W) return -INFINITY;
+    if (b.valid && !b.valid[n * (Lq + b.W) + j]) return -INFINITY;
+    if (b.seg && b.seg[n * Lq + i] != (j < b.W ? 0 : b.seg[n * Lq + j - b.W])) return -INFINITY;
+    const float s = qk * scale;
+    return b.slopes ? fmaf(-b.slopes[h], float(i + b.W - j), s) : s;  // (one rounding, the same in all four kernels)
+}
+
+// ------------------------------------------------------------------------------------------------------------ forward
+template <int kWidth>
+__global__ __launch_bounds__(kBlock) void band_fwd_kernel(Rows q, Rows k, Rows v, Band band, float *out, float *lse, Shape s, int64_t q_tiles,
+                                                          int64_t items) {
+    extern __shared__ float lds[];
+    const int D = s.D, ld = D | 1;
+    float *sq = lds, *sk = sq + kOwn * ld, *sv = sk + kTile * ld, *sp = sv + kTile * ld;  // sp: [kOwn][kTile]
+    const int r = threadIdx.x / kGroup, g = threadIdx.x % kGroup;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t tile = item % q_tiles, nh = item / q_tiles, h = nh % s.H, n = nh / s.H;
+        const int64_t q0 = tile * kOwn, i = q0 + r;
+        load_rows<kWidth>(sq, ld, q, n, h, q0, kOwn, s.Lq, D);
+        float m = -INFINITY, l = 0.0f, acc[kAcc];
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc[e] = 0.0f;
+        const int64_t k_end = min(s.Lk, q0 + kOwn + band.W);  // the last query of the tile sees key q0 + 15 + W
+        for (int64_t k0 = q0; k0 < k_end; k0 += kTile) {
+            __syncthreads();  // the previous tile's readers are done (and sq is not being written over a reader)
+            load_rows<kWidth>(sk, ld, k, n, h, k0, kTile, s.Lk, D);
+            load_rows<kWidth>(sv, ld, v, n, h, k0, kTile, s.Lk, D);
+            __syncthreads();
+            float score[kPerLane], top = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < kPerLane; ++c) {
+                const int64_t j = k0 + g + c * kGroup;
+                score[c] = (i < s.Lq && j < s.Lk) ? band_score(band, dot(sq + r * ld, sk + (g + c * kGroup) * ld, D), s.scale, n, h, i, j, s.Lq)
+                                                  : -INFINITY;
+                top = fmaxf(top, score[c]);
+            }
+            const float m_new = fmaxf(m, group_max(top));
+            float alpha = 1.0f, part = 0.0f;
+            if (m_new != -INFINITY) {  // (a row that has seen no key yet keeps m = -inf, l = 0 and p = 0)
+                alpha = (m == -INFINITY) ? 0.0f : expf(m - m_new);
+#pragma unroll
+                for (int c = 0; c < kPerLane; ++c) {
+                    const float p = (score[c] == -INFINITY) ? 0.0f : expf(score[c] - m_new);
+                    sp[r * kTile + g + c * kGroup] = p;
+                    part += p;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < kPerLane; ++c) sp[r * kTile + g + c * kGroup] = 0.0f;
+            }
+            l = l * alpha + group_sum(part);
+            m = m_new;
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) {
+                const int d = g + e * kGroup;
+                if (d < D) {
+                    float a = acc[e] * alpha;
+                    for (int j = 0; j < kTile; ++j) a = fmaf(sp[r * kTile + j], sv[j * ld + d], a);
+                    acc[e] = a;
+                }
+            }
+        }
+        if (i < s.Lq) {
+            const float inv = l > 0.0f ? 1.0f / l : 0.0f;  // a row with no visible key: zeros and lse = -inf
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) acc[e] = acc[e] * inv;
+            store_columns(out + ((n * s.Lq + i) * s.H + h) * D, acc, g, D);
+            if (g == 0) lse[(n * s.H + h) * s.Lq + i] = l > 0.0f ? m + logf(l) : -INFINITY;
+        }
+        __syncthreads();
+    }
+}
+
+// -------------------------------------------------------------------------------------------------- forward, Lq == 1
+// The step of a rollout: one query per (n, h) and W + 1 candidate keys, each read once, so nothing goes through LDS.  One
+// 16-lane group per (n, h): lane g scores key c0 + g of a chunk of 16 straight from global memory (its own K row, kWidth
+// floats per load), the statistics go round the group, and lane g accumulates columns g, g + 16, ... of the output over the
+// chunk's V rows (a row's columns are adjacent lanes: coalesced).  A block is one wave of four groups: it has no barrier and
+// no LDS, and a small batch spreads over four times the compute units a 256-thread block would reach.
+constexpr int kStepBlock = 64;
+constexpr int kStepGroups = kStepBlock / kGroup;
+
+template <int kWidth>
+__global__ __launch_bounds__(kStepBlock) void band_step_kernel(Rows q, Rows k, Rows v, Band band, float *out, float *lse, Shape s, int64_t items) {
+    const int r = threadIdx.x / kGroup, g = threadIdx.x % kGroup;
+    const int D = s.D;
+    for (int64_t nh = int64_t(blockIdx.x) * kStepGroups + r; nh < items; nh += int64_t(gridDim.x) * kStepGroups) {
+        const int64_t h = nh % s.H, n = nh / s.H;
+        const float *q_row = q.p + n * q.sn + h * D, *k_base = k.p + n * k.sn + h * D, *v_base = v.p + n * v.sn + h * D;
+        float m = -INFINITY, l = 0.0f, acc[kAcc];
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc[e] = 0.0f;
+        for (int64_t c0 = 0; c0 < s.Lk; c0 += kGroup) {  // (Lk = W + 1: every key is a candidate of the one query)
+            const int64_t j = c0 + g;
+            float score = -INFINITY;
+            if (j < s.Lk) {
+                const float *k_row = k_base + j * k.sl;
+                float qk = 0.0f;
+                if constexpr (kWidth == 4) {
+                    for (int d = 0; d < D; d += 4) {
+                        const float4 a = *reinterpret_cast<const float4 *>(q_row + d), b = *reinterpret_cast<const float4 *>(k_row + d);
+                        qk = fmaf(a.x, b.x, qk), qk = fmaf(a.y, b.y, qk), qk = fmaf(a.z, b.z, qk), qk = fmaf(a.w, b.w, qk);
+                    }
+                } else {
+                    qk = dot(q_row, k_row, D);
+                }
+                score = band_score(band, qk, s.scale, n, h, 0, j, 1);
+            }
+            const float m_new = fmaxf(m, group_max(score));
+            float alpha = 1.0f, p = 0.0f;
+            if (m_new != -INFINITY) {
+                alpha = (m == -INFINITY) ? 0.0f : expf(m - m_new);
+                p = (score == -INFINITY) ? 0.0f : expf(score - m_new);
+            }
+            l = l * alpha + group_sum(p);
+            m = m_new;
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) acc[e] = acc[e] * alpha;
+            for (int t = 0; t < kGroup; ++t) {
+                const float pt = __shfl(p, t, kGroup);  // (every lane of the group takes part; the loads below are guarded)
+                if (c0 + t < s.Lk) {
+                    const float *v_row = v_base + (c0 + t) * v.sl;
+#pragma unroll
+                    for (int e = 0; e < kAcc; ++e)
+                        if (g + e * kGroup < D) acc[e] = fmaf(pt, v_row[g + e * kGroup], acc[e]);
+                }
+            }
+        }
+        const float inv = l > 0.0f ? 1.0f / l : 0.0f;
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc[e] = acc[e] * inv;
+        store_columns(out + nh * D, acc, g, D);
+        if (g == 0) lse[nh] = l > 0.0f ? m + logf(l) : -INFINITY;
+    }
+}
+
+// ------------------------------------------------------------------------------------------- backward, query-major: dQ
+template <int kWidth>
+__global__ __launch_bounds__(kBlock) void band_bwd_dq_kernel(Rows q, Rows k, Rows v, Rows o, Rows dout, const float *lse, Band band,
+                                                             float *dq, float *delta, Shape s, int64_t q_tiles, int64_t items) {
+    extern __shared__ float lds[];
+    const int D = s.D, ld = D | 1;
+    float *sq = lds, *sdo = sq + kOwn * ld, *sk = sdo + kOwn * ld, *sv = sk + kTile * ld, *sds = sv + kTile * ld;  // sds: [kOwn][kTile]
+    const int r = threadIdx.x / kGroup, g = threadIdx.x % kGroup;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t tile = item % q_tiles, nh = item / q_tiles, h = nh % s.H, n = nh / s.H;
+        const int64_t q0 = tile * kOwn, i = q0 + r;
+        load_rows<kWidth>(sq, ld, q, n, h, q0, kOwn, s.Lq, D);
+        load_rows<kWidth>(sdo, ld, dout, n, h, q0, kOwn, s.Lq, D);
+        load_rows<kWidth>(sk, ld, o, n, h, q0, kOwn, s.Lq, D);  // (out passes through the key tile's place once)
+        __syncthreads();
+        float part = 0.0f;
+        for (int d = g; d < D; d += kGroup) part = fmaf(sdo[r * ld + d], sk[r * ld + d], part);
+        const float row_delta = group_sum(part);
+        const float row_lse = i < s.Lq ? lse[(n * s.H + h) * s.Lq + i] : -INFINITY;
+        if (i < s.Lq && g == 0) delta[(n * s.H + h) * s.Lq + i] = row_delta;
+        float acc[kAcc];
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc[e] = 0.0f;
+        const int64_t k_end = min(s.Lk, q0 + kOwn + band.W);
+        for (int64_t k0 = q0; k0 < k_end; k0 += kTile) {
+            __syncthreads();
+            load_rows<kWidth>(sk, ld, k, n, h, k0, kTile, s.Lk, D);
+            load_rows<kWidth>(sv, ld, v, n, h, k0, kTile, s.Lk, D);
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < kPerLane; ++c) {
+                const int t = g + c * kGroup;
+                const int64_t j = k0 + t;
+                float ds = 0.0f;
+                if (i < s.Lq && j < s.Lk) {
+                    const float sc = band_score(band, dot(sq + r * ld, sk + t * ld, D), s.scale, n, h, i, j, s.Lq);
+                    const float p = probability(sc, row_lse);
+                    if (p != 0.0f) ds = p * (dot(sdo + r * ld, sv + t * ld, D) - row_delta) * s.scale;
+                }
+                sds[r * kTile + t] = ds;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) {
+                const int d = g + e * kGroup;
+                if (d < D) {
+                    float a = acc[e];
+                    for (int j = 0; j < kTile; ++j) a = fmaf(sds[r * kTile + j], sk[j * ld + d], a);
+                    acc[e] = a;
+                }
+            }
+        }
+        if (i < s.Lq) store_columns(dq + ((n * s.Lq + i) * s.H + h) * D, acc, g, D);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------- backward, key-major: dK and dV
+// Owns keys j0 ... j0 + 15 with j0 = key_from + 16 * tile: the keys in front of key_from are not visited, and dk / dv hold
+// rows j - key_from.
+template <int kWidth>
+__global__ __launch_bounds__(kBlock) void band_bwd_dkv_kernel(Rows q, Rows k, Rows v, Rows dout, const float *lse, const float *delta,
+                                                              Band band, float *dk, float *dv, Shape s, int64_t key_from, int64_t k_tiles,
+                                                              int64_t items) {
+    extern __shared__ float lds[];
+    const int D = s.D, ld = D | 1;
+    float *sk = lds, *sv = sk + kOwn * ld, *sq = sv + kOwn * ld, *sdo = sq + kTile * ld;
+    float *sp = sdo + kTile * ld, *sds = sp + kOwn * kTile, *slse = sds + kOwn * kTile, *sdelta = slse + kTile;  // sp, sds: [kOwn][kTile]
+    const int r = threadIdx.x / kGroup, g = threadIdx.x % kGroup;
+    const int64_t rows_out = s.Lk - key_from;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t tile = item % k_tiles, nh = item / k_tiles, h = nh % s.H, n = nh / s.H;
+        const int64_t j0 = key_from + tile * kOwn, j = j0 + r;
+        load_rows<kWidth>(sk, ld, k, n, h, j0, kOwn, s.Lk, D);
+        load_rows<kWidth>(sv, ld, v, n, h, j0, kOwn, s.Lk, D);
+        float acc_k[kAcc], acc_v[kAcc];
+#pragma unroll
+        for (int e = 0; e < kAcc; ++e) acc_k[e] = acc_v[e] = 0.0f;
+        // key j is seen by queries j - W ... j
+        const int64_t q_begin = j0 > band.W ? j0 - band.W : 0, q_end = min(s.Lq, j0 + kOwn);
+        for (int64_t q0 = q_begin; q0 < q_end; q0 += kTile) {
+            __syncthreads();
+            load_rows<kWidth>(sq, ld, q, n, h, q0, kTile, s.Lq, D);
+            load_rows<kWidth>(sdo, ld, dout, n, h, q0, kTile, s.Lq, D);
+            if (threadIdx.x < kTile) {
+                const int64_t i = q0 + threadIdx.x;
+                slse[threadIdx.x] = i < s.Lq ? lse[(n * s.H + h) * s.Lq + i] : -INFINITY;
+                sdelta[threadIdx.x] = i < s.Lq ? delta[(n * s.H + h) * s.Lq + i] : 0.0f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < kPerLane; ++c) {
+                const int t = g + c * kGroup;
+                const int64_t i = q0 + t;
+                float p = 0.0f, ds = 0.0f;
+                if (i < s.Lq && j < s.Lk) {
+                    const float sc = band_score(band, dot(sq + t * ld, sk + r * ld, D), s.scale, n, h, i, j, s.Lq);
+                    p = probability(sc, slse[t]);
+                    if (p != 0.0f) ds = p * (dot(sdo + t * ld, sv + r * ld, D) - sdelta[t]) * s.scale;
+                }
+                sp[r * kTile + t] = p;
+                sds[r * kTile + t] = ds;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < kAcc; ++e) {
+                const int d = g + e * kGroup;
+                if (d < D) {
+                    float a = acc_v[e], b = acc_k[e];
+                    for (int t = 0; t < kTile; ++t) {
+                        a = fmaf(sp[r * kTile + t], sdo[t * ld + d], a);
+                        b = fmaf(sds[r * kTile + t], sq[t * ld + d], b);
+                    }
+                    acc_v[e] = a, acc_k[e] = b;
+                }
+            }
+        }
+        if (j < s.Lk) {
+            store_columns(dk + ((n * rows_out + (j - key_from)) * s.H + h) * D, acc_k, g, D);
+            store_columns(dv + ((n * rows_out + (j - key_from)) * s.H + h) * D, acc_v, g, D);
+        }
+        __syncthreads();
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------- host
+bool valid_band_sizes(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
+    return N >= 0 && H >= 1 && Lq >= 1 && W >= 1 && D >= 1 && D <= CUSRL_MAX_SDPA_HEAD_DIM;
+}
+
+bool band_sizes_fit(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
+    return W <= INT64_MAX - Lq && sizes_fit(N, H, Lq, Lq + W, D);
+}
+
+}  // namespace
+}  // namespace cusrl
+
+extern "C" int cusrl_band_sdpa_fwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                                   int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *key_valid,
+                                   const int32_t *q_segment, const float *alibi_slopes, float scale, float *out, float *lse, int64_t N,
+                                   int64_t H, int64_t Lq, int64_t W, int64_t D, void *stream) {
+    if (!q || !k || !v || !out || !lse || !valid_band_sizes(N, H, Lq, W, D)) return CUSRL_E_INVALID;
+    if (!band_sizes_fit(N, H, Lq, W, D)) return CUSRL_E_UNSUPPORTED;
+    if (N == 0) return 0;
+    const Rows rq{q, q_stride_n, q_stride_l}, rk{k, k_stride_n, k_stride_l}, rv{v, v_stride_n, v_stride_l};
+    const Band band{key_valid, q_segment, alibi_slopes, W};
+    const Shape shape{N, H, Lq, Lq + W, int(D), scale};
+    const bool vec = rows_vectorise(rq, int(D)) && rows_vectorise(rk, int(D)) && rows_vectorise(rv, int(D));
+    if (Lq == 1) {  // the step: no LDS, one 16-lane group per (n, h)
+        const int64_t items = N * H;
+        const dim3 grid{grid_for(ceil_div(items, int64_t(kStepGroups)))}, block{kStepBlock};
+        if (vec)
+            hipLaunchKernelGGL((band_step_kernel<4>), grid, block, 0, as_stream(stream), rq, rk, rv, band, out, lse, shape, items);
+        else
+            hipLaunchKernelGGL((band_step_kernel<1>), grid, block, 0, as_stream(stream), rq, rk, rv, band, out, lse, shape, items);
+        return launch_status();
+    }
+    const int64_t q_tiles = ceil_div(Lq, kOwn);
+    if (N * H > INT64_MAX / q_tiles) return CUSRL_E_UNSUPPORTED;
+    const int64_t items = N * H * q_tiles;
+    const dim3 grid{grid_for(items)}, block{kBlock};
+    const size_t lds = lds_bytes(kOwn + 2 * kTile, kOwn * kTile, int(D));
+    if (vec)
+        hipLaunchKernelGGL((band_fwd_kernel<4>), grid, block, lds, as_stream(stream), rq, rk, rv, band, out, lse, shape, q_tiles, items);
+    else
+        hipLaunchKernelGGL((band_fwd_kernel<1>), grid, block, lds, as_stream(stream), rq, rk, rv, band, out, lse, shape, q_tiles, items);
+    return launch_status();
+}
+
+extern "C" int64_t cusrl_band_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
+    if (!valid_band_sizes(N, H, Lq, W, D) || !band_sizes_fit(N, H, Lq, W, D)) return -1;
+    return N * H * Lq;  // delta, one fp32 per query row and head
+}
+
+extern "C" int cusrl_band_sdpa_bwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                                   int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *key_valid,
+                                   const int32_t *q_segment, const float *alibi_slopes, float scale, const float *out, const float *lse,
+                                   const float *dout, int64_t dout_stride_n, int64_t dout_stride_l, int64_t key_grad_from, float *dq,
+                                   float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D,
+                                   void *stream) {
+    if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || !valid_band_sizes(N, H, Lq, W, D) || key_grad_from < 0 ||
+        key_grad_from > W)
+        return CUSRL_E_INVALID;
+    if (!band_sizes_fit(N, H, Lq, W, D)) return CUSRL_E_UNSUPPORTED;
+    if (N == 0) return 0;
+    if (!workspace) return CUSRL_E_INVALID;
+    const int64_t Lk = Lq + W;
+    const Rows rq{q, q_stride_n, q_stride_l}, rk{k, k_stride_n, k_stride_l}, rv{v, v_stride_n, v_stride_l};
+    const Rows ro{out, Lq * H * D, H * D}, rdo{dout, dout_stride_n, dout_stride_l};
+    const Band band{key_valid, q_segment, alibi_slopes, W};
+    const Shape shape{N, H, Lq, Lk, int(D), scale};
+    const int64_t q_tiles = ceil_div(Lq, kOwn), k_tiles = ceil_div(Lk - key_grad_from, kOwn);
+    if (N * H > INT64_MAX / q_tiles || N * H > INT64_MAX / k_tiles) return CUSRL_E_UNSUPPORTED;
+    const bool vec = rows_vectorise(rq, int(D)) && rows_vectorise(rk, int(D)) && rows_vectorise(rv, int(D)) &&
+                     rows_vectorise(ro, int(D)) && rows_vectorise(rdo, int(D));
+    const dim3 block{kBlock};
+    {
+        const int64_t items = N * H * q_tiles;
+        const dim3 grid{grid_for(items)};
+        const size_t lds = lds_bytes(2 * kOwn + 2 * kTile, kOwn * kTile, int(D));
+        if (vec)
+            hipLaunchKernelGGL((band_bwd_dq_kernel<4>), grid, block, lds, as_stream(stream), rq, rk, rv, ro, rdo, lse, band, dq, workspace,
+                               shape, q_tiles, items);
+        else
+            hipLaunchKernelGGL((band_bwd_dq_kernel<1>), grid, block, lds, as_stream(stream), rq, rk, rv, ro, rdo, lse, band, dq, workspace,
+                               shape, q_tiles, items);
+        if (const int status = launch_status()) return status;
+    }
+    const int64_t items = N * H * k_tiles;
+    const dim3 grid{grid_for(items)};
+    const size_t lds = lds_bytes(2 * kOwn + 2 * kTile, 2 * kOwn * kTile + 2 * kTile, int(D));
+    if (vec)
+        hipLaunchKernelGGL((band_bwd_dkv_kernel<4>), grid, block, lds, as_stream(stream), rq, rk, rv, rdo, lse, workspace, band, dk, dv,
+                           shape, key_grad_from, k_tiles, items);
+    else
+        hipLaunchKernelGGL((band_bwd_dkv_kernel<1>), grid, block, lds, as_stream(stream), rq, rk, rv, rdo, lse, workspace, band, dk, dv,
+                           shape, key_grad_from, k_tiles, items);
+    return launch_status();
+}

@@ -1,5 +1,6 @@
 from cusrl_amd.nn.actor import Actor, Value
 from cusrl_amd.nn.activation import GeGlu, SwiGlu
+from cusrl_amd.nn.causal_attn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
 from cusrl_amd.nn.attention import MultiheadAttention, MultiheadCrossAttention, MultiheadSelfAttention, make_norm
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
 from cusrl_amd.nn.encoding import RotaryEmbedding
@@ -63,6 +64,10 @@ __all__ = [
     "TransformerDecoderLayer",
     "TransformerEncoderLayer",
     "make_norm",
+    "CausalMultiheadSelfAttention",
+    "CausalTransformerEncoderLayer",
+    "compute_segment_ids",
+    "get_alibi_slopes",
 ]
 
 

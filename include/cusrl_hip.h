@@ -995,6 +995,44 @@ int64_t cusrl_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t Lk, i
 int cusrl_rope_apply(const float *x, int64_t x_stride_n, int64_t x_stride_l, const float *cos_rows, const float *sin_rows,
                      float *out, int64_t N, int64_t L, int64_t H, int64_t D, int transpose, void *stream);
 
+/* ---- causal sliding-window ("band") attention — the attention core of cusrl/nn/module/causal_attn.py:135-258, whose mask and
+ * score rule are cusrl/nn/utils/attention.py:117-124 and 158-159 (additive entries of ABI 7; csrc/attention.hip).  fp32.
+ *
+ * q [N, Lq, H, D]; k and v [N, Lk, H, D] with Lk = Lq + W, the first W keys being the cache.  Layout, strides and the 16-byte /
+ * 4-byte load rule are those of cusrl_sdpa_* above.  Key j is visible to query i iff all of
+ *   i <= j <= i + W;
+ *   key_valid[n * Lk + j] != 0                      (key_valid: uint8 [N, Lk] contiguous, or NULL: every key exists);
+ *   q_segment[n * Lq + i] == seg_kv(n, j)           (q_segment: int32 [N, Lq] contiguous, or NULL: one segment), where
+ *                                                   seg_kv(n, j) = 0 for j < W and q_segment[n * Lq + j - W] otherwise.
+ * s_ij = scale * sum_d q_id k_jd - alibi_slopes[h] * (float)(i + W - j)   (alibi_slopes: fp32 [H], or NULL: no bias), -inf
+ * where key j is not visible.  out, lse, p, delta, ds, dq, dk, dv: the formulas of cusrl_sdpa_fwd / cusrl_sdpa_bwd.
+ *
+ * cusrl_band_sdpa_fwd, ONE launch; only the band is streamed: a workgroup's 16 queries q0 .. q0 + 15 read the key tiles from
+ *   q0 up to min(Lk, q0 + 16 + W).  Lq == 1 (the step of a rollout) takes a kernel of its own: one 16-lane group per (n, h)
+ *   reads the W + 1 keys straight from global memory, online softmax in chunks of 16 keys.
+ * cusrl_band_sdpa_bwd, TWO launches (query-major: dq and delta into `workspace`; key-major: dk, dv).  dk and dv are
+ *   [N, Lk - key_grad_from, H, D] contiguous, row j - key_grad_from holding key j; keys in front of key_grad_from are not
+ *   visited (0 <= key_grad_from <= W: a cache whose projection is detached passes W).  A workgroup's 16 keys j0 .. j0 + 15 read
+ *   the query tiles from max(0, j0 - W) up to min(Lq, j0 + 16).
+ *   workspace: float[cusrl_band_sdpa_bwd_workspace(N, H, Lq, W, D)] (-1 for sizes the entries refuse).
+ * One owning lane per output element, terms added in index order, no atomics, the same bits on every call.  A query with no
+ * visible key: out = 0, lse = -inf, exactly zero added to every gradient.
+ *
+ * N == 0 is a successful no-op.  CUSRL_E_INVALID, nothing launched: a NULL operand the call needs (key_valid, q_segment and
+ * alibi_slopes are optional), a negative size, H, Lq or W < 1, D outside 1 .. CUSRL_MAX_SDPA_HEAD_DIM, key_grad_from outside
+ * 0 .. W.  CUSRL_E_UNSUPPORTED: an extent beyond int64. */
+int cusrl_band_sdpa_fwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                        int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *key_valid,
+                        const int32_t *q_segment, const float *alibi_slopes, float scale, float *out, float *lse, int64_t N,
+                        int64_t H, int64_t Lq, int64_t W, int64_t D, void *stream);
+int cusrl_band_sdpa_bwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                        int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *key_valid,
+                        const int32_t *q_segment, const float *alibi_slopes, float scale, const float *out, const float *lse,
+                        const float *dout, int64_t dout_stride_n, int64_t dout_stride_l, int64_t key_grad_from, float *dq,
+                        float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D,
+                        void *stream);
+int64_t cusrl_band_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the

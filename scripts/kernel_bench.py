@@ -273,6 +273,34 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
     acos, asin = f(La, Da // 2), f(La, Da // 2)
     rows.measure(f"rope apply [B,{La},{Ha},{Da}] (B={Na})", lambda: _launch_rope(aq, acos, asin, False), 2 * tokens)
 
+    # ---- band attention (the band kernels of csrc/attention.hip): Lq = 24 queries over a window of 16 (40 keys) and the step
+    # Lq = 1 (17 keys), with key validity, segments and slopes, k / v read as the slices of a packed [Na, Lk, 2, 4, 16] projection;
+    # beside them the dense kernel fed the equivalent [Na, 4, Lq, Lk] bias on the same tensors.  Bytes: operands read + results
+    # written (the dense rows count their mask too)
+    from cusrl_amd.ops.band_attention import _launch_band_fwd, band_mask
+
+    Wb = 16
+    bslopes = torch.tensor([0.5, 0.25, 0.125, 0.0625], device=DEV)
+    for Lb in (24, 1):
+        bq, bdout = f(Na, Lb, Ha, Da), f(Na, Lb, Ha, Da)
+        bk, bv = f(Na, Lb + Wb, 2, Ha, Da).unbind(dim=2)
+        bvalid = torch.ones(Na, Lb + Wb, dtype=torch.bool, device=DEV)
+        bvalid[:, :Wb // 2] = False
+        bseg = (torch.arange(Lb, device=DEV) >= Lb // 2).to(torch.int32).expand(Na, Lb).contiguous()
+        bias = band_mask(bq, Wb, bvalid, bseg, bslopes).contiguous()
+        q_bytes, kv_bytes = Na * Lb * Ha * Da * 4, Na * (Lb + Wb) * Ha * Da * 4
+        rows.measure(f"band sdpa fwd [B,{Lb}+{Wb},{Ha},{Da}] (B={Na})", lambda: _launch_band_fwd(bq, bk, bv, Wb, bvalid, bseg, bslopes),
+                     2 * q_bytes + 2 * kv_bytes)
+        rows.measure(f"sdpa fwd dense band mask [B,{Lb}+{Wb},{Ha},{Da}] (B={Na})", lambda: _launch_sdpa_fwd(bq, bk, bv, bias, False),
+                     2 * q_bytes + 2 * kv_bytes + bias.numel() * 4)
+        if Lb > 1:
+            bout, blse = _launch_band_fwd(bq, bk, bv, Wb, bvalid, bseg, bslopes)
+            rows.measure(f"band sdpa bwd [B,{Lb}+{Wb},{Ha},{Da}] (B={Na})",
+                         lambda: ops.band_sdpa_backward(bq, bk, bv, bout, blse, bdout, Wb, bvalid, bseg, bslopes, key_grad_from=Wb),
+                         6 * q_bytes + 4 * kv_bytes)
+            rows.measure(f"sdpa bwd dense band mask [B,{Lb}+{Wb},{Ha},{Da}] (B={Na})",
+                         lambda: ops.sdpa_backward(bq, bk, bv, bout, blse, bdout, bias, False), 6 * q_bytes + 8 * kv_bytes + 2 * bias.numel() * 4)
+
     # ---- observation sanitiser (ObservationNanToNum): one [N, obs] observation.  Clean input is read and never written (4 B per
     # element, store on change); torch's in-place op reads and rewrites it (8 B).  All-NaN input is written back whole (8 B): it
     # has to be refilled before every launch, so the refill is timed with it and alone — subtract.
