@@ -89,15 +89,35 @@ def _mask_arguments(mask, N, H, Lq, Lk):
     return (_ptr(keep), _ptr(bias), *_mask_strides(mask, N, H, Lq, Lk))
 
 
+def _rows_arguments(*tensors):
+    """``(data_ptr, stride_n, stride_l)`` of each ``[N, L, H, D]`` tensor, as the entries take them."""
+    return tuple(a for t in tensors for a in (t.data_ptr(), t.stride(0), t.stride(1)))
+
+
+def _forward_outputs(q):
+    """``(out [N, Lq, H, D], lse [N, H, Lq])`` for a forward launch to fill."""
+    N, Lq, H, D = q.shape
+    return (torch.empty((N, Lq, H, D), dtype=torch.float32, device=q.device),
+            torch.empty((N, H, Lq), dtype=torch.float32, device=q.device))
+
+
+def _backward_operands(q, dout, key_rows: int, workspace_floats: int):
+    """``dout`` in the rows layout (a copy where it is not), then what a backward call fills: ``dq [N, Lq, H, D]``, ``dk`` and
+    ``dv`` ``[N, key_rows, H, D]`` and the fp32 workspace."""
+    N, Lq, H, D = q.shape
+    if not _rows_layout(dout):
+        dout = dout.contiguous()
+    dq, dk, dv = (torch.empty((N, rows, H, D), dtype=torch.float32, device=q.device) for rows in (Lq, key_rows, key_rows))
+    return dout, dq, dk, dv, torch.empty(int(workspace_floats), dtype=torch.float32, device=q.device)
+
+
 def _launch_sdpa_fwd(q, k, v, mask=None, is_causal: bool = False):
     """One ``cusrl_sdpa_fwd`` launch on ``[N, L, H, D]`` operands: ``(out [N, Lq, H, D], lse [N, H, Lq])``."""
     N, Lq, H, D = q.shape
     Lk = k.shape[1]
-    out = torch.empty((N, Lq, H, D), dtype=torch.float32, device=q.device)
-    lse = torch.empty((N, H, Lq), dtype=torch.float32, device=q.device)
-    _checked.cusrl_sdpa_fwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
-                            v.stride(1), *_mask_arguments(mask, N, H, Lq, Lk), int(is_causal), 1.0 / math.sqrt(D), out.data_ptr(),
-                            lse.data_ptr(), N, H, Lq, Lk, D, _stream())
+    out, lse = _forward_outputs(q)
+    _checked.cusrl_sdpa_fwd(*_rows_arguments(q, k, v), *_mask_arguments(mask, N, H, Lq, Lk), int(is_causal), 1.0 / math.sqrt(D),
+                            out.data_ptr(), lse.data_ptr(), N, H, Lq, Lk, D, _stream())
     return out, lse
 
 
@@ -106,14 +126,8 @@ def sdpa_backward(q, k, v, out, lse, dout, mask=None, is_causal: bool = False):
     be strided as :func:`sdpa_supported` allows; ``out`` and ``lse`` are the forward's."""
     N, Lq, H, D = q.shape
     Lk = k.shape[1]
-    if not _rows_layout(dout):
-        dout = dout.contiguous()
-    dq = torch.empty((N, Lq, H, D), dtype=torch.float32, device=q.device)
-    dk = torch.empty((N, Lk, H, D), dtype=torch.float32, device=q.device)
-    dv = torch.empty((N, Lk, H, D), dtype=torch.float32, device=q.device)
-    workspace = torch.empty(int(_native.lib().cusrl_sdpa_bwd_workspace(N, H, Lq, Lk, D)), dtype=torch.float32, device=q.device)
-    _checked.cusrl_sdpa_bwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
-                            v.stride(1), out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dout.stride(0), dout.stride(1),
+    dout, dq, dk, dv, workspace = _backward_operands(q, dout, Lk, _native.lib().cusrl_sdpa_bwd_workspace(N, H, Lq, Lk, D))
+    _checked.cusrl_sdpa_bwd(*_rows_arguments(q, k, v), out.data_ptr(), lse.data_ptr(), *_rows_arguments(dout),
                             *_mask_arguments(mask, N, H, Lq, Lk), int(is_causal), 1.0 / math.sqrt(D), dq.data_ptr(), dk.data_ptr(),
                             dv.data_ptr(), workspace.data_ptr(), N, H, Lq, Lk, D, _stream())
     return dq, dk, dv

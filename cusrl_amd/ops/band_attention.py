@@ -11,7 +11,8 @@ import torch
 
 from cusrl_amd import _native
 from cusrl_amd.ops._common import _checked, _ptr, _stream
-from cusrl_amd.ops.attention import MAX_SDPA_HEAD_DIM, _differentiated_inside_double_differentiable, _rows_layout, sdpa
+from cusrl_amd.ops.attention import (MAX_SDPA_HEAD_DIM, _backward_operands, _differentiated_inside_double_differentiable, _forward_outputs,
+                                     _rows_arguments, _rows_layout, sdpa)
 
 
 def _check_shapes(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from) -> None:
@@ -76,11 +77,9 @@ def _side_arguments(key_valid, q_segment, alibi_slopes):
 def _launch_band_fwd(q, k, v, window, key_valid=None, q_segment=None, alibi_slopes=None):
     """One ``cusrl_band_sdpa_fwd`` launch: ``(out [N, Lq, H, D], lse [N, H, Lq])``."""
     N, Lq, H, D = q.shape
-    out = torch.empty((N, Lq, H, D), dtype=torch.float32, device=q.device)
-    lse = torch.empty((N, H, Lq), dtype=torch.float32, device=q.device)
-    _checked.cusrl_band_sdpa_fwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
-                                 v.stride(1), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D), out.data_ptr(),
-                                 lse.data_ptr(), N, H, Lq, window, D, _stream())
+    out, lse = _forward_outputs(q)
+    _checked.cusrl_band_sdpa_fwd(*_rows_arguments(q, k, v), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D),
+                                 out.data_ptr(), lse.data_ptr(), N, H, Lq, window, D, _stream())
     return out, lse
 
 
@@ -88,17 +87,11 @@ def band_sdpa_backward(q, k, v, out, lse, dout, window, key_valid=None, q_segmen
     """The ``cusrl_band_sdpa_bwd`` call by itself: ``(dq [N, Lq, H, D], dk, dv [N, Lk - key_grad_from, H, D])``, contiguous; row
     ``j - key_grad_from`` of ``dk`` / ``dv`` is key ``j``'s, and the keys in front of ``key_grad_from`` are not visited."""
     N, Lq, H, D = q.shape
-    if not _rows_layout(dout):
-        dout = dout.contiguous()
-    rows = Lq + window - key_grad_from
-    dq = torch.empty((N, Lq, H, D), dtype=torch.float32, device=q.device)
-    dk = torch.empty((N, rows, H, D), dtype=torch.float32, device=q.device)
-    dv = torch.empty((N, rows, H, D), dtype=torch.float32, device=q.device)
-    workspace = torch.empty(int(_native.lib().cusrl_band_sdpa_bwd_workspace(N, H, Lq, window, D)), dtype=torch.float32, device=q.device)
-    _checked.cusrl_band_sdpa_bwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
-                                 v.stride(1), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D), out.data_ptr(),
-                                 lse.data_ptr(), dout.data_ptr(), dout.stride(0), dout.stride(1), key_grad_from, dq.data_ptr(),
-                                 dk.data_ptr(), dv.data_ptr(), workspace.data_ptr(), N, H, Lq, window, D, _stream())
+    dout, dq, dk, dv, workspace = _backward_operands(q, dout, Lq + window - key_grad_from,
+                                                     _native.lib().cusrl_band_sdpa_bwd_workspace(N, H, Lq, window, D))
+    _checked.cusrl_band_sdpa_bwd(*_rows_arguments(q, k, v), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D),
+                                 out.data_ptr(), lse.data_ptr(), *_rows_arguments(dout), key_grad_from, dq.data_ptr(), dk.data_ptr(),
+                                 dv.data_ptr(), workspace.data_ptr(), N, H, Lq, window, D, _stream())
     return dq, dk, dv
 
 

@@ -204,6 +204,24 @@ def test_the_backward_gives_the_same_bits_every_time(cusrl, golden, shape):
     assert all(torch.equal(first[name], second[name]) for name in first)
 
 
+@pytest.mark.parametrize("shape", [(2, 2, 17, 33, 8), (1, 2, 40, 31, 4), (2, 3, 33, 20, 6)], ids=lambda s: "x".join(map(str, s)))
+def test_key_grad_from_gives_the_rows_of_the_whole_backward(cusrl, golden, shape):
+    """The key-major pass started at key 7 or at key ``W`` stores the bits of rows ``key_grad_from:`` of the pass started at key
+    0, and ``dq`` does not move: wherever an owner's query tiles start it adds its terms in query order, and a query outside the
+    band contributes a product with an exact zero."""
+    from cusrl_amd.ops.band_attention import _launch_band_fwd, band_sdpa_backward
+
+    case = _ca.kernel_case(golden("attention"), shape, "all")
+    q, k, v, dout = (case[name].to(DEV) for name in ("q", "k", "v", "dout"))
+    window, sides = shape[3], _sides(case)
+    out, lse = _launch_band_fwd(q, k, v, window, *sides)
+    dq, dk, dv = band_sdpa_backward(q, k, v, out, lse, dout, window, *sides)
+    for start in (7, window):
+        dq_from, dk_from, dv_from = band_sdpa_backward(q, k, v, out, lse, dout, window, *sides, key_grad_from=start)
+        assert torch.equal(dq_from, dq), start
+        assert torch.equal(dk_from, dk[:, start:]) and torch.equal(dv_from, dv[:, start:]), start
+
+
 @pytest.mark.parametrize("D", [8, 6])
 def test_packed_kv_views_launch_where_they_are(cusrl, golden, monkeypatch, D):
     """The two slices of a packed ``[N, Lk, 2, H, D]`` projection are what the launch sees (their own data pointers and strides)
