@@ -65,16 +65,6 @@ __device__ __forceinline__ bool sanitize_quad(uint4 &v, uint32_t nan, uint32_t p
 }
 
 template <bool NT>
-__device__ __forceinline__ uint4 sanitize_load(const uint4 *p) {
-    if constexpr (NT) {
-        const float4 v = nt_load16(reinterpret_cast<const float4 *>(p));  // a move of 16 bytes: the bits pass untouched
-        return make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w));
-    } else {
-        return *p;
-    }
-}
-
-template <bool NT>
 __device__ __forceinline__ void sanitize_array(uint32_t *__restrict__ words, int64_t n, int64_t tid, int64_t stride, uint32_t nan,
                                                uint32_t posinf, uint32_t neginf) {
     int64_t head = int64_t((16 - (reinterpret_cast<uintptr_t>(words) & 15)) & 15) / 4;
@@ -89,8 +79,8 @@ __device__ __forceinline__ void sanitize_array(uint32_t *__restrict__ words, int
     for (int64_t q0 = tid; q0 < quads; q0 += 2 * stride) {
         const int64_t q1 = q0 + stride;
         const bool second = q1 < quads;
-        uint4 v0 = sanitize_load<NT>(body + q0), v1 = make_uint4(0u, 0u, 0u, 0u);
-        if (second) v1 = sanitize_load<NT>(body + q1);
+        uint4 v0 = stream_load16<NT>(reinterpret_cast<const char *>(body + q0)), v1 = make_uint4(0u, 0u, 0u, 0u);
+        if (second) v1 = stream_load16<NT>(reinterpret_cast<const char *>(body + q1));
         if (sanitize_quad(v0, nan, posinf, neginf)) body[q0] = v0;
         if (second && sanitize_quad(v1, nan, posinf, neginf)) body[q1] = v1;
     }

@@ -4,6 +4,8 @@
 // (no device-side table upload, no per-leaf launches).
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "common.hpp"
 #include "push_body.hpp"
 
@@ -61,35 +63,35 @@ __device__ __forceinline__ void pin_loaded(uint8_t (&r)[kGatherItems]) {
     for (int i = 0; i < 4; ++i) r[i] = uint8_t(t[i]);
 }
 
-template <typename V>
-__device__ __forceinline__ void gather_unit(const char *__restrict__ src, char *__restrict__ dst,
-                                            const int64_t *__restrict__ idx, int64_t ops, int64_t op0, int lpr,
-                                            int64_t src_pitch, int64_t dst_pitch, int64_t B, int64_t N, bool temporal) {
-    int64_t row[kGatherItems], col[kGatherItems], src_row[kGatherItems];
-#pragma unroll
-    for (int it = 0; it < kGatherItems; ++it) {
-        const int64_t op = min(op0 + int64_t(it) * kBlock, ops - 1);
-        if (lpr == 1) {
-            row[it] = op;
-            col[it] = 0;
-        } else {
-            row[it] = op / lpr;
-            col[it] = op - row[it] * lpr;
-        }
-    }
-    if (idx == nullptr) {  // identity: a strided row copy (building the per-slot record from the leaves)
-#pragma unroll
-        for (int it = 0; it < kGatherItems; ++it) src_row[it] = row[it];
-    } else if (temporal) {
+// Lane-op `it` of a lane whose first op is `op0` -> (row, column) of its leaf, at `lpr` lane-ops per row.  CLAMPED to the
+// last valid op, never predicated (see above): a clamped lane-op moves the last element once more, identical bytes.
+__device__ __forceinline__ void split_op(int64_t op0, int it, int64_t ops, int lpr, int64_t &row, int64_t &col) {
+    const int64_t op = min(op0 + int64_t(it) * kBlock, ops - 1);
+    row = lpr == 1 ? op : op / lpr;  // (most leaves: one 16-byte lane-op per row, no 64-bit division)
+    col = op - row * lpr;
+}
+
+// Output rows -> source slots for all items of a lane: idx[r] for a list of flat slots; temporal, step r / B of env
+// idx[r % B] of a [T, N] buffer.  The form is chosen ONCE in front of the items, so that the index loads stay back to back.
+__device__ __forceinline__ void source_slots(const int64_t *__restrict__ idx, const int64_t (&row)[kGatherItems], int64_t B,
+                                             int64_t N, bool temporal, int64_t (&slot)[kGatherItems]) {
+    if (temporal) {
 #pragma unroll
         for (int it = 0; it < kGatherItems; ++it) {
             const int64_t t = row[it] / B, b = row[it] - t * B;
-            src_row[it] = t * N + idx[b];
+            slot[it] = t * N + idx[b];
         }
     } else {
 #pragma unroll
-        for (int it = 0; it < kGatherItems; ++it) src_row[it] = idx[row[it]];
+        for (int it = 0; it < kGatherItems; ++it) slot[it] = idx[row[it]];
     }
+}
+
+// The row mover of the gather (src_row indexed, dst_row the identity) and of the scatter (the other way round).
+template <typename V>
+__device__ __forceinline__ void move_rows(const char *__restrict__ src, char *__restrict__ dst,
+                                          const int64_t (&src_row)[kGatherItems], const int64_t (&dst_row)[kGatherItems],
+                                          const int64_t (&col)[kGatherItems], int64_t src_pitch, int64_t dst_pitch) {
     V regs[kGatherItems];
 #pragma unroll
     for (int it = 0; it < kGatherItems; ++it)
@@ -100,7 +102,23 @@ __device__ __forceinline__ void gather_unit(const char *__restrict__ src, char *
     // keeps the whole body branch-free (with masked stores LLVM sinks each load into its store's block again)
 #pragma unroll
     for (int it = 0; it < kGatherItems; ++it)
-        *reinterpret_cast<V *>(dst + row[it] * dst_pitch + col[it] * int64_t(sizeof(V))) = regs[it];
+        *reinterpret_cast<V *>(dst + dst_row[it] * dst_pitch + col[it] * int64_t(sizeof(V))) = regs[it];
+}
+
+template <typename V>
+__device__ __forceinline__ void gather_unit(const char *__restrict__ src, char *__restrict__ dst,
+                                            const int64_t *__restrict__ idx, int64_t ops, int64_t op0, int lpr,
+                                            int64_t src_pitch, int64_t dst_pitch, int64_t B, int64_t N, bool temporal) {
+    int64_t row[kGatherItems], col[kGatherItems], src_row[kGatherItems];
+#pragma unroll
+    for (int it = 0; it < kGatherItems; ++it) split_op(op0, it, ops, lpr, row[it], col[it]);
+    if (idx == nullptr) {  // identity: a strided row copy (building the per-slot record from the leaves)
+#pragma unroll
+        for (int it = 0; it < kGatherItems; ++it) src_row[it] = row[it];
+    } else {
+        source_slots(idx, row, B, N, temporal, src_row);
+    }
+    move_rows<V>(src, dst, src_row, row, col, src_pitch, dst_pitch);
 }
 
 // 1-byte leaves (terminated / truncated / done): one lane gathers 4 consecutive output rows (4 index loads, then 4
@@ -108,19 +126,13 @@ __device__ __forceinline__ void gather_unit(const char *__restrict__ src, char *
 __device__ __forceinline__ void gather_bytes_packed(const char *__restrict__ src, char *__restrict__ dst,
                                                     const int64_t *__restrict__ idx, int64_t rows, int64_t op,
                                                     int64_t B, int64_t N, bool temporal) {
+    static_assert(kGatherItems == 4, "the four rows of one dword go through the slot helper as a lane's items");
     const int64_t r0 = op * 4;
     if (r0 >= rows) return;
-    int64_t src_row[4];
+    int64_t row[kGatherItems], src_row[kGatherItems];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t r = min(r0 + j, rows - 1);
-        if (temporal) {
-            const int64_t t = r / B, b = r - t * B;
-            src_row[j] = t * N + idx[b];
-        } else {
-            src_row[j] = idx[r];
-        }
-    }
+    for (int j = 0; j < 4; ++j) row[j] = min(r0 + j, rows - 1);
+    source_slots(idx, row, B, N, temporal, src_row);
     uint32_t packed = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) packed |= uint32_t(uint8_t(src[src_row[j]])) << (8 * j);
@@ -141,64 +153,42 @@ __device__ __forceinline__ void gather_bytes_packed(const char *__restrict__ src
 // 2 bytes, the rest 1 byte; an 8-byte leaf is two 4-byte entries with a row stride of 8 — so the kernels are three
 // straight-line, compile-time-indexed passes without any per-entry switch: every descriptor read is a load at a
 // static kernarg offset and no register image of the record has to be indexed at run time (that would live in scratch).
-constexpr int kMaxWideInRecord = 8;
-
-struct WideInRecord {  // a wide leaf (a multiple of 16 bytes per slot) living in the record: chunks [first, first + count)
-    char *ptr;         // gather: destination tensor
-    int32_t pitch;     // its row size in bytes
-    uint16_t first_chunk, num_chunks;
-};
-
 struct RecordTable {
     int32_t n4, n2, n1;
     int32_t record_bytes;               // a multiple of 16, at most CUSRL_MAX_RECORD_BYTES
-    int32_t n_wide, used_chunks;        // gather: wide leaves in the record; 16-byte chunks that hold anything
     uint16_t offset[CUSRL_MAX_PACKED];  // byte offset inside the record
     uint8_t stride[CUSRL_MAX_PACKED];   // bytes between consecutive rows of the leaf (its row size)
     char *ptr[CUSRL_MAX_PACKED];        // pack: source leaf (+ byte offset);  gather: destination tensor (+ byte offset)
-    WideInRecord wide[kMaxWideInRecord];
 };
 
 constexpr int kRecordTableDwords = sizeof(RecordTable) / 4;
-static_assert(sizeof(RecordTable) % 4 == 0 && kRecordTableDwords <= 2 * kWave, "two dwords of the table per lane");
+static_assert(sizeof(RecordTable) % 4 == 0 && kRecordTableDwords <= kWave, "one dword of the table per lane");
 
 // The table as seen by one wave: lane k holds dword k of the kernarg copy, fetched by ONE vector load (a single
 // round trip to kernarg memory; scalar loads sunk next to each use would be a chain of microsecond misses), and every
 // descriptor is then a v_readlane with a compile-time lane index, i.e. a scalar value again.
 struct WaveRecordTable {
-    uint32_t lo, hi;  // lane k holds dwords k and k + 64 of the table
+    uint32_t word;  // lane k holds dword k of the table (the lanes behind its end repeat the last one)
     __device__ __forceinline__ explicit WaveRecordTable(size_t kernarg_offset) {
         const uint32_t *karg = (const uint32_t *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + kernarg_offset);
-        const int lane = threadIdx.x & (kWave - 1);
-        lo = karg[lane];
-        hi = karg[lane + kWave < kRecordTableDwords ? lane + kWave : 0];
+        word = karg[min(int(threadIdx.x & (kWave - 1)), kRecordTableDwords - 1)];
     }
-    __device__ __forceinline__ uint32_t dword(int k) const {
-        return k < kWave ? __builtin_amdgcn_readlane(lo, k) : __builtin_amdgcn_readlane(hi, k - kWave);
-    }
+    static constexpr int kOffsetBase = 4, kStrideBase = kOffsetBase + CUSRL_MAX_PACKED / 2,
+                         kPtrBase = kStrideBase + CUSRL_MAX_PACKED / 4;
+    __device__ __forceinline__ uint32_t dword(int k) const { return __builtin_amdgcn_readlane(word, k); }
     __device__ __forceinline__ int n4() const { return int(dword(0)); }
     __device__ __forceinline__ int n2() const { return int(dword(1)); }
     __device__ __forceinline__ int n1() const { return int(dword(2)); }
     __device__ __forceinline__ int record_bytes() const { return int(dword(3)); }
-    __device__ __forceinline__ int n_wide() const { return int(dword(4)); }
-    __device__ __forceinline__ int used_chunks() const { return int(dword(5)); }
-    __device__ __forceinline__ int offset(int f) const { return (dword(6 + f / 2) >> (16 * (f % 2))) & 0xffff; }
-    __device__ __forceinline__ int stride(int f) const {
-        return (dword(6 + CUSRL_MAX_PACKED / 2 + f / 4) >> (8 * (f % 4))) & 0xff;
+    __device__ __forceinline__ int offset(int f) const { return (dword(kOffsetBase + f / 2) >> (16 * (f % 2))) & 0xffff; }
+    __device__ __forceinline__ int stride(int f) const { return (dword(kStrideBase + f / 4) >> (8 * (f % 4))) & 0xff; }
+    __device__ __forceinline__ char *ptr(int f) const {
+        return reinterpret_cast<char *>(uint64_t(dword(kPtrBase + 2 * f)) | (uint64_t(dword(kPtrBase + 2 * f + 1)) << 32));
     }
-    __device__ __forceinline__ char *pointer_at(int base) const {
-        return reinterpret_cast<char *>(uint64_t(dword(base)) | (uint64_t(dword(base + 1)) << 32));
-    }
-    __device__ __forceinline__ char *ptr(int f) const { return pointer_at(6 + CUSRL_MAX_PACKED / 2 + CUSRL_MAX_PACKED / 4 + 2 * f); }
-    static constexpr int kWideBase = 6 + CUSRL_MAX_PACKED / 2 + CUSRL_MAX_PACKED / 4 + 2 * CUSRL_MAX_PACKED;
-    __device__ __forceinline__ char *wide_ptr(int k) const { return pointer_at(kWideBase + 4 * k); }
-    __device__ __forceinline__ int wide_pitch(int k) const { return int(dword(kWideBase + 4 * k + 2)); }
-    __device__ __forceinline__ int wide_first(int k) const { return int(dword(kWideBase + 4 * k + 3) & 0xffff); }
-    __device__ __forceinline__ int wide_count(int k) const { return int(dword(kWideBase + 4 * k + 3) >> 16); }
 };
-static_assert(offsetof(RecordTable, offset) == 24 && offsetof(RecordTable, stride) == 24 + 2 * CUSRL_MAX_PACKED &&
-                  offsetof(RecordTable, ptr) == 24 + 3 * CUSRL_MAX_PACKED &&
-                  offsetof(RecordTable, wide) == 24 + 3 * CUSRL_MAX_PACKED + 8 * CUSRL_MAX_PACKED && sizeof(WideInRecord) == 16,
+static_assert(offsetof(RecordTable, offset) == 4 * WaveRecordTable::kOffsetBase &&
+                  offsetof(RecordTable, stride) == 4 * WaveRecordTable::kStrideBase &&
+                  offsetof(RecordTable, ptr) == 4 * WaveRecordTable::kPtrBase,
               "WaveRecordTable decodes this layout");
 
 // Record-major gather: a lane-op is one 16-byte chunk of one sampled slot's record, consecutive lanes take consecutive
@@ -250,7 +240,7 @@ __device__ __forceinline__ void gather_record_major(size_t map_kernarg_offset, i
     const int shift = 31 - __clz(chunks);
 #pragma unroll
     for (int it = 0; it < kGatherItems; ++it) {
-        // clamped, unpredicated (see gather_unit); in the power-of-two form an out-of-range op is folded onto the LAST
+        // clamped, unpredicated (see split_op); in the power-of-two form an out-of-range op is folded onto the LAST
         // record at the lane's own chunk index, so the lane's chunk stays the same for all items (duplicates rewrite
         // identical bytes)
         int64_t op = op0 + int64_t(it) * kBlock;
@@ -259,16 +249,7 @@ __device__ __forceinline__ void gather_record_major(size_t map_kernarg_offset, i
         out_row[it] = pow2 ? (op >> shift) : op / chunks;
         chunk[it] = int(op - out_row[it] * chunks);
     }
-    if (temporal) {
-#pragma unroll
-        for (int it = 0; it < kGatherItems; ++it) {
-            const int64_t t = out_row[it] / B, b = out_row[it] - t * B;
-            src_row[it] = t * N + idx[b];
-        }
-    } else {
-#pragma unroll
-        for (int it = 0; it < kGatherItems; ++it) src_row[it] = idx[out_row[it]];
-    }
+    source_slots(idx, out_row, B, N, temporal, src_row);
     uint4 regs[kGatherItems];
 #pragma unroll
     for (int it = 0; it < kGatherItems; ++it)
@@ -415,7 +396,7 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const GatherArgs args, c
     }
     const int64_t op0 = int64_t(blk - tab.block_start[f]) * kGatherOpsPerBlock + threadIdx.x;
     const int64_t ops = rows * lpr;
-    switch (unit) {
+    switch (unit) {  // (not through with_unit_type: the same five calls behind the lambda cost this kernel an SGPR)
         case 16: gather_unit<uint4>(src, dst, idx, ops, op0, lpr, src_pitch, dst_pitch, B, N, temp); break;
         case 8: gather_unit<uint2>(src, dst, idx, ops, op0, lpr, src_pitch, dst_pitch, B, N, temp); break;
         case 4: gather_unit<uint32_t>(src, dst, idx, ops, op0, lpr, src_pitch, dst_pitch, B, N, temp); break;
@@ -492,6 +473,8 @@ __global__ __launch_bounds__(kBlock) void compact_flags_kernel(const uint8_t *__
         __hip_atomic_store(count_out, block_offset + total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+__global__ void zero_count_kernel(int32_t *count) { __hip_atomic_store(count, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+
 // --------------------------------------------------------------------------------------------- scatter
 template <typename V>
 __global__ __launch_bounds__(kBlock) void scatter_rows_kernel(const char *__restrict__ src,
@@ -501,25 +484,14 @@ __global__ __launch_bounds__(kBlock) void scatter_rows_kernel(const char *__rest
     const int64_t limit = count_dev ? min(K, int64_t(*count_dev)) : K;
     const int64_t ops = limit * lpr;
     if (ops <= 0) return;
-    // same shape as the gather: clamped, unpredicated, index loads -> row loads -> stores (duplicates are identical)
+    // the gather's mover with the index vector on the destination side (duplicates are identical)
     const int64_t op0 = int64_t(blockIdx.x) * kGatherOpsPerBlock + threadIdx.x;
     int64_t row[kGatherItems], col[kGatherItems], dst_row[kGatherItems];
 #pragma unroll
-    for (int it = 0; it < kGatherItems; ++it) {
-        const int64_t op = min(op0 + int64_t(it) * kBlock, ops - 1);
-        row[it] = lpr == 1 ? op : op / lpr;
-        col[it] = op - row[it] * lpr;
-    }
+    for (int it = 0; it < kGatherItems; ++it) split_op(op0, it, ops, lpr, row[it], col[it]);
 #pragma unroll
     for (int it = 0; it < kGatherItems; ++it) dst_row[it] = indices[row[it]];
-    V regs[kGatherItems];
-#pragma unroll
-    for (int it = 0; it < kGatherItems; ++it)
-        regs[it] = *reinterpret_cast<const V *>(src + row[it] * row_bytes + col[it] * int64_t(sizeof(V)));
-    pin_loaded(regs);
-#pragma unroll
-    for (int it = 0; it < kGatherItems; ++it)
-        *reinterpret_cast<V *>(dst + dst_row[it] * row_bytes + col[it] * int64_t(sizeof(V))) = regs[it];
+    move_rows<V>(src, dst, row, dst_row, col, row_bytes, row_bytes);
 }
 
 // The act input of the next env step in ONE pass (cusrl/template/environment.py:365-379 `update_observation_and_state`
@@ -540,11 +512,7 @@ __global__ __launch_bounds__(kBlock) void splice_rows_kernel(const char *__restr
     int64_t target[kGatherItems];
     bool finished[kGatherItems];
 #pragma unroll
-    for (int it = 0; it < kGatherItems; ++it) {
-        const int64_t op = min(op0 + int64_t(it) * kBlock, ops - 1);  // clamped, unpredicated loads (see gather_unit)
-        row[it] = lpr == 1 ? op : op / lpr;
-        col[it] = op - row[it] * lpr;
-    }
+    for (int it = 0; it < kGatherItems; ++it) split_op(op0, it, ops, lpr, row[it], col[it]);
 #pragma unroll
     for (int it = 0; it < kGatherItems; ++it) {
         finished[it] = done[row[it]] != 0;
@@ -575,10 +543,26 @@ __global__ __launch_bounds__(kBlock) void window_indices_kernel(const int64_t *_
     out[i] = ((cursor + start[b] + t) % T) * N + env[b];
 }
 
-static int pick_unit(const void *a, const void *b, int64_t row_bytes) {
-    for (int unit : {16, 8, 4, 2})
-        if (row_bytes % unit == 0 && aligned(a, unit) && aligned(b, unit)) return unit;
+// widest lane-op that divides the row and keeps every tensor of the call aligned
+static int pick_unit(int64_t row_bytes, std::initializer_list<const void *> tensors) {
+    for (int unit : {16, 8, 4, 2}) {
+        bool fits = row_bytes % unit == 0;
+        for (const void *p : tensors) fits = fits && aligned(p, unit);
+        if (fits) return unit;
+    }
     return 1;
+}
+
+// bytes per lane-op -> the type a lane moves: `f` is a generic lambda, called with a value of that type
+template <typename F>
+static void with_unit_type(int unit, F &&f) {
+    switch (unit) {
+        case 16: f(uint4{}); break;
+        case 8: f(uint2{}); break;
+        case 4: f(uint32_t{}); break;
+        case 2: f(uint16_t{}); break;
+        default: f(uint8_t{}); break;
+    }
 }
 
 }  // namespace cusrl
@@ -621,13 +605,11 @@ struct WideField {
 };
 
 static int fill_record_table(const cusrl_packed_field_t *packed, int n_packed, int64_t record_bytes,
-                             RecordTable &rec, WideField *wide, int &n_wide) {
+                             RecordTable &rec, WideField *wide, int &n_wide, int &used_chunks) {
     rec.n4 = rec.n2 = rec.n1 = 0;
     rec.record_bytes = int32_t(record_bytes);
-    rec.n_wide = rec.used_chunks = 0;
-    n_wide = 0;
+    n_wide = used_chunks = 0;
     for (int i = 0; i < CUSRL_MAX_PACKED; ++i) rec.offset[i] = 0, rec.stride[i] = 4, rec.ptr[i] = nullptr;
-    for (int i = 0; i < kMaxWideInRecord; ++i) rec.wide[i] = WideInRecord{nullptr, 16, 0, 0};
     if (n_packed < 0 || n_packed > CUSRL_MAX_PACKED + CUSRL_MAX_FIELDS) return CUSRL_E_TOO_MANY;
     if (n_packed == 0) return 0;
     if (!packed || record_bytes < 16 || record_bytes % 16 != 0 || record_bytes > CUSRL_MAX_RECORD_BYTES)
@@ -656,9 +638,10 @@ static int fill_record_table(const cusrl_packed_field_t *packed, int n_packed, i
     int last = 0;
     for (int b = 0; b < record_bytes; ++b)
         if (used[b]) last = b;
-    rec.used_chunks = last / 16 + 1;  // trailing padding chunks are never read
+    used_chunks = last / 16 + 1;  // 16-byte chunks that hold anything: trailing padding chunks are never read
     int at = 0;
     for (int pass_width : {4, 2, 1}) {  // 4-byte entries first (an 8-byte leaf = two of them), then 2-byte, then 1-byte
+        int32_t &count = pass_width == 4 ? rec.n4 : pass_width == 2 ? rec.n2 : rec.n1;
         for (int i = 0; i < n_packed; ++i) {
             const int32_t w = packed[i].width, off = packed[i].offset;
             if (w >= 16 || (w == 8 ? 4 : w) != pass_width) continue;
@@ -666,12 +649,29 @@ static int fill_record_table(const cusrl_packed_field_t *packed, int n_packed, i
                 rec.offset[at] = uint16_t(off + 4 * half);
                 rec.stride[at] = uint8_t(w);
                 rec.ptr[at] = static_cast<char *>(packed[i].ptr) + 4 * half;
-                ++at;
+                ++at, ++count;
             }
         }
-        (pass_width == 4 ? rec.n4 : pass_width == 2 ? rec.n2 : rec.n1) = at - (pass_width == 4 ? 0 : pass_width == 2 ? rec.n4 : rec.n4 + rec.n2);
     }
     return 0;
+}
+
+static int entry_width(const RecordTable &rec, int f) { return f < rec.n4 ? 4 : f < rec.n4 + rec.n2 ? 2 : 1; }
+
+// Appends a leaf of `rows` rows of `row_bytes` to the table and its blocks to the launch; unit 0 = four 1-byte rows per
+// lane-op (gather_bytes_packed).  False when the launch outgrows a grid.
+static bool add_leaf(GatherTable &tab, int &n, int64_t &blocks, const void *src, void *dst, int64_t row_bytes,
+                     int64_t src_pitch, int64_t dst_pitch, int unit, int64_t rows) {
+    GatherLeaf &leaf = tab.leaf[n];
+    leaf.src = static_cast<const char *>(src);
+    leaf.dst = static_cast<char *>(dst);
+    leaf.src_pitch = int32_t(src_pitch);
+    leaf.dst_pitch = int32_t(dst_pitch);
+    leaf.unit = unit;
+    leaf.lanes_per_row = unit == 0 ? 1 : int32_t(row_bytes / unit);
+    tab.block_start[n++] = int32_t(blocks);
+    blocks += unit == 0 ? ceil_div((rows + 3) / 4, kBlock) : ceil_div(rows * leaf.lanes_per_row, kGatherOpsPerBlock);
+    return blocks <= INT32_MAX;
 }
 
 static void set_block_tail(GatherTable &tab, int n, int64_t blocks) {
@@ -687,13 +687,12 @@ static int pack_rows(const cusrl_packed_field_t *fields, int n_fields, void *rec
     GatherArgs args;
     RecordTable rec;
     WideField wide[CUSRL_MAX_FIELDS];
-    int n_wide = 0;
-    if (int rc = fill_record_table(fields, n_fields, record_bytes, rec, wide, n_wide)) return rc;
+    int n_wide = 0, used_chunks = 0;
+    if (int rc = fill_record_table(fields, n_fields, record_bytes, rec, wide, n_wide, used_chunks)) return rc;
     if (owned_chunks > 0) {  // every narrow entry inside the owned chunks, no wide leaf over them
         if (int64_t(owned_first + owned_chunks) * 16 > record_bytes) return CUSRL_E_INVALID;
         for (int f = 0; f < rec.n4 + rec.n2 + rec.n1; ++f) {
-            const int width = f < rec.n4 ? 4 : f < rec.n4 + rec.n2 ? 2 : 1;
-            if (rec.offset[f] < owned_first * 16 || rec.offset[f] + width > (owned_first + owned_chunks) * 16)
+            if (rec.offset[f] < owned_first * 16 || rec.offset[f] + entry_width(rec, f) > (owned_first + owned_chunks) * 16)
                 return CUSRL_E_INVALID;
         }
         for (int i = 0; i < n_wide; ++i)
@@ -703,19 +702,12 @@ static int pack_rows(const cusrl_packed_field_t *fields, int n_fields, void *rec
     if (n_wide > 0) {  // wide leaves: a strided row copy leaf -> record (the gather kernel without an index vector)
         GatherTable &tab = args.tab;
         int64_t blocks = 0;
-        for (int i = 0; i < n_wide; ++i) {
-            GatherLeaf &leaf = tab.leaf[i];
-            leaf.src = wide[i].ptr;
-            leaf.dst = static_cast<char *>(record) + wide[i].offset;
-            leaf.src_pitch = wide[i].width;
-            leaf.dst_pitch = int32_t(record_bytes);
-            leaf.unit = 16;
-            leaf.lanes_per_row = wide[i].width / 16;
-            tab.block_start[i] = int32_t(blocks);
-            blocks += ceil_div(rows * leaf.lanes_per_row, kGatherOpsPerBlock);
-            if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
-        }
-        set_block_tail(tab, n_wide, blocks);
+        int n = 0;
+        for (int i = 0; i < n_wide; ++i)
+            if (!add_leaf(tab, n, blocks, wide[i].ptr, static_cast<char *>(record) + wide[i].offset, wide[i].width,
+                          wide[i].width, record_bytes, 16, rows))
+                return CUSRL_E_UNSUPPORTED;
+        set_block_tail(tab, n, blocks);
         args.map.chunks = args.map.n_entries = 0;
         args.map.record_bytes = int32_t(record_bytes);
         hipLaunchKernelGGL(gather_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), args,
@@ -757,37 +749,21 @@ extern "C" int cusrl_gather_rows_packed(const cusrl_field_t *fields, int n_field
     GatherTable &tab = args.tab;
     RecordTable rec;
     WideField wide[CUSRL_MAX_FIELDS];
-    int n_wide = 0;
-    if (int rc = fill_record_table(packed, n_packed, n_packed > 0 ? record_bytes : 16, rec, wide, n_wide)) return rc;
+    int n_wide = 0, used_chunks = 0;
+    if (int rc = fill_record_table(packed, n_packed, n_packed > 0 ? record_bytes : 16, rec, wide, n_wide, used_chunks))
+        return rc;
     int64_t blocks = 0;
     int n = 0;
     for (int i = 0; i < n_fields; ++i) {
         const int64_t rb = fields[i].row_bytes;
         if (rb < 0 || rb > INT32_MAX || (rb > 0 && (!fields[i].src || !fields[i].dst))) return CUSRL_E_INVALID;
         if (rb == 0) continue;
-        GatherLeaf &leaf = tab.leaf[n];
-        leaf.src = static_cast<const char *>(fields[i].src);
-        leaf.dst = static_cast<char *>(fields[i].dst);
-        leaf.src_pitch = leaf.dst_pitch = int32_t(rb);
-        int64_t ops;
-        if (rb == 1 && aligned(leaf.dst, 4)) {
-            leaf.unit = 0;
-            leaf.lanes_per_row = 1;
-            ops = (rows + 3) / 4;
-        } else {
-            const int unit = pick_unit(leaf.src, leaf.dst, rb);
-            leaf.unit = unit;
-            leaf.lanes_per_row = int32_t(rb / unit);
-            ops = rows * (rb / unit);
-        }
-        tab.block_start[n] = int32_t(blocks);
-        blocks += ceil_div(ops, leaf.unit == 0 ? kBlock : kGatherOpsPerBlock);
-        if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
-        ++n;
+        const int unit = rb == 1 && aligned(fields[i].dst, 4) ? 0 : pick_unit(rb, {fields[i].src, fields[i].dst});
+        if (!add_leaf(tab, n, blocks, fields[i].src, fields[i].dst, rb, rb, rb, unit, rows)) return CUSRL_E_UNSUPPORTED;
     }
     // the chunk map of the record-major pass: chunk -> wide leaf (destination, pitch, first chunk) or entry mask
     RecordMap &map = args.map;
-    map.chunks = n_packed > 0 ? rec.used_chunks : 0;
+    map.chunks = used_chunks;
     map.record_bytes = int32_t(record_bytes);
     map.n_entries = rec.n4 + rec.n2 + rec.n1;
     map.pad = 0;
@@ -797,8 +773,7 @@ extern "C" int cusrl_gather_rows_packed(const cusrl_field_t *fields, int n_field
         for (int c = wide[i].offset / 16; c < (wide[i].offset + wide[i].width) / 16; ++c)
             map.chunk[c] = ChunkInfo{wide[i].ptr, wide[i].width, wide[i].offset / 16};
     for (int f = 0; f < map.n_entries; ++f) {
-        const int width = f < rec.n4 ? 4 : (f < rec.n4 + rec.n2 ? 2 : 1);
-        map.entry[f] = EntryInfo{rec.ptr[f], rec.offset[f], int32_t(rec.stride[f]) | (width << 8)};
+        map.entry[f] = EntryInfo{rec.ptr[f], rec.offset[f], int32_t(rec.stride[f]) | (entry_width(rec, f) << 8)};
         map.chunk[rec.offset[f] / 16].detail |= 1 << f;
     }
     set_block_tail(tab, n, blocks);
@@ -827,8 +802,6 @@ extern "C" int cusrl_window_indices(const int64_t *start, const int64_t *env, in
     return launch_status();
 }
 
-__global__ void zero_count_kernel(int32_t *count) { __hip_atomic_store(count, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-
 extern "C" int64_t cusrl_flag_blocks(int64_t n) { return n <= 0 ? 0 : ceil_div(n, kFlagChunk); }
 
 extern "C" int cusrl_compact_flags(const uint8_t *flags, int64_t n, int32_t *block_counts, int recount,
@@ -851,35 +824,18 @@ extern "C" int cusrl_compact_flags(const uint8_t *flags, int64_t n, int32_t *blo
     return launch_status();
 }
 
-#define CUSRL_LAUNCH_SCATTER(V)                                                                                      \
-    hipLaunchKernelGGL(scatter_rows_kernel<V>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream),           \
-                       static_cast<const char *>(src), indices, static_cast<char *>(dst), K, lpr, row_bytes, count_dev)
-
-#define CUSRL_LAUNCH_SPLICE(V)                                                                                       \
-    hipLaunchKernelGGL(splice_rows_kernel<V>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream),           \
-                       static_cast<const char *>(src), static_cast<const char *>(init), indices, count_dev, done,    \
-                       static_cast<char *>(dst), N, lpr, row_bytes)
-
 extern "C" int cusrl_splice_rows(const void *src, const void *init, const int64_t *indices, const int32_t *count_dev,
                                  const uint8_t *done, void *dst, int64_t N, int64_t row_bytes, void *stream) {
     if (N == 0 || row_bytes == 0) return 0;
     if (!src || !init || !indices || !count_dev || !done || !dst || N < 0 || row_bytes < 0) return CUSRL_E_INVALID;
-    int unit = 1;
-    for (int u : {16, 8, 4, 2})
-        if (row_bytes % u == 0 && aligned(src, u) && aligned(init, u) && aligned(dst, u)) {
-            unit = u;
-            break;
-        }
-    const int lpr = int(row_bytes / unit);
+    const int unit = pick_unit(row_bytes, {src, init, dst}), lpr = int(row_bytes / unit);
     const int64_t blocks = ceil_div(N * lpr, kGatherOpsPerBlock);
     if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
-    switch (unit) {
-        case 16: CUSRL_LAUNCH_SPLICE(uint4); break;
-        case 8: CUSRL_LAUNCH_SPLICE(uint2); break;
-        case 4: CUSRL_LAUNCH_SPLICE(uint32_t); break;
-        case 2: CUSRL_LAUNCH_SPLICE(uint16_t); break;
-        default: CUSRL_LAUNCH_SPLICE(uint8_t); break;
-    }
+    with_unit_type(unit, [&](auto lane) {
+        hipLaunchKernelGGL(splice_rows_kernel<decltype(lane)>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream),
+                           static_cast<const char *>(src), static_cast<const char *>(init), indices, count_dev, done,
+                           static_cast<char *>(dst), N, lpr, row_bytes);
+    });
     return launch_status();
 }
 
@@ -887,16 +843,12 @@ extern "C" int cusrl_scatter_rows(const void *src, const int64_t *indices, void 
                                   const int32_t *count_dev, void *stream) {
     if (K == 0 || row_bytes == 0) return 0;
     if (!src || !indices || !dst || K < 0 || row_bytes < 0) return CUSRL_E_INVALID;
-    const int unit = pick_unit(src, dst, row_bytes);
-    const int lpr = int(row_bytes / unit);
+    const int unit = pick_unit(row_bytes, {src, dst}), lpr = int(row_bytes / unit);
     const int64_t blocks = ceil_div(K * lpr, kGatherOpsPerBlock);
     if (blocks > INT32_MAX) return CUSRL_E_UNSUPPORTED;
-    switch (unit) {
-        case 16: CUSRL_LAUNCH_SCATTER(uint4); break;
-        case 8: CUSRL_LAUNCH_SCATTER(uint2); break;
-        case 4: CUSRL_LAUNCH_SCATTER(uint32_t); break;
-        case 2: CUSRL_LAUNCH_SCATTER(uint16_t); break;
-        default: CUSRL_LAUNCH_SCATTER(uint8_t); break;
-    }
+    with_unit_type(unit, [&](auto lane) {
+        hipLaunchKernelGGL(scatter_rows_kernel<decltype(lane)>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream),
+                           static_cast<const char *>(src), indices, static_cast<char *>(dst), K, lpr, row_bytes, count_dev);
+    });
     return launch_status();
 }

@@ -52,6 +52,26 @@ __device__ __forceinline__ void nt_store16(float4 *p, const float4 &v) {
     __builtin_nontemporal_store(n, reinterpret_cast<native_float4 *>(p));
 }
 
+// 16 opaque bytes, streamed (NT) or not: the non-temporal pair moves them as a float4, the bits pass through untouched
+template <bool NT>
+__device__ __forceinline__ uint4 stream_load16(const char *p) {
+    if constexpr (NT) {
+        const float4 v = nt_load16(reinterpret_cast<const float4 *>(p));
+        return make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w));
+    } else {
+        return *reinterpret_cast<const uint4 *>(p);
+    }
+}
+template <bool NT>
+__device__ __forceinline__ void stream_store16(char *p, const uint4 &v) {
+    if constexpr (NT) {
+        nt_store16(reinterpret_cast<float4 *>(p),
+                   make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)));
+    } else {
+        *reinterpret_cast<uint4 *>(p) = v;
+    }
+}
+
 // ---- wave / block reductions (wave64 shuffles; LDS only across the 4 waves of a block) ----
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

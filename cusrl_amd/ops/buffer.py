@@ -2,6 +2,7 @@
 
 from __future__ import annotations
 
+import ctypes
 from collections.abc import Sequence
 
 import torch
@@ -60,6 +61,33 @@ def _row_elems(storage: torch.Tensor) -> int:
     return n
 
 
+def _index_vector(indices: torch.Tensor) -> torch.Tensor:
+    require_device(indices, "indices")
+    if indices.dtype != torch.int64:
+        raise TypeError(f"'indices' must be int64, got {indices.dtype}")
+    return indices.contiguous()
+
+
+def _destinations(caller: str, given, leaves: Sequence[torch.Tensor], lead: tuple, rows: int) -> list[torch.Tensor]:
+    """The gather's outputs, ``lead + row shape`` per leaf: new tensors, or the ones the caller ``given`` (validated)."""
+    if given is None:
+        return [torch.empty(lead + tuple(s.shape[2:]), dtype=s.dtype, device=s.device) for s in leaves]
+    given = list(given)
+    for dst, src in zip(given, leaves):
+        if not dst.is_contiguous() or dst.dtype != src.dtype or dst.numel() != rows * _row_elems(src):
+            raise ValueError(f"{caller}: an 'out' tensor does not match its leaf (contiguous, same dtype, batch rows)")
+    return given
+
+
+def _field_table(storages: Sequence[torch.Tensor], outputs: Sequence[torch.Tensor]):
+    table = (Field * max(len(storages), 1))()
+    for slot, src, dst in zip(table, storages, outputs):
+        if not src.is_contiguous():
+            raise ValueError("buffer leaves must be contiguous [capacity, parallelism, ...] tensors")
+        slot.src, slot.dst, slot.row_bytes = src.data_ptr(), dst.data_ptr(), _row_bytes(src, 2)
+    return table
+
+
 def gather_rows(
     storages: Sequence[torch.Tensor],
     indices: torch.Tensor,
@@ -74,35 +102,16 @@ def gather_rows(
     (``:113-114``) for each ``[T, N, ...]`` leaf.  ``out``: contiguous destinations the caller owns (e.g. two halves of
     one joint batch), one per leaf.
     """
-    require_device(indices, "indices")
-    if indices.dtype != torch.int64:
-        raise TypeError(f"'indices' must be int64, got {indices.dtype}")
-    if not indices.is_contiguous():
-        indices = indices.contiguous()
+    indices = _index_vector(indices)
     batch = indices.numel()
-    lead = (capacity, batch) if temporal else (batch,)
-    if out is None:
-        outputs = [torch.empty(lead + tuple(s.shape[2:]), dtype=s.dtype, device=s.device) for s in storages]
-    else:
-        outputs = list(out)
-        for dst, src in zip(outputs, storages):
-            if not dst.is_contiguous() or dst.dtype != src.dtype or dst.numel() != batch * (capacity if temporal else 1) * _row_elems(src):
-                raise ValueError("gather_rows: an 'out' tensor does not match its leaf (contiguous, same dtype, batch rows)")
+    rows = batch * (capacity if temporal else 1)
+    outputs = _destinations("gather_rows", out, storages, (capacity, batch) if temporal else (batch,), rows)
     if batch == 0:
         return outputs
     for start in range(0, len(storages), _native.MAX_FIELDS):
-        chunk = range(start, min(start + _native.MAX_FIELDS, len(storages)))
-        table = (Field * len(chunk))()
-        for i, k in enumerate(chunk):
-            src = storages[k]
-            if not src.is_contiguous():
-                raise ValueError("buffer leaves must be contiguous [capacity, parallelism, ...] tensors")
-            table[i].src = src.data_ptr()
-            table[i].dst = outputs[k].data_ptr()
-            table[i].row_bytes = _row_bytes(src, 2)
-        rows = batch * (capacity if temporal else 1)
-        _observed("cusrl_gather_rows", table, len(chunk), indices.data_ptr(), batch, capacity, parallelism, int(temporal),
-                nbytes=lambda: rows * sum(2 * _row_bytes(storages[k], 2) for k in chunk) + batch * 8)
+        chunk = storages[start : start + _native.MAX_FIELDS]
+        _observed("cusrl_gather_rows", _field_table(chunk, outputs[start:]), len(chunk), indices.data_ptr(), batch, capacity,
+                parallelism, int(temporal), nbytes=lambda: rows * sum(2 * _row_bytes(s, 2) for s in chunk) + batch * 8)
     return outputs
 
 
@@ -198,9 +207,15 @@ class RecordPack:
             raise ValueError("the packed leaves exceed one record (1024 bytes / 16 narrow entries)")
         self.record = torch.empty((self.rows, self.record_bytes), dtype=torch.uint8, device=first.device)
         self.key = tuple((name, t.data_ptr(), _row_bytes(t, 2)) for name, t in self.leaves.items())
-        self._table = (PackedField * len(self.leaves))()
-        for slot, (name, storage) in zip(self._table, self.leaves.items()):
-            slot.ptr, slot.offset, slot.width = storage.data_ptr(), self.offsets[name], _row_bytes(storage, 2)
+        self._table = self.packed_table(list(self.leaves))
+
+    def packed_table(self, names: Sequence[str], tensors: Sequence[torch.Tensor] | None = None):
+        """``cusrl_packed_field_t`` array of the leaves ``names`` — their place in the record — pointing at the leaves
+        themselves (pack) or at ``tensors``, one per name (the gather's destinations)."""
+        table = (PackedField * len(names))()
+        for slot, name, tensor in zip(table, names, tensors or [self.leaves[name] for name in names]):
+            slot.ptr, slot.offset, slot.width = tensor.data_ptr(), self.offsets[name], _row_bytes(self.leaves[name], 2)
+        return table
 
     def build(self, names: Sequence[str] | None = None) -> None:
         """(Re)write the record from the leaves — all of them, or only ``names`` (the leaves that changed since the
@@ -211,11 +226,7 @@ class RecordPack:
             chosen = [name for name in self.leaves if name in set(names)]
             if not chosen:
                 return
-            table = (PackedField * len(chosen))()
-            for slot, name in zip(table, chosen):
-                storage = self.leaves[name]
-                slot.ptr, slot.offset, slot.width = storage.data_ptr(), self.offsets[name], _row_bytes(storage, 2)
-            count, moved = len(chosen), sum(_row_bytes(self.leaves[name], 2) for name in chosen)
+            table, count, moved = self.packed_table(chosen), len(chosen), sum(_row_bytes(self.leaves[name], 2) for name in chosen)
         owned = self._owned_chunks(None if names is None else set(names))
         if owned is not None:
             _observed("cusrl_pack_rows_owned", table, count, self.record.data_ptr(), self.record_bytes, self.rows, owned[0], owned[1],
@@ -240,8 +251,6 @@ class RecordPack:
     def through_offsets(self, leaves: Sequence[str]):
         """int32 array for ``cusrl_buffer_push_through``: the record offset of every pushed leaf that can be written
         through (a wide leaf of this record: whole 16-byte chunks), -1 for the others; None when there is none."""
-        import ctypes
-
         offsets = (ctypes.c_int32 * max(len(leaves), 1))()
         any_through = False
         for i, name in enumerate(leaves):
@@ -272,39 +281,18 @@ def gather_rows_packed(
         return gather_rows(storages, indices, capacity, parallelism, temporal, out=out), []
     if len(storages) > _native.MAX_FIELDS:
         raise ValueError("gather_rows_packed: too many plain leaves for one launch")
-    require_device(indices, "indices")
-    if indices.dtype != torch.int64:
-        raise TypeError(f"'indices' must be int64, got {indices.dtype}")
-    if not indices.is_contiguous():
-        indices = indices.contiguous()
+    indices = _index_vector(indices)
     batch = indices.numel()
     lead = (capacity, batch) if temporal else (batch,)
+    rows = batch * (capacity if temporal else 1)
     sources = [pack.leaves[name] for name in packed_names]
-    rows_out = batch * (capacity if temporal else 1)
-
-    def destinations(given, leaves):
-        if given is None:
-            return [torch.empty(lead + tuple(s.shape[2:]), dtype=s.dtype, device=s.device) for s in leaves]
-        given = list(given)
-        for dst, src in zip(given, leaves):
-            if not dst.is_contiguous() or dst.dtype != src.dtype or dst.numel() != rows_out * _row_elems(src):
-                raise ValueError("gather_rows_packed: an 'out' tensor does not match its leaf (contiguous, same dtype, batch rows)")
-        return given
-
-    outputs, packed_outputs = destinations(out, storages), destinations(packed_out, sources)
+    outputs = _destinations("gather_rows_packed", out, storages, lead, rows)
+    packed_outputs = _destinations("gather_rows_packed", packed_out, sources, lead, rows)
     if batch == 0:
         return outputs, packed_outputs
-    table = (Field * max(len(storages), 1))()
-    for i, src in enumerate(storages):
-        if not src.is_contiguous():
-            raise ValueError("buffer leaves must be contiguous [capacity, parallelism, ...] tensors")
-        table[i].src, table[i].dst, table[i].row_bytes = src.data_ptr(), outputs[i].data_ptr(), _row_bytes(src, 2)
-    packed_table = (PackedField * len(packed_names))()
-    for slot, name, out in zip(packed_table, packed_names, packed_outputs):
-        slot.ptr, slot.offset, slot.width = out.data_ptr(), pack.offsets[name], _row_bytes(pack.leaves[name], 2)
-    rows = batch * (capacity if temporal else 1)
-    _observed("cusrl_gather_rows_packed", table, len(storages), pack.record.data_ptr(), pack.record_bytes, packed_table,
-            len(packed_names), indices.data_ptr(), batch, capacity, parallelism, int(temporal),
+    _observed("cusrl_gather_rows_packed", _field_table(storages, outputs), len(storages), pack.record.data_ptr(),
+            pack.record_bytes, pack.packed_table(packed_names, packed_outputs), len(packed_names), indices.data_ptr(), batch, capacity,
+            parallelism, int(temporal),
             nbytes=lambda: rows * (sum(2 * _row_bytes(s, 2) for s in storages) + sum(2 * _row_bytes(s, 2) for s in sources)) + batch * 8)
     return outputs, packed_outputs
 

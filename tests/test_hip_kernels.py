@@ -1721,6 +1721,53 @@ def test_assign_rows_equals_index_put(ops):
     ops.assign_rows(dst, indices[:0], src[:0])  # empty: no launch
 
 
+def test_scatter_rows_with_a_device_count_at_every_lane_unit(ops):
+    """``scatter_rows`` under a count the kernel reads, with ``uint8`` rows so that the row size alone picks the lane unit
+    (16 / 8 / 4 / 2 / 1 bytes), over two blocks, and from a source that is only 4-byte aligned; then ``splice_rows`` with
+    an ``init`` that is only 8-byte aligned.  Bit-exact against ``index_put`` on a sentinel-filled destination."""
+    generator = torch.Generator(device=DEV).manual_seed(11)
+    sentinel = 0xA5  # the source bytes stay below 128: a row that still holds the sentinel was not written
+    for K, W, skew in ((40, 48, 0), (40, 24, 0), (40, 12, 0), (40, 6, 0), (40, 3, 0), (70, 256, 0), (40, 48, 4)):
+        rows = 64 if K <= 64 else 128
+        base = torch.randint(0, 128, (K * W + skew,), dtype=torch.uint8, device=DEV, generator=generator)
+        src = base[skew:].view(K, W)
+        assert src.is_contiguous() and src.data_ptr() % 16 == skew
+        indices = torch.randperm(rows, device=DEV, generator=generator)[:K]  # unique rows: no dependence on store order
+        for count in (0, 3, K, K + 5):
+            dst = torch.full((rows, W), sentinel, dtype=torch.uint8, device=DEV)
+            want = dst.clone()
+            want[indices[: min(K, count)]] = src[: min(K, count)]
+            ops.scatter_rows(src, indices, dst, torch.tensor([count], dtype=torch.int32, device=DEV))
+            assert torch.equal(dst, want), (K, W, skew, count)
+    N, W = 33, 48
+    src = torch.randint(0, 128, (N, W), dtype=torch.uint8, device=DEV, generator=generator)
+    init = torch.randint(0, 128, (N * W + 8,), dtype=torch.uint8, device=DEV, generator=generator)[8:].view(N, W)
+    assert init.data_ptr() % 16 == 8 and src.data_ptr() % 16 == 0
+    done = torch.rand(N, 1, device=DEV, generator=generator) < 0.3
+    finished = done.squeeze(-1).nonzero().squeeze(-1)
+    indices = torch.zeros(N, dtype=torch.int64, device=DEV)
+    indices[: finished.numel()] = finished
+    count = torch.tensor([finished.numel()], dtype=torch.int32, device=DEV)
+    dst = torch.full_like(src, sentinel)
+    ops.splice_rows(src, init, indices, count, done, dst)
+    expect = src.clone()
+    expect[finished] = init[: finished.numel()]
+    assert torch.equal(dst, expect)
+
+
+def test_gather_two_byte_unit_leaves_bit_exact(ops):
+    """``float16`` leaves of 3 and of 1 channel: 6- and 2-byte rows, the gather's 2-byte lane unit (no other case takes it)."""
+    T, N, B = 3, 5, 7
+    rng = np.random.default_rng(T * N + B)
+    leaves = [rng.standard_normal((T, N, 3)).astype(np.float16), rng.standard_normal((T, N, 1)).astype(np.float16)]
+    idx = rng.permutation(T * N)[:B].astype(np.int64)
+    for x, out in zip(leaves, ops.gather_rows([dev(x) for x in leaves], dev(idx), T, N)):
+        assert np.array_equal(host(out), oracle.gather_rows(x, idx)), x.shape
+    env_idx = rng.permutation(N)[:3].astype(np.int64)
+    for x, out in zip(leaves, ops.gather_rows([dev(x) for x in leaves], dev(env_idx), T, N, temporal=True)):
+        assert np.array_equal(host(out), oracle.gather_rows(x, env_idx, temporal=True)), x.shape
+
+
 def test_assemble_gradients_reduces_deferred_column_windows(ops):
     """Partial rows of the column-sum kernels: a window [column, column + numel) of rows of width row_stride."""
     rng = np.random.default_rng(9)
