@@ -21,6 +21,7 @@ from cusrl_amd.nn import (
     TransformerEncoderLayer, make_norm,
 )
 from cusrl_amd.nn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
+from cusrl_amd.nn import Cnn, CnnFactory, LearnablePositionalEncoding2D, SeparableConv2d, SinusoidalPositionalEncoding2D
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
 )
@@ -122,4 +123,9 @@ __all__ = [
     "CausalTransformerEncoderLayer",
     "compute_segment_ids",
     "get_alibi_slopes",
+    "Cnn",
+    "CnnFactory",
+    "LearnablePositionalEncoding2D",
+    "SeparableConv2d",
+    "SinusoidalPositionalEncoding2D",
 ]

@@ -105,6 +105,7 @@ MAX_MIRROR_FIELDS = _CONSTANTS["MAX_MIRROR_FIELDS"]
 MAX_SYMMETRIZE_CHANNELS = _CONSTANTS["MAX_SYMMETRIZE_CHANNELS"]
 MAX_SYMMETRIC_HEAD_ACTIONS = _CONSTANTS["MAX_SYMMETRIC_HEAD_ACTIONS"]
 MAX_LAYER_NORM_WIDTH = _CONSTANTS["MAX_LAYER_NORM_WIDTH"]
+MAX_DWCONV_TAPS = _CONSTANTS["MAX_DWCONV_TAPS"]
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
 

@@ -1,9 +1,11 @@
 from cusrl_amd.nn.actor import Actor, Value
 from cusrl_amd.nn.activation import GeGlu, SwiGlu
+from cusrl_amd.nn.cnn import Cnn, CnnFactory
 from cusrl_amd.nn.causal_attn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
 from cusrl_amd.nn.attention import MultiheadAttention, MultiheadCrossAttention, MultiheadSelfAttention, make_norm
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
 from cusrl_amd.nn.encoding import RotaryEmbedding
+from cusrl_amd.nn.encoding2d import LearnablePositionalEncoding2D, SinusoidalPositionalEncoding2D
 from cusrl_amd.nn.feedforward import FeedForward
 from cusrl_amd.nn.gate import (
     Gate, GruGate, HighwayGate, InputGate, OutputGate, PassthroughGate, ResidualGate, SigmoidTanhGate, gate_map, get_gate_cls,
@@ -13,6 +15,7 @@ from cusrl_amd.nn.module import LinearFp32, Mlp, Module, ModuleFactory
 from cusrl_amd.nn.normalization import Denormalization, DenormalizationFactory, Normalization, NormalizationFactory
 from cusrl_amd.nn.rms import RunningMeanStd
 from cusrl_amd.nn.rnn import Gru, Lstm, Rnn
+from cusrl_amd.nn.separable_conv import SeparableConv2d
 from cusrl_amd.nn.sequential import Sequential, SequentialFactory
 from cusrl_amd.nn.simba import Simba, SimbaBlock, SimbaFactory
 from cusrl_amd.nn.transformer import TransformerDecoderLayer, TransformerEncoderLayer
@@ -68,6 +71,11 @@ __all__ = [
     "CausalTransformerEncoderLayer",
     "compute_segment_ids",
     "get_alibi_slopes",
+    "Cnn",
+    "CnnFactory",
+    "LearnablePositionalEncoding2D",
+    "SeparableConv2d",
+    "SinusoidalPositionalEncoding2D",
 ]
 
 

@@ -37,6 +37,9 @@ from cusrl_amd.ops.buffer import (
     HostCounter, RecordPack, _row_elems, assign_rows, buffer_push, compact_flags, gather_rows, gather_rows_packed, make_push_table,
     push_table, scatter_rows, splice_rows, window_indices,
 )
+from cusrl_amd.ops.conv import (
+    DepthwiseConv2d, depthwise_conv2d, dwconv2d_backward_input, dwconv2d_backward_params, dwconv2d_supported,
+)
 from cusrl_amd.ops.gate import GateCombine, Glu, gate_backward, gate_combine, gate_supported, glu, glu_backward, glu_supported
 from cusrl_amd.ops.gradient import (
     DeferredColumns, adam_norm_workspace, adam_step, adam_step_normed, adam_step_window, assemble_gradients, clip_grad_norm_,

@@ -1033,6 +1033,42 @@ int cusrl_band_sdpa_bwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, 
                         void *stream);
 int64_t cusrl_band_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D);
 
+/* ---- depthwise 2-D convolution — the spatial half of cusrl/nn/layer/separable_conv.py:52-64, an nn.Conv2d with
+ * groups == in_channels == out_channels and zero padding (additive entries of ABI 7; csrc/conv.hip).  fp32, contiguous:
+ *   x, dx [N, C, H, W];  w, dw [C, KH, KW] (the memory of torch's [C, 1, KH, KW]);  bias, dbias [C] (NULL: no bias);
+ *   out, dout [N, C, Ho, Wo] with Ho = (H + 2 PH - DH (KH - 1) - 1) / SH + 1 (rounded down) and Wo likewise: torch's formula.
+ * Geometry (KH, KW, SH, SW, PH, PW, DH, DW): kernel, stride, zero padding (the same on both sides of an axis), dilation.
+ *
+ * cusrl_dwconv2d_fwd, ONE launch:
+ *   out[n,c,oy,ox] = bias[c] + sum_ky sum_kx w[c,ky,kx] x[n,c, oy SH - PH + ky DH, ox SW - PW + kx DW],
+ *   a tap outside the image contributing nothing; fp32, the terms added in (ky, kx) order, no fma.
+ * cusrl_dwconv2d_bwd_input, ONE launch, a gather: dx[n,c,iy,ix] = sum over the (ky, kx, oy, ox) with oy SH - PH + ky DH == iy
+ *   and ox SW - PW + kx DW == ix of w[c,ky,kx] dout[n,c,oy,ox], in (ky, kx) order.  One owning thread per element, no atomics;
+ *   a row or column no window reads (a stride remainder) is the empty sum, exactly 0.0f.
+ * cusrl_dwconv2d_bwd_params, at most TWO launches: dw[c,ky,kx] = sum_{n,oy,ox} dout[n,c,oy,ox] x[n,c,iy,ix] (taps inside the
+ *   image only) and, unless dbias is NULL, dbias[c] = sum_{n,oy,ox} dout[n,c,oy,ox].  float64 sums in a fixed order — a thread
+ *   walks its (n, oy, ox) in ascending order, lanes, waves and blocks are added in index order — rounded to fp32 once: the same
+ *   bits on every call.  Up to 64 blocks per channel write a row of CUSRL_MAX_DWCONV_TAPS + 1 sums into
+ *   double partials[cusrl_dwconv2d_num_partials(N, C, Ho, Wo)] and one finalize launch adds the rows; where one block per
+ *   channel covers everything (N Ho Wo <= 1024) it writes dw and dbias itself, num_partials is 0 and partials may be NULL.
+ *   (-1: sizes the entries refuse.)
+ * No floating-point atomics anywhere.  Every access is 4 bytes wide: any 4-byte aligned pointer works and gives the same bits.
+ * Element indices are 64-bit wherever a count does not fit 32.  No output may alias an input.
+ *
+ * N == 0 is a successful no-op.  Validation runs on the host before anything is launched.  CUSRL_E_INVALID: a NULL pointer the
+ * call uses (bias / dbias are optional; partials where num_partials > 0), N < 0, C, H, W, K*, S* or D* < 1, P* < 0, a geometry
+ * whose Ho or Wo is below 1.  CUSRL_E_UNSUPPORTED: KH KW > CUSRL_MAX_DWCONV_TAPS (7 x 7), an extent or element count beyond
+ * int64, more than INT32_MAX / 3200 channels. */
+#define CUSRL_MAX_DWCONV_TAPS 49
+int cusrl_dwconv2d_fwd(const float *x, const float *w, const float *bias, float *out, int64_t N, int64_t C, int64_t H, int64_t W,
+                       int64_t KH, int64_t KW, int64_t SH, int64_t SW, int64_t PH, int64_t PW, int64_t DH, int64_t DW, void *stream);
+int cusrl_dwconv2d_bwd_input(const float *dout, const float *w, float *dx, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
+                             int64_t KW, int64_t SH, int64_t SW, int64_t PH, int64_t PW, int64_t DH, int64_t DW, void *stream);
+int cusrl_dwconv2d_bwd_params(const float *x, const float *dout, float *dw, float *dbias, double *partials, int64_t N, int64_t C,
+                              int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t SH, int64_t SW, int64_t PH, int64_t PW,
+                              int64_t DH, int64_t DW, void *stream);
+int64_t cusrl_dwconv2d_num_partials(int64_t N, int64_t C, int64_t Ho, int64_t Wo);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
