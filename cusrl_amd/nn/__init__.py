@@ -2,6 +2,9 @@ from cusrl_amd.nn.actor import Actor, Value
 from cusrl_amd.nn.activation import GeGlu, SwiGlu
 from cusrl_amd.nn.cnn import Cnn, CnnFactory
 from cusrl_amd.nn.causal_attn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
+from cusrl_amd.nn.bijector import (
+    Bijector, ExponentialBijector, IdentityBijector, SigmoidBijector, SoftplusBijector, make_bijector,
+)
 from cusrl_amd.nn.attention import MultiheadAttention, MultiheadCrossAttention, MultiheadSelfAttention, make_norm
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
 from cusrl_amd.nn.encoding import RotaryEmbedding
@@ -76,6 +79,12 @@ __all__ = [
     "LearnablePositionalEncoding2D",
     "SeparableConv2d",
     "SinusoidalPositionalEncoding2D",
+    "Bijector",
+    "ExponentialBijector",
+    "IdentityBijector",
+    "SigmoidBijector",
+    "SoftplusBijector",
+    "make_bijector",
 ]
 
 

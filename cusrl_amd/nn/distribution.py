@@ -15,71 +15,15 @@ import torch
 from torch import Tensor, distributions, nn
 from torch.nn.functional import one_hot
 
+from cusrl_amd.nn.bijector import (  # noqa: F401  (the family lived here: every earlier import keeps working)
+    Bijector, ExponentialBijector, IdentityBijector, SigmoidBijector, SoftplusBijector, make_bijector,
+)
 from cusrl_amd.nn.module import LinearFp32, Module, ModuleFactory, disable_autocast, linear_act
 
 __all__ = ["AdaptiveNormalDist", "Distribution", "NormalDist", "OneHotCategoricalDist", "make_bijector"]
 
 _LOG_SQRT_2PI = math.log(math.sqrt(2 * math.pi))
 _ENTROPY_CONST = 0.5 + 0.5 * math.log(2 * math.pi)
-
-
-# ----------------------------------------------------------------------------------------------- bijectors
-class Bijector(nn.Module):
-    def forward(self, input):
-        raise NotImplementedError
-
-    def inverse(self, input):
-        raise NotImplementedError
-
-
-class IdentityBijector(Bijector):
-    def forward(self, input):
-        return input
-
-    def inverse(self, input):
-        return input
-
-
-class ExponentialBijector(Bijector):
-    def __init__(self, min_value: float = 0.01, max_value: float = 1.0):
-        super().__init__()
-        self.min_value, self.max_value = min_value, max_value
-        self.min_input, self.max_input = math.log(min_value), math.log(max_value)
-
-    def forward(self, input):
-        if isinstance(input, Tensor):
-            return torch.exp(input.clamp(self.min_input, self.max_input))
-        return math.exp(min(max(input, self.min_input), self.max_input))
-
-    def inverse(self, input):
-        if isinstance(input, Tensor):
-            return torch.log(input.clamp(self.min_value, self.max_value))
-        return math.log(min(max(input, self.min_value), self.max_value))
-
-
-class SoftplusBijector(Bijector):
-    def forward(self, input):
-        if isinstance(input, Tensor):
-            return nn.functional.softplus(input)
-        return math.log1p(math.exp(input))
-
-    def inverse(self, input):
-        if isinstance(input, Tensor):
-            return input + torch.log(-torch.expm1(-input))
-        return input + math.log(-math.expm1(-input))
-
-
-def make_bijector(spec) -> Bijector:
-    if spec is None:
-        return IdentityBijector()
-    if isinstance(spec, Bijector):
-        return spec
-    name, _, params = str(spec).partition("_")
-    args = [float(p) for p in params.split("_") if p]
-    table = {"identity": IdentityBijector, "exp": ExponentialBijector, "softplus": SoftplusBijector}
-    if name not in table:
-        raise ValueError(f"Unknown bijector '{spec}'")
-    return table[name](*args)
 
 
 # ----------------------------------------------------------------------------------------------- distributions

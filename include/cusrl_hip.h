@@ -1069,6 +1069,30 @@ int cusrl_dwconv2d_bwd_params(const float *x, const float *dout, float *dw, floa
                               int64_t DH, int64_t DW, void *stream);
 int64_t cusrl_dwconv2d_num_partials(int64_t N, int64_t C, int64_t Ho, int64_t Wo);
 
+/* ---- std bijectors — the bounded sigmoid and the bounded softplus behind a policy's standard deviation,
+ * cusrl/nn/layer/bijector.py:76-126 (additive entries of ABI 7; csrc/bijector.hip).  x, y, dy, dx: contiguous fp32 [n].  ONE
+ * launch each; the launch shape of cusrl_column_affine_*: 4-byte aligned pointers work (16-byte lanes when n % 4 == 0 and every
+ * pointer is 16-byte aligned, 4-byte lanes otherwise: the same bits), grid capped with a stride over the rest, 64-bit element
+ * indices.  y may be x and dx may be dy.  Every step is one rounded fp32 operation (no fma) with the accurate expf / log1pf;
+ * s(v) = 1 / (1 + expf(-v)).  The backward recomputes from x: no output is saved.  The float parameters are the fp32 roundings
+ * of the module's Python floats, which is what torch makes of them.
+ *
+ *   kind                 p0, p1, p2                       cusrl_bijector_fwd: y =                    cusrl_bijector_bwd: dx =
+ *   BIJECTOR_SIGMOID     min, range, (unused)             min + range s(x)                  (:86)    dy range (1 - s(x)) s(x)
+ *   BIJECTOR_SOFTPLUS    scale, min_input, max_input      (z > 20 ? z : log1pf(expf(z))) / scale     dy (z > 20 ? 1 : s(z)) where
+ *                                                         with z = clamp(x, min_input, max_input) scale     min_input <= x <= max_input (edges
+ *                                                         (:110-111; 20 is torch's softplus threshold)       inclusive), exactly 0.0f elsewhere
+ * A NaN x gives a NaN y and, for the softplus, dx = 0.0f (torch's clamp backward); NaN and +-Inf in x or dy otherwise come out
+ * where torch's expression puts them.
+ *
+ * n == 0 launches nothing and writes nothing.  CUSRL_E_INVALID, nothing launched: a NULL pointer, n < 0, an unknown kind, and for
+ * the softplus scale <= 0 or min_input > max_input (a NaN among them included).  CUSRL_E_UNSUPPORTED: more lanes than a grid
+ * of 32-bit extent has threads (n / 4, or n on the 4-byte path, above INT32_MAX * 256). */
+#define CUSRL_BIJECTOR_SIGMOID 0
+#define CUSRL_BIJECTOR_SOFTPLUS 1
+int cusrl_bijector_fwd(int kind, const float *x, float *y, int64_t n, float p0, float p1, float p2, void *stream);
+int cusrl_bijector_bwd(int kind, const float *x, const float *dy, float *dx, int64_t n, float p0, float p1, float p2, void *stream);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
