@@ -1,4 +1,5 @@
 from cusrl_amd.hook.on_policy.advantage import AdvantageNormalization, AdvantageReduction
+from cusrl_amd.hook.on_policy.buffer_schedule import OnPolicyBufferCapacitySchedule
 from cusrl_amd.hook.on_policy.common import OnPolicyPreparation
 from cusrl_amd.hook.on_policy.gae import GeneralizedAdvantageEstimation
 from cusrl_amd.hook.on_policy.gradient_clipping import GradientClipping
@@ -15,6 +16,7 @@ __all__ = [
     "GeneralizedAdvantageEstimation",
     "GradientClipping",
     "MiniBatchWiseLRSchedule",
+    "OnPolicyBufferCapacitySchedule",
     "OnPolicyPreparation",
     "OnPolicyStatistics",
     "PpoSurrogateLoss",

@@ -68,9 +68,34 @@ def capture_signature(agent) -> tuple:
     through a schedule, ``ObservationNormalization.freeze()``, ``set_inference_mode``) sends the graph back to its
     eager warm-up + re-capture."""
     parts = [agent.deterministic, agent.inference_mode]
-    for hook in agent.hook:
+    pending = list(agent.hook)
+    while pending:
+        hook = pending.pop(0)
         parts.append((hook.name, hook._active, tuple((name, _freeze(getattr(hook, name, None))) for name in sorted(hook._mutable))))
+        pending[:0] = getattr(hook, "_hooks", ())  # the hooks of a nested composite (OptimizationStage), in place
     return tuple(parts)
+
+
+class _Settling:
+    """Hysteresis of re-capture against a signature that keeps moving (a schedule that changes a hook's weight before every
+    iteration would otherwise have every region captured anew every iteration, each capture used once): a region whose hook
+    signature changed in iteration k runs eagerly for the rest of k and is captured again in the first later iteration that
+    begins under the signature the previous one ended with.  ``holds`` is asked once per use of the region.  Only the hook part
+    of the signature counts: a changed buffer layout is a one-off and re-captures at once, as it always has."""
+
+    def __init__(self, agent):
+        self.agent = agent
+        self.signature: tuple | None = None
+        self.changed_in: int | None = None
+        self.repeated = False  # the latest change came one iteration after another one
+
+    def holds(self, signature: tuple) -> bool:
+        iteration = self.agent.iteration
+        if self.signature is not None and signature != self.signature and self.changed_in != iteration:
+            self.repeated = self.changed_in == iteration - 1
+            self.changed_in = iteration
+        self.signature = signature
+        return self.changed_in != iteration
 
 
 class TrackedMetadata(dict):
@@ -160,6 +185,7 @@ class _Capture:
 
     MAX_TAPS = 256  # (a whole-rollout graph taps every env step's metrics)
     censuses: list[dict] = []  # node census of the most recent captures of the process (tests, scripts/graph_census.py)
+    counts: dict[str, int] = {}  # captures of the process so far, by region (the qualified name of the captured body)
 
     def capture(self, fn, stream: torch.cuda.Stream, pool=None):
         for values, _, record in self.stage_metrics(self.agent.metrics):  # an earlier capture's sums: its accumulator goes away
@@ -215,6 +241,7 @@ class _Capture:
             if self.census["memset"]:
                 raise RuntimeError(f"{self.census['memset']} memset nodes left in a captured region after the replacement")
         self.census["region"] = getattr(fn, "__qualname__", "region")
+        _Capture.counts[self.census["region"]] = _Capture.counts.get(self.census["region"], 0) + 1
         _Capture.censuses.append(self.census)
         del _Capture.censuses[:-512]
         graph.instantiate()
@@ -269,6 +296,7 @@ class GraphedTrainStep:
         self.graph_collectives = configure_distributed() and native_comm() is not None
         self.single_graph = not configure_distributed() or self.graph_collectives
         self.signature: tuple | None = None
+        self.settling = _Settling(agent)
         # fields of the batch the step reads: learned by the eager warm-up (which gathers everything), so that the
         # captured gather moves only those leaves (LazyBatch, template/buffer.py)
         self.hot_fields: set[str] = set()
@@ -367,6 +395,7 @@ class GraphedTrainStep:
         if agent.flat_optimizer is not None:
             agent.flat_optimizer.refresh()  # learning-rate changes reach the captured step through device memory
         signature = (capture_signature(agent), agent.buffer.layout_version)
+        settled = self.settling.holds(signature[0])
         if self.state == 2 and signature != self.signature:
             for values, reset, record in self.stage_metrics(agent.metrics):  # (now: the flags below describe the NEXT capture)
                 agent.metrics.defer(values.clone(), record)
@@ -375,7 +404,9 @@ class GraphedTrainStep:
                 self.deferred_loss.armed = self.deferred_loss.value_armed = False  # the new capture records its own launches
             self.state = 1  # a host-side value the capture froze has changed: capture again (the warm-up is still valid)
         self.signature = signature
-        if self.state == 0:  # eager on the capture stream: warms rocBLAS / allocator and performs this real step
+        # eager on the capture stream: warms rocBLAS / allocator and performs this real step; also while the hook signature
+        # is on the move (_Settling)
+        if self.state == 0 or (self.state == 1 and not settled):
             self.stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self.stream):
                 self._phase_a()
@@ -635,18 +666,20 @@ class GraphedRegion:
         self.stream: torch.cuda.Stream = agent._graph_stream
         self.state = 0
         self.signature: tuple | None = None
+        self.settling = _Settling(agent)
         self.outputs = None
 
     def run(self, *extra):
         agent = self.agent
         signature = (capture_signature(agent), agent.buffer.layout_version, extra)
+        settled = self.settling.holds(signature[0])
         if self.state == 2 and signature != self.signature:
             self.state = 1
         self.signature = signature
         if self.state == 2:
             self.capture.replay()
             return self.outputs
-        if self.state == 0:
+        if self.state == 0 or not settled:  # (the hook signature is on the move: eager until it holds, _Settling)
             self.stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self.stream):
                 outputs = self.fn()
@@ -761,6 +794,7 @@ class GraphedRolloutStep:
         self.stream: torch.cuda.Stream = self.agent._graph_stream
         self.steps: dict[tuple, dict] = {}
         self.signature: tuple | None = None
+        self.settling = _Settling(self.agent)
         # persistent device state shared by every step graph
         env, device = trainer.environment, self.agent.device
         n = env.num_instances
@@ -856,10 +890,13 @@ class GraphedRolloutStep:
         buffer layout) with the current values; a change sends every step graph back to capture."""
         agent = self.agent
         signature = (capture_signature(agent), agent.buffer.layout_version)
+        # a first change re-captures in this very rollout; a hook signature that moved in the previous iteration as well is on a
+        # schedule: the steps run eagerly until an iteration begins under the signature the previous one began with (_Settling)
+        moving = not self.settling.holds(signature[0]) and self.settling.repeated
         if signature != self.signature:
             self.flush_metrics()
             for entry in self.steps.values():
-                entry["state"] = min(entry["state"], 1)
+                entry["state"] = 0 if moving else min(entry["state"], 1)
             self.rollouts.clear()
             self.signature = signature
             agent.actor.noise_shape = None  # (set again by the step bodies that take the fused explore pass under these flags)

@@ -317,13 +317,20 @@ class HookComposite(Hook):
     post_act = _fan_out("post_act")
     post_step = _fan_out("post_step")
     pre_update = _fan_out("pre_update")
-    pre_objective = _fan_out("pre_objective")
     pre_optim = _fan_out("pre_optim")
     post_optim = _fan_out("post_optim")
     post_objective = _fan_out("post_objective")
     post_update = _fan_out("post_update")
     apply_schedule = _fan_out("apply_schedule")
     on_replay = _fan_out("on_replay")
+
+    def pre_objective(self, metadata, batch):
+        # flags read hook by hook, not up front: a control hook standing in front (ConditionalObjectiveActivation) switches
+        # later hooks on or off for this very step
+        inference = self.agent.inference_mode
+        for hook in self._hooks:
+            if hook._active and not (inference and hook._training_only):
+                hook.pre_objective(metadata, batch)
 
     def should_update(self, transition) -> bool:
         return all(hook.should_update(transition) for hook in self.active_hooks())
