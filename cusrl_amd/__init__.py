@@ -6,7 +6,7 @@ gather, PPO objective forward+backward) runs as hand-written HIP kernels for gfx
 """
 
 from cusrl_amd import hook, nn, preset, sampler, template, testing, utils
-from cusrl_amd.hook import NextStatePrediction, PolicyDistillationLoss, ReturnPrediction, StateEstimation, StatePrediction
+from cusrl_amd.hook import NextStatePrediction, PolicyDistillation, PolicyDistillationLoss, ReturnPrediction, StateEstimation, StatePrediction
 from cusrl_amd.nn import (
     Actor, AdaptiveNormalDist, Denormalization, DenormalizationFactory, Distribution, GradientPenaltyLoss, Gru, L2RegularizationLoss,
     LinearFp32, Lstm, Mlp, Module, ModuleFactory, NormalDist, NormalNllLoss, Normalization, NormalizationFactory,
@@ -22,6 +22,7 @@ from cusrl_amd.nn import (
 )
 from cusrl_amd.nn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
 from cusrl_amd.nn import Cnn, CnnFactory, LearnablePositionalEncoding2D, SeparableConv2d, SinusoidalPositionalEncoding2D
+from cusrl_amd.nn import ExpertPolicy, Identity, StubModule
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
 )
@@ -128,4 +129,8 @@ __all__ = [
     "LearnablePositionalEncoding2D",
     "SeparableConv2d",
     "SinusoidalPositionalEncoding2D",
+    "ExpertPolicy",
+    "Identity",
+    "PolicyDistillation",
+    "StubModule",
 ]

@@ -1,5 +1,5 @@
 from cusrl_amd.hook.auxiliary.amp import AdversarialMotionPrior
-from cusrl_amd.hook.auxiliary.distillation import PolicyDistillationLoss
+from cusrl_amd.hook.auxiliary.distillation import PolicyDistillation, PolicyDistillationLoss
 from cusrl_amd.hook.auxiliary.estimation import StateEstimation
 from cusrl_amd.hook.auxiliary.representation import NextStatePrediction, ReturnPrediction, StatePrediction
 from cusrl_amd.hook.auxiliary.rnd import RandomNetworkDistillation
@@ -20,6 +20,7 @@ __all__ = [
     "MirrorDef",
     "MirrorSymmetryLoss",
     "NextStatePrediction",
+    "PolicyDistillation",
     "PolicyDistillationLoss",
     "RandomNetworkDistillation",
     "ReturnPrediction",

@@ -9,6 +9,7 @@ from cusrl_amd.nn.attention import MultiheadAttention, MultiheadCrossAttention, 
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
 from cusrl_amd.nn.encoding import RotaryEmbedding
 from cusrl_amd.nn.encoding2d import LearnablePositionalEncoding2D, SinusoidalPositionalEncoding2D
+from cusrl_amd.nn.expert import ExpertPolicy
 from cusrl_amd.nn.feedforward import FeedForward
 from cusrl_amd.nn.gate import (
     Gate, GruGate, HighwayGate, InputGate, OutputGate, PassthroughGate, ResidualGate, SigmoidTanhGate, gate_map, get_gate_cls,
@@ -21,6 +22,7 @@ from cusrl_amd.nn.rnn import Gru, Lstm, Rnn
 from cusrl_amd.nn.separable_conv import SeparableConv2d
 from cusrl_amd.nn.sequential import Sequential, SequentialFactory
 from cusrl_amd.nn.simba import Simba, SimbaBlock, SimbaFactory
+from cusrl_amd.nn.stub import Identity, StubModule
 from cusrl_amd.nn.transformer import TransformerDecoderLayer, TransformerEncoderLayer
 
 __all__ = [
@@ -85,6 +87,9 @@ __all__ = [
     "SigmoidBijector",
     "SoftplusBijector",
     "make_bijector",
+    "ExpertPolicy",
+    "Identity",
+    "StubModule",
 ]
 
 

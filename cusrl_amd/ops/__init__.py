@@ -28,6 +28,7 @@ from cusrl_amd.ops.advantage import (
 from cusrl_amd.ops.affine import ColumnAffine, column_affine, column_affine_supported
 from cusrl_amd.ops.attention import Rope, Sdpa, rope, rope_supported, sdpa, sdpa_backward, sdpa_supported
 from cusrl_amd.ops.band_attention import BandSdpa, band_mask, band_sdpa, band_sdpa_backward, band_sdpa_supported
+from cusrl_amd.ops.bias_act import bias_act, bias_act_supported
 from cusrl_amd.ops.bijector import BijectorFunction, bijector_supported, sigmoid_bijector, softplus_bijector
 from cusrl_amd.ops.auxiliary import (
     accumulate_scalars_, action_smoothness_fwd_bwd, amp_prepare, amp_prepare_supported, amp_style_reward_, amp_style_reward_mean_, bce_pair_fwd_bwd,

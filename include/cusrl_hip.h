@@ -1093,6 +1093,26 @@ int64_t cusrl_dwconv2d_num_partials(int64_t N, int64_t C, int64_t Ho, int64_t Wo
 int cusrl_bijector_fwd(int kind, const float *x, float *y, int64_t n, float p0, float p1, float p2, void *stream);
 int cusrl_bijector_bwd(int kind, const float *x, const float *dy, float *dx, int64_t n, float p0, float p1, float p2, void *stream);
 
+/* ---- bias + activation behind a bias-free GEMM — the per-step query of a frozen expert policy (cusrl_amd/nn/expert.py, the
+ * teacher of cusrl/hook/auxiliary/distillation.py:50-97; additive entry of ABI 7; csrc/bias_act.hip) ----
+ * ONE launch:  out[r, h] = act(x[r, h] + bias[h]),  x and out [rows, H] contiguous fp32, bias [H]; out may be x.  The addition
+ * is one rounded fp32 operation, then
+ *   ACT_IDENTITY   v
+ *   ACT_RELU       v > 0 ? v : 0                     (a NaN stays a NaN)
+ *   ACT_ELU        v > 0 ? v : alpha * expm1f(v)     (torch's formula; `alpha` is read by this code only)
+ *   ACT_TANH       tanhf(v)                          (+-1 for a large |v|: nothing overflows)
+ * NaN propagates; -0.0 and +-Inf come out as the formula gives them.  4-byte aligned pointers work: 16-byte accesses when
+ * H % 4 == 0 and all three pointers are 16-byte aligned, 4-byte accesses otherwise, the same bits either way.  A thread keeps its
+ * slice of the bias in registers while it walks rows.  No host synchronisation: the launch may be captured.
+ * CUSRL_E_INVALID, nothing launched: a NULL pointer, rows < 1 or H < 1.  CUSRL_E_UNSUPPORTED, nothing launched: an unknown
+ * activation code, rows * H beyond int64, or a row of more than 65535 * 256 column lanes. */
+#define CUSRL_ACT_IDENTITY 0
+#define CUSRL_ACT_RELU 1
+#define CUSRL_ACT_ELU 2
+#define CUSRL_ACT_TANH 3
+int cusrl_bias_act(const float *x, const float *bias, float *out, int64_t rows, int64_t H, int activation, float alpha,
+                   void *stream);
+
 
 /* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
