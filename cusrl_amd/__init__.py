@@ -22,7 +22,7 @@ from cusrl_amd.nn import (
 )
 from cusrl_amd.nn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
 from cusrl_amd.nn import Cnn, CnnFactory, LearnablePositionalEncoding2D, SeparableConv2d, SinusoidalPositionalEncoding2D
-from cusrl_amd.nn import ExpertPolicy, Identity, StubModule
+from cusrl_amd.nn import ExpertPolicy, Identity, InferenceWrapper, StubModule
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
 )
@@ -33,10 +33,16 @@ from cusrl_amd.template import (
     Environment,
     EnvironmentSpec,
     Hook,
+    Logger,
+    LoggerFactory,
     OptimizerFactory,
+    Player,
+    PlayerHook,
     Sampler,
     Trainer,
     TrainerHook,
+    Trial,
+    make_logger_factory,
 )
 from cusrl_amd.utils import CONFIG as config
 from cusrl_amd.utils import device, set_global_seed
@@ -133,4 +139,11 @@ __all__ = [
     "Identity",
     "PolicyDistillation",
     "StubModule",
+    "InferenceWrapper",
+    "Logger",
+    "LoggerFactory",
+    "Player",
+    "PlayerHook",
+    "Trial",
+    "make_logger_factory",
 ]

@@ -137,7 +137,18 @@ __global__ __launch_bounds__(kBlock) void categorical_sample_logp_kernel(const f
 // quadratic flag re-read would matter) falls back to an atomic ticket: same slots, unspecified order within the step.
 constexpr int64_t kOrderedStatsMaxEnvs = 262144;
 
-template <bool kOrdered>
+// What the play loop's epilogue (cusrl_play_epilogue) computes on top of the step epilogue: the per-env episode counter and
+// the number of envs still below the episode target.  workspace[0] is the running count of this launch, workspace[1] its
+// ticket counter; both are zero between launches (the block that draws the last ticket puts them back).
+constexpr int kPlayWorkspaceWords = 2;
+struct PlayArgs {
+    int64_t *episode_count;
+    int64_t target_episodes;
+    int32_t *unfinished_out;
+    uint32_t *workspace;
+};
+
+template <bool kOrdered, bool kPlay = false>
 __device__ __forceinline__ void episode_stats_body(const int block, const int num_blocks, uint8_t *__restrict__ done_copy,
                                                    const float *__restrict__ reward,
                                                    const uint8_t *__restrict__ done,
@@ -147,7 +158,8 @@ __device__ __forceinline__ void episode_stats_body(const int block, const int nu
                                                    unsigned long long *__restrict__ num_episodes,
                                                    double *__restrict__ step_reward_sum,
                                                    int64_t *__restrict__ indices_out, int32_t *__restrict__ count_out,
-                                                   int64_t N, int D, int64_t R, int parity) {
+                                                   int64_t N, int D, int64_t R, int parity,
+                                                   const PlayArgs &play = PlayArgs{}) {
     // `block` of `num_blocks`: the launch's block index (the plain launch) or the epilogue part of a fused launch;
     // done_copy != NULL: the flag is ALSO stored there (the rollout buffer's `done` slab of this step)
     // `done_b` != NULL: the flag of env n is done[n] | done_b[n] (terminated | truncated, actor_critic.py:277), written
@@ -219,6 +231,28 @@ __device__ __forceinline__ void episode_stats_body(const int block, const int nu
         if (threadIdx.x == 0) atomicAdd(step_reward_sum + d, block_total);
     }
     if (active) episode_len[n] = finished ? 0.0f : len;
+    if constexpr (kPlay) {
+        // episode_count[n] += finished[n]; *unfinished_out = #{n : episode_count[n] < target} (player.py:246,269).  The count
+        // crosses blocks as an integer: every block adds its own into workspace[0], then draws a ticket from workspace[1]
+        // (acq_rel: its add is ordered in front, the last drawer's read behind); the block with the last ticket takes the
+        // total, leaves both words zero for the next launch and publishes — exact in any order of arrival.
+        int open = 0;
+        if (active) {
+            const int64_t played = play.episode_count[n] + (finished ? 1 : 0);
+            if (finished) play.episode_count[n] = played;
+            open = played < play.target_episodes ? 1 : 0;
+        }
+        const int block_open = block_sum(open, iscratch);
+        if (threadIdx.x == 0) {
+            __hip_atomic_fetch_add(play.workspace, uint32_t(block_open), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t ticket = __hip_atomic_fetch_add(play.workspace + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            if (ticket == uint32_t(num_blocks - 1)) {
+                const uint32_t total = __hip_atomic_exchange(play.workspace, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(play.workspace + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(play.unfinished_out, int32_t(total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
 }
 
 
@@ -263,6 +297,13 @@ __global__ __launch_bounds__(kBlock) void step_epilogue_push_kernel(const Epilog
                                  e.indices_out, e.count_out, e.N, e.D, e.R, e.parity);
     else
         push_body<0>(tab, int(blockIdx.x) - e.epilogue_blocks);
+}
+
+// The step epilogue of the play loop (template/player.py): the same body, plus the episode counters and the unfinished count.
+__global__ __launch_bounds__(kBlock) void play_epilogue_kernel(const EpilogueArgs e, const PlayArgs play) {
+    episode_stats_body<true, true>(blockIdx.x, e.epilogue_blocks, nullptr, e.reward, e.terminated, e.truncated, e.done_out,
+                                   e.episode_rew, e.episode_len, e.ring_rew, e.ring_len, e.num_episodes, e.step_reward_sum,
+                                   e.indices_out, e.count_out, e.N, e.D, e.R, e.parity, play);
 }
 
 // ---- intrinsic-reward epilogues: one launch instead of sub / square / mean / mul / add_ (RND) or
@@ -435,5 +476,29 @@ extern "C" int cusrl_step_epilogue(const float *reward, const uint8_t *terminate
                        terminated, truncated, done_out, episode_rew, episode_len, ring_rew, ring_len,
                        reinterpret_cast<unsigned long long *>(num_episodes), step_reward_sum, indices_out, count_out, N,
                        int(D), R, parity);
+    return launch_status();
+}
+
+extern "C" int64_t cusrl_play_epilogue_workspace_words(void) { return kPlayWorkspaceWords; }
+
+extern "C" int cusrl_play_epilogue(const float *reward, const uint8_t *terminated, const uint8_t *truncated, uint8_t *done_out,
+                                   float *episode_rew, float *episode_len, float *ring_rew, float *ring_len,
+                                   uint64_t *num_episodes, double *step_reward_sum, int64_t *indices_out, int32_t *count_out,
+                                   int64_t N, int64_t D, int64_t R, int parity, int64_t *episode_count,
+                                   int64_t target_episodes, int32_t *unfinished_out, uint32_t *workspace, void *stream) {
+    if (N <= 0 || D <= 0 || R <= 0 || (parity != 0 && parity != 1) || target_episodes < 1) return CUSRL_E_INVALID;
+    if (!reward || !terminated || !truncated || !done_out || !episode_rew || !episode_len || !ring_rew || !ring_len ||
+        !num_episodes || !step_reward_sum || !indices_out || !count_out || !episode_count || !unfinished_out || !workspace)
+        return CUSRL_E_INVALID;
+    if (D > INT32_MAX || N > kOrderedStatsMaxEnvs) return CUSRL_E_UNSUPPORTED;
+    EpilogueArgs e;
+    e.reward = reward, e.terminated = terminated, e.truncated = truncated, e.done_out = done_out, e.done_slab = nullptr;
+    e.episode_rew = episode_rew, e.episode_len = episode_len, e.ring_rew = ring_rew, e.ring_len = ring_len;
+    e.num_episodes = reinterpret_cast<unsigned long long *>(num_episodes);
+    e.step_reward_sum = step_reward_sum, e.indices_out = indices_out, e.count_out = count_out;
+    e.N = N, e.R = R, e.D = int(D), e.parity = parity;
+    e.epilogue_blocks = int(ceil_div(N, kBlock));
+    const PlayArgs play{episode_count, target_episodes, unfinished_out, workspace};
+    hipLaunchKernelGGL(play_epilogue_kernel, dim3(uint32_t(e.epilogue_blocks)), dim3(kBlock), 0, as_stream(stream), e, play);
     return launch_status();
 }

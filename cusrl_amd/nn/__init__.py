@@ -14,6 +14,7 @@ from cusrl_amd.nn.feedforward import FeedForward
 from cusrl_amd.nn.gate import (
     Gate, GruGate, HighwayGate, InputGate, OutputGate, PassthroughGate, ResidualGate, SigmoidTanhGate, gate_map, get_gate_cls,
 )
+from cusrl_amd.nn.inference import InferenceWrapper
 from cusrl_amd.nn.loss import L2RegularizationLoss, NormalNllLoss
 from cusrl_amd.nn.module import LinearFp32, Mlp, Module, ModuleFactory
 from cusrl_amd.nn.normalization import Denormalization, DenormalizationFactory, Normalization, NormalizationFactory
@@ -89,6 +90,7 @@ __all__ = [
     "make_bijector",
     "ExpertPolicy",
     "Identity",
+    "InferenceWrapper",
     "StubModule",
 ]
 

@@ -63,7 +63,8 @@ from cusrl_amd.ops.recurrent import (
     lstm_gates_forward, rnn_cell_backward, rnn_cell_forward,
 )
 from cusrl_amd.ops.rollout import (
-    PendingStepEpilogue, categorical_sample_logp, episode_stats, normal_sample_logp, step_epilogue, synthetic_env_step,
+    PendingStepEpilogue, categorical_sample_logp, episode_stats, normal_sample_logp, play_epilogue, play_epilogue_workspace,
+    step_epilogue, synthetic_env_step,
 )
 from cusrl_amd.ops.symmetry import (
     _mirror_table, _rows_2d, mirror_mse_fwd_bwd, mirror_rows, mirror_rows_bwd, symmetric_head_bwd, symmetric_head_fwd,

@@ -94,6 +94,43 @@ def step_epilogue(reward, terminated, truncated, done_out, episode_rew, episode_
     )
 
 
+def play_epilogue_workspace(device) -> torch.Tensor:
+    """The zeroed ticket workspace of :func:`play_epilogue` — allocated (and zeroed) once, every launch leaves it zero."""
+    from cusrl_amd import _native
+
+    return torch.zeros(int(_native.lib().cusrl_play_epilogue_workspace_words()), dtype=torch.int32, device=device)
+
+
+def play_epilogue(reward, terminated, truncated, done_out, episode_rew, episode_len, ring_rew, ring_len, num_episodes,
+                  step_reward_sum, indices_out, count_out, parity: int, episode_count, target_episodes: int, unfinished_out,
+                  workspace) -> None:
+    """:func:`step_epilogue` of the play loop (``cusrl_play_epilogue``, ONE launch): on top of it ``episode_count += done``
+    (int64 ``[N]``, in place) and ``unfinished_out`` = number of envs still below ``target_episodes`` (one int32 on the device or
+    in pinned host memory).  ``workspace``: :func:`play_epilogue_workspace`, zero before and after every launch."""
+    reward = _f32(reward, "reward")
+    terminated, truncated = _flag(terminated, "terminated"), _flag(truncated, "truncated")
+    require_device(episode_count, "episode_count"), require_device(workspace, "workspace")
+    N, D = reward.shape
+    if terminated.numel() != N or truncated.numel() != N or done_out.numel() != N or indices_out.numel() < N:
+        raise ValueError("play_epilogue: inconsistent sizes")
+    if episode_rew.shape != (N, D) or episode_len.numel() != N or ring_rew.shape[-1] != D or step_reward_sum.numel() != D:
+        raise ValueError(f"play_epilogue: the reward is [{N}, {D}] but the accumulators were built for {tuple(episode_rew.shape)}")
+    if episode_count.dtype != torch.int64 or episode_count.numel() != N or not episode_count.is_contiguous():
+        raise TypeError("play_epilogue: 'episode_count' must be a contiguous int64 [N] device tensor")
+    if unfinished_out.dtype != torch.int32 or unfinished_out.numel() != 1 or not (unfinished_out.is_cuda or unfinished_out.is_pinned()):
+        raise TypeError("play_epilogue: 'unfinished_out' must be a 1-element int32 tensor on the device or in pinned host memory")
+    if workspace.dtype != torch.int32 or workspace.numel() < 2 or not workspace.is_contiguous():
+        raise TypeError("play_epilogue: 'workspace' must come from play_epilogue_workspace()")
+    _observed(
+        "cusrl_play_epilogue",
+        reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), done_out.data_ptr(), episode_rew.data_ptr(),
+        episode_len.data_ptr(), ring_rew.data_ptr(), ring_len.data_ptr(), num_episodes.data_ptr(), step_reward_sum.data_ptr(),
+        indices_out.data_ptr(), count_out.data_ptr(), N, D, ring_len.numel(), int(parity), episode_count.data_ptr(),
+        int(target_episodes), unfinished_out.data_ptr(), workspace.data_ptr(),
+        nbytes=lambda: N * (12 * D + 11 + 16),
+    )
+
+
 class PendingStepEpilogue:
     """A step epilogue whose launch has been handed to the buffer push of the same env step (``cusrl_step_epilogue_push``:
     ONE launch for both).  ``launch()`` issues it on its own — the push could not take it."""

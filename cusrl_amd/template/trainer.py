@@ -1,6 +1,6 @@
 """Outer training loop (counterpart of cusrl/template/trainer.py:33-416): rollout until the agent asks for an
-update, update, log.  Checkpointing goes through an optional logger object with ``save_checkpoint``; version
-dumps, trial folders and console boxes of the reference are out of scope."""
+update, update, log.  Checkpointing goes through an optional logger object with ``save_checkpoint`` (``template/logger.py``
+ships one); version dumps and console boxes of the reference are out of scope."""
 
 from __future__ import annotations
 
@@ -24,10 +24,11 @@ class EnvironmentStats:
     (``cusrl_episode_stats``) with no host round trip; on CPU / NumPy envs it is the reference's torch-op form.
     """
 
-    def __init__(self, num_envs: int, reward_dim: int = 1, buffer_size: int = 100, device=None):
+    def __init__(self, num_envs: int, reward_dim: int = 1, buffer_size: int = 100, device=None, on_device: bool | None = None):
         self.num_envs, self.reward_dim, self.buffer_size = num_envs, reward_dim, buffer_size
         self.device = torch.device("cpu" if device is None else device)
-        self.on_device = self.device.type == "cuda"
+        # (`on_device=False` on a GPU: the reference's torch-op form over device tensors — the play loop's host bookkeeping)
+        self.on_device = self.device.type == "cuda" and on_device is not False
         zeros = lambda *shape, **kw: torch.zeros(shape, device=self.device, **kw)  # noqa: E731
         self.episode_rew, self.episode_len = zeros(num_envs, reward_dim), zeros(num_envs, 1)
         self.rew_buffer, self.len_buffer = zeros(buffer_size, reward_dim), zeros(buffer_size, 1)
@@ -61,6 +62,17 @@ class EnvironmentStats:
 
         ops.step_epilogue(reward, terminated, truncated, done_out, self.episode_rew, self.episode_len, self.rew_buffer,
                           self.len_buffer, self._episodes_dev, self._reward_sum, indices_out, count_out, self._parity)
+        self.count_step()
+
+    def track_play(self, reward, terminated, truncated, done_out, indices_out, count_out, episode_count, target_episodes,
+                   unfinished_out, workspace):
+        """:meth:`track_fused` of the play loop (``cusrl_play_epilogue``, still one launch): also ``episode_count += done`` and
+        the number of envs below ``target_episodes`` into ``unfinished_out`` (player.py:246,269)."""
+        from cusrl_amd import ops
+
+        ops.play_epilogue(reward, terminated, truncated, done_out, self.episode_rew, self.episode_len, self.rew_buffer,
+                          self.len_buffer, self._episodes_dev, self._reward_sum, indices_out, count_out, self._parity,
+                          episode_count, target_episodes, unfinished_out, workspace)
         self.count_step()
 
     def defer_fused(self, reward, terminated, truncated, done_out, indices_out, count_out):

@@ -2,7 +2,7 @@ from cusrl_amd.utils import distributed, scheduler
 from cusrl_amd.utils.config import CONFIG, configure_distributed, device, is_autocast_available
 from cusrl_amd.utils.distributed import is_main_process
 from cusrl_amd.utils.metrics import Metrics
-from cusrl_amd.utils.misc import get_first, set_global_seed
+from cusrl_amd.utils.misc import get_first, set_global_seed, to_numpy
 from cusrl_amd.utils.scheduler import (
     CosineAnnealingScheduler,
     LessThan,
@@ -11,7 +11,7 @@ from cusrl_amd.utils.scheduler import (
     StepScheduler,
     TanhScheduler,
 )
-from cusrl_amd.utils.timing import Timer
+from cusrl_amd.utils.timing import Rate, Timer
 
 __all__ = [
     "CONFIG",
@@ -20,6 +20,7 @@ __all__ = [
     "Metrics",
     "NotLessThan",
     "PiecewiseLinearScheduler",
+    "Rate",
     "StepScheduler",
     "TanhScheduler",
     "Timer",
@@ -31,4 +32,5 @@ __all__ = [
     "is_main_process",
     "scheduler",
     "set_global_seed",
+    "to_numpy",
 ]

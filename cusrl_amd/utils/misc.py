@@ -14,7 +14,7 @@ import torch
 from cusrl_amd.utils import switches
 from cusrl_amd.utils.config import CONFIG
 
-__all__ = ["MISSING", "camel_to_snake", "get_first", "host_form", "set_global_seed"]
+__all__ = ["MISSING", "camel_to_snake", "get_first", "host_form", "set_global_seed", "to_numpy"]
 
 MISSING = object()
 
@@ -61,3 +61,13 @@ _CAMEL_2 = re.compile(r"([a-z0-9])([A-Z])")
 
 def camel_to_snake(name: str) -> str:
     return _CAMEL_2.sub(r"\1_\2", _CAMEL_1.sub(r"\1_\2", name)).lower()
+
+
+def to_numpy(value: Any) -> np.ndarray:
+    """NumPy arrays as they are, tensors detached and copied to the host, anything else through ``np.asarray``
+    (cusrl/utils/misc.py:184-201)."""
+    if isinstance(value, np.ndarray):
+        return value
+    if isinstance(value, torch.Tensor):
+        return value.detach().cpu().numpy()
+    return np.asarray(value)

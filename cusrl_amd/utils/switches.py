@@ -132,5 +132,11 @@ def read(key: str) -> Any:
     return switch.parse(os.environ.get(switch.name))
 
 
+def publish(name: str, value: str) -> None:
+    """Leave ``name=value`` in the process environment for whoever is started from here (the one variable the package WRITES
+    besides the seed: ``TRIAL_LOG_DIR``, the run directory of a ``Logger`` — cusrl/template/logger.py:94)."""
+    os.environ[name] = value
+
+
 def declared() -> tuple[Switch, ...]:
     return tuple(SWITCHES.values())

@@ -10,7 +10,7 @@ import torch
 
 from cusrl_amd.utils.config import device as resolve_device
 
-__all__ = ["Timer"]
+__all__ = ["Rate", "Timer"]
 
 
 class Timer:
@@ -110,3 +110,23 @@ class Timer:
         self.start(name)
         yield
         self.stop(name)
+
+
+class Rate:
+    """Run a loop at ``fps`` iterations per second (cusrl/utils/timing.py:182-212): ``tick()`` sleeps out the rest of the period;
+    the schedule stays anchored to the previous tick but never falls more than ``threshold`` seconds behind real time."""
+
+    def __init__(self, fps: float, threshold: float = 0.05):
+        if fps <= 0:
+            raise ValueError("'fps' must be greater than 0")
+        if threshold < 0:
+            raise ValueError("'threshold' must be greater than or equal to 0")
+        self.dt = 1.0 / fps
+        self.last_time = time.perf_counter()
+        self.threshold = threshold
+
+    def tick(self):
+        elapsed = time.perf_counter() - self.last_time
+        if elapsed < self.dt:
+            time.sleep(self.dt - elapsed)
+        self.last_time = max(self.last_time + self.dt, time.perf_counter() - self.threshold)

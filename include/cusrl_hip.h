@@ -395,6 +395,23 @@ int cusrl_step_epilogue_push(const float *reward, const uint8_t *terminated, con
                              int parity, const cusrl_field_t *fields, int n_fields, int done_field, int64_t cursor,
                              void *stream);
 
+/* cusrl_step_epilogue for the PLAY loop (cusrl/template/player.py:228-247; additive entry of ABI 7): everything
+ * cusrl_step_epilogue does — the same device code, same results — and in the same launch
+ *   episode_count[n] += (terminated[n] | truncated[n])           (player.py:269, int64 [N], device, in place)
+ *   *unfinished_out = #{n : episode_count[n] < target_episodes}   (player.py:246 — 0 ends the loop)
+ * unfinished_out: one int32 on the device or in pinned host memory, written once with a system-scope release store.
+ * workspace: cusrl_play_epilogue_workspace_words() uint32 words on the device, zeroed ONCE by the caller when allocated: the
+ * launch leaves them zero again (the block that draws the last ticket takes the integer total and resets both words), so
+ * consecutive launches on one stream need no preparation — no memset, no second kernel, no synchronisation.
+ * CUSRL_E_INVALID, nothing launched: a NULL pointer, N, D or R < 1, parity outside {0, 1}, target_episodes < 1;
+ * CUSRL_E_UNSUPPORTED, nothing launched: N > cusrl_step_epilogue_max_envs() (there is no ticket-slot form of it). */
+int cusrl_play_epilogue(const float *reward, const uint8_t *terminated, const uint8_t *truncated, uint8_t *done_out,
+                        float *episode_rew, float *episode_len, float *ring_rew, float *ring_len, uint64_t *num_episodes,
+                        double *step_reward_sum, int64_t *indices_out, int32_t *count_out, int64_t N, int64_t D, int64_t R,
+                        int parity, int64_t *episode_count, int64_t target_episodes, int32_t *unfinished_out,
+                        uint32_t *workspace, void *stream);
+int64_t cusrl_play_epilogue_workspace_words(void);
+
 /* ---- post-update policy statistics — cusrl/hook/on_policy/stats.py:28-40 for Normal policies ----
  * out[0] = mean_b KL(N(old_mean, old_std) || N(new_mean, new_std)) summed over the A action dims (kl_divergence),
  * out[1] = mean of advantage * exp(log N(action; new_mean, new_std) - old_logp)  (importance_weighted_advantage),
