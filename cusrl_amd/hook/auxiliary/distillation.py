@@ -60,7 +60,8 @@ class PolicyDistillation(PolicyDistillationLoss):
 
     Args:
         expert_path (str):
-            Path to the expert policy: a file written by ``ExpertPolicy.save``, or an exported TorchScript module.
+            Path to the expert policy: a file written by ``ExpertPolicy.save`` or by ``ActorCritic.export``, or an exported
+            TorchScript module.
         observation_name (str):
             Transition key used as input to the expert policy. Defaults to ``"observation"``.
         weight (float):
@@ -94,6 +95,11 @@ class PolicyDistillation(PolicyDistillationLoss):
         else:
             # (a file of another format is never unpickled: it is TorchScript, the reference's contract, or an error)
             expert = ExpertPolicy.try_load(self.expert_path, map_location=device)
+            if expert is None:
+                from cusrl_amd.nn.deployed import DeployedPolicy
+
+                # a policy file written by ActorCritic.export: callable, with a reset(done) — all this hook needs
+                expert = DeployedPolicy.try_load(self.expert_path, map_location=device)
             if expert is None:
                 expert = torch.jit.load(self.expert_path, map_location=device)
         # a plain attribute: not registered with the agent, so neither checkpointed nor handed to an optimizer

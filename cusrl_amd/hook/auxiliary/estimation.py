@@ -105,6 +105,13 @@ class StateEstimation(Hook):
     def post_step(self, transition):
         self.estimator.reset_memory(self._estimator_memory, transition["done"])
 
+    def export_stages(self, which: str = "actor"):
+        # pre_act writes the estimate beside the observation: the actor's input is untouched unless it is stored over it
+        if self.estimation_name == "observation":
+            raise ValueError(f"ActorCritic.export: hook '{self.name}' stores its estimate as the actor's observation; no export "
+                             "stage expresses an estimator in front of the actor")
+        return ()
+
     def objective(self, metadata, batch):
         source = batch[self.source_name][..., self.source_indices]
         estimation, _ = self.estimator(source, memory=batch.get("estimator_memory"), done=batch["done"])

@@ -72,6 +72,9 @@ class ObservationNanToNum(Hook):
     def post_step(self, transition):
         self._sanitize(transition.get("next_observation"), transition.get("next_state"))
 
+    def export_stages(self, which: str = "actor"):
+        return (({"kind": "nan_to_num", "nan": float(self.nan), "posinf": float(self.posinf), "neginf": float(self.neginf)}, {}),)
+
     def _sanitize(self, first: Tensor | None, second: Tensor | None):
         tensors = [t for t in (first, second) if t is not None]
         if not tensors:
@@ -213,6 +216,11 @@ class ObservationNormalization(Hook):
         self.observation_rms.var.copy_(self.state_rms.var[index])
         self.observation_rms.std.copy_(self.state_rms.std[index])
         self.observation_rms._count.copy_(self.state_rms._count)
+
+    def export_stages(self, which: str = "actor"):
+        """The actor sees observations, so its stage carries the OBSERVATION statistics (never the state's), as they stand."""
+        rms = self.observation_rms
+        return (({"kind": "normalize", "clamp": rms.clamp, "epsilon": float(rms.epsilon)}, {"mean": rms.mean, "std": rms.std}),)
 
     # ---- update
     def pre_update(self, buffer):

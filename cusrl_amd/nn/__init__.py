@@ -9,6 +9,7 @@ from cusrl_amd.nn.attention import MultiheadAttention, MultiheadCrossAttention, 
 from cusrl_amd.nn.distribution import AdaptiveNormalDist, Distribution, NormalDist, OneHotCategoricalDist
 from cusrl_amd.nn.encoding import RotaryEmbedding
 from cusrl_amd.nn.encoding2d import LearnablePositionalEncoding2D, SinusoidalPositionalEncoding2D
+from cusrl_amd.nn.deployed import DeployedPolicy
 from cusrl_amd.nn.expert import ExpertPolicy
 from cusrl_amd.nn.feedforward import FeedForward
 from cusrl_amd.nn.gate import (
@@ -88,6 +89,7 @@ __all__ = [
     "SigmoidBijector",
     "SoftplusBijector",
     "make_bijector",
+    "DeployedPolicy",
     "ExpertPolicy",
     "Identity",
     "InferenceWrapper",

@@ -1,5 +1,6 @@
 """Actor-critic agent: rollout into the HBM buffer, then minibatch PPO-style updates driven by hooks
-(counterpart of cusrl/template/actor_critic.py:23-320; the ONNX/JIT export part is out of scope).
+(counterpart of cusrl/template/actor_critic.py:23-418; ``export`` writes this package's own policy file, template/export.py —
+ONNX and TorchScript output are out of scope).
 
 Differences that matter on MI355X (semantics unchanged):
 * ``buffer.push`` is one HIP launch per env step; minibatches come from one gather launch (template/buffer.py);
@@ -689,3 +690,15 @@ class ActorCritic(Agent):
         if self.buffer_capacity != capacity:
             self.buffer_capacity = capacity
             self.buffer.resize(capacity)
+
+    def export(self, output_dir, name: str = "policy", *, with_environment_normalization: bool = True, action_clip=None) -> str:
+        """Write the actor as a self-contained policy file ``<output_dir>/<name>.pt`` (actor_critic.py:332-418; format
+        ``"cusrl_amd.policy"``, template/export.py) and return its path.  ``nn.DeployedPolicy.load`` runs it:
+        ``action = policy(observation)``, ``policy.reset(done)``.  The file carries what the hooks do to an observation at
+        deployment (``Hook.export_stages``, in hook order), the actor's backbone and mean head — the action is deterministic —
+        and, with ``with_environment_normalization``, the spec's ``action_denormalization``; ``action_clip``: ``(lo, hi)``,
+        scalars or one value per action.  An agent the stage set cannot express raises ``ValueError`` naming what was found."""
+        from cusrl_amd.template.export import export_policy
+
+        return export_policy(self, output_dir, name, with_environment_normalization=with_environment_normalization,
+                             action_clip=action_clip)

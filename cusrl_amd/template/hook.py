@@ -247,6 +247,13 @@ class Hook(Generic[AgentT]):
 
     def post_export(self, graph): ...
 
+    def export_stages(self, which: str = "actor") -> tuple:
+        """Extension (instead of the reference's ``pre_export`` / ``post_export`` graph rewiring): what this hook does to the
+        observation of network ``which`` at deployment, as ``(meta, tensors)`` stages of a ``nn.DeployedPolicy``
+        (``ActorCritic.export`` collects them in hook order).  A hook that overrides ``pre_act`` must override this too — to
+        return ``()`` when its ``pre_act`` leaves the observation alone — or the export refuses the agent."""
+        return ()
+
     @classmethod
     def warn(cls, message):
         distributed.print_rank0(f"\033[1;31m{cls.__name__}: {message}\033[0m")

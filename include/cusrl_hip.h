@@ -1130,8 +1130,40 @@ int cusrl_bijector_bwd(int kind, const float *x, const float *dy, float *dx, int
 int cusrl_bias_act(const float *x, const float *bias, float *out, int64_t rows, int64_t H, int activation, float alpha,
                    void *stream);
 
+/* ---- the two elementwise ends of a deployed policy's step (cusrl_amd/nn/deployed.py, the runner of a file written by
+ * ActorCritic.export — cusrl/template/actor_critic.py:332-418; additive entries of ABI 7; csrc/deploy.hip) ----
+ * cusrl_deploy_prologue, ONE launch in front of the first GEMM:
+ *   out[b, k] = clamp((nan_to_num(obs[b, k]) - mean[k]) / std[k], -clamp, clamp)       obs, out [B, K] contiguous fp32
+ * Each part is optional.  `replace` is a HOST pointer to the three floats {nan, posinf, neginf}, read before the call returns
+ * (NULL: no sanitiser); the classification is the bit pattern's, as cusrl_nan_to_num2 does it.  mean, std [K] (both NULL: no
+ * normaliser).  clamp <= 0 (or a NaN): no clamp.  The result has the bits of cusrl_nan_to_num2 followed by cusrl_rms_normalize on
+ * the same operands: the same classification, subtraction, correctly rounded division and fminf(fmaxf()) in the same order.
+ * out may be obs.  4-byte aligned pointers work: 16-byte accesses when K % 4 == 0 and every pointer given is 16-byte aligned,
+ * 4-byte accesses otherwise, the same bits either way.
+ * cusrl_deploy_epilogue, ONE launch behind the head's bias-free GEMM, in place on its output y [B, A]:
+ *   y[b, a] = clip((y[b, a] + bias[a]) * scale[a] + shift[a], lo[a], hi[a])            bias, scale, shift, lo, hi [A]
+ * One add, one multiply and one add (two roundings, never an FMA), then v < lo ? lo : v and v > hi ? hi : v (a NaN stays a
+ * NaN, as torch.clamp leaves it).  bias NULL: no bias; scale and shift both NULL: no affine; lo and hi both NULL: no clip.
+ * done != NULL (B one-byte flags): the same launch writes zeros over the rows b of memory [B, M] with done[b] != 0 and touches
+ * no other row (16-byte stores when M % 4 == 0 and memory is 16-byte aligned, 4-byte stores otherwise).  With nothing to do
+ * (every part NULL) nothing is launched.
+ * Both: B == 0 launches nothing.  No host synchronisation: the launches may be captured.  CUSRL_E_INVALID, nothing launched:
+ * B < 0, K or A < 1, M < 0, a NULL obs / out / y with B > 0, one of a pair (mean and std, scale and shift, lo and hi) without the
+ * other, done without a memory of M >= 1, an obs or out that is not 4-byte aligned.  CUSRL_E_UNSUPPORTED: K or A above
+ * INT32_MAX, an element count beyond int64.
+ * The `_cpu` entries restate the two kernels on the host, element by element with the same expressions (every pointer a HOST
+ * pointer, no stream): what the GPU tests compare the kernels' bits against. */
+int cusrl_deploy_prologue(const float *obs, const float *replace /* host, 3 floats */, const float *mean, const float *std,
+                          float clamp, float *out, int64_t B, int64_t K, void *stream);
+int cusrl_deploy_prologue_cpu(const float *obs, const float *replace, const float *mean, const float *std, float clamp, float *out,
+                              int64_t B, int64_t K);
+int cusrl_deploy_epilogue(float *y, const float *bias, const float *scale, const float *shift, const float *lo, const float *hi,
+                          int64_t B, int64_t A, const uint8_t *done, float *memory, int64_t M, void *stream);
+int cusrl_deploy_epilogue_cpu(float *y, const float *bias, const float *scale, const float *shift, const float *lo, const float *hi,
+                              int64_t B, int64_t A, const uint8_t *done, float *memory, int64_t M);
 
-/* ---- a6 / a14  data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
+
+/* ---- a6 / a14 data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
  * device that is current when it is created.  Rank 0 draws the 128-byte id (cusrl_comm_unique_id), the host hands it
  * to the other ranks by any means (the Python host uses its torch.distributed store), every rank calls
