@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 #include "loss_reduce.hpp"
+#include "philox.hpp"
 
 namespace cusrl {
 
@@ -451,21 +452,7 @@ __global__ __launch_bounds__(kPrepThreads) void bce_pair_fwd_bwd_kernel(const fl
 // ~ N(0, 1) [N, obs], reward ~ N(0, 1) [N, R], terminated ~ Bernoulli(p_term), truncated ~ Bernoulli(p_trunc), and one fresh
 // N(0, 1) row per env for the resets — ONE launch instead of five generator launches (rand, compare, 3 x randn).
 // Counter-based Philox4x32-10 keyed on (seed, step counter, stream, element): the step counter lives in device memory and is
-// advanced by the kernel itself, so a hipGraph replay draws fresh numbers like an eager call does.
-struct Philox {
-    uint32_t c[4];
-};
-__device__ __forceinline__ Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = uint64_t(0xD2511F53u) * c0, p1 = uint64_t(0xCD9E8D57u) * c2;
-        const uint32_t n0 = uint32_t(p1 >> 32) ^ c1 ^ k0, n1 = uint32_t(p1), n2 = uint32_t(p0 >> 32) ^ c3 ^ k1, n3 = uint32_t(p0);
-        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-    return Philox{{c0, c1, c2, c3}};
-}
-__device__ __forceinline__ float philox_uniform(uint32_t x) { return float(x >> 8) * 5.9604645e-8f + 2.9802322e-8f; }  // (0, 1)
+// advanced by the kernel itself, so a hipGraph replay draws fresh numbers like an eager call does.  (The generator: philox.hpp.)
 __device__ __forceinline__ float4 philox_normal4(const Philox &r) {  // two Box-Muller pairs
     const float r0 = sqrtf(-2.0f * logf(philox_uniform(r.c[0]))), r1 = sqrtf(-2.0f * logf(philox_uniform(r.c[2])));
     float s0, c0, s1, c1;

@@ -43,6 +43,9 @@ from cusrl_amd.ops.conv import (
     DepthwiseConv2d, depthwise_conv2d, dwconv2d_backward_input, dwconv2d_backward_params, dwconv2d_supported,
 )
 from cusrl_amd.ops.deploy import deploy_epilogue_, deploy_epilogue_cpu_, deploy_prologue, deploy_prologue_cpu, deploy_supported
+from cusrl_amd.ops.environment import (
+    CLASSIC_TASKS, ClassicTask, classic_reset, classic_reset_cpu, classic_step, classic_step_cpu,
+)
 from cusrl_amd.ops.gate import GateCombine, Glu, gate_backward, gate_combine, gate_supported, glu, glu_backward, glu_supported
 from cusrl_amd.ops.gradient import (
     DeferredColumns, adam_norm_workspace, adam_step, adam_step_normed, adam_step_window, assemble_gradients, clip_grad_norm_,

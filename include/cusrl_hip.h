@@ -1162,6 +1162,61 @@ int cusrl_deploy_epilogue(float *y, const float *bias, const float *scale, const
 int cusrl_deploy_epilogue_cpu(float *y, const float *bias, const float *scale, const float *shift, const float *lo, const float *hi,
                               int64_t B, int64_t A, const uint8_t *done, float *memory, int64_t M);
 
+/* ---- classic-control tasks as device-resident environments (cusrl_amd/environment/; the reference takes these tasks from
+ * gymnasium through cusrl/environment/gym.py, one host round trip per step; additive entries of ABI 7; csrc/environment.hip) ----
+ * Per env e: a contiguous fp32 row state[e, S], an int32 steps[e] (steps taken in the running episode) and an int64 episode[e]
+ * (how often the env has been reset).  All arithmetic fp32, one rounding per written operation, in the written order; sinf /
+ * cosf are the platform's.  An action row of a discrete task is read as logits / one-hot: the FIRST maximal column is taken.
+ *
+ *   CLASSIC_CARTPOLE     S = 4 (x, x', th, th'), action [N, 2], observation = state, F = column 1 ? +10 : -10
+ *       temp = (F + 0.05 th'^2 sin th) / 1.1;   th'' = (9.8 sin th - cos th temp) / (0.5 (4/3 - 0.1 cos^2 th / 1.1))
+ *       x''  = temp - 0.05 th'' cos th / 1.1;   x += 0.02 x', x' += 0.02 x'', th += 0.02 th', th' += 0.02 th'' (old derivatives)
+ *       reward 1;  terminated = |x| > 2.4 or |th| > 12 * 2 pi / 360;  default max_steps 500
+ *       reset: four draws U[-0.05, 0.05]
+ *   CLASSIC_PENDULUM     S = 2 (th, th'), action [N, 1], observation [cos th, sin th, th'], u = clamp(a, -2, 2)
+ *       reward = -(wrap(th)^2 + 0.1 th'^2 + 0.001 u^2) of the OLD state, wrap(th) = floor-mod(th + pi, 2 pi) - pi
+ *       th' = clamp(th' + (15 sin th + 3 u) 0.05, -8, 8), then th += 0.05 th';  never terminated;  default max_steps 200
+ *       reset: th ~ U[-pi, pi], th' ~ U[-1, 1]
+ *   CLASSIC_MOUNTAINCAR  S = 2 (p, v), action [N, 3] -> a in {0, 1, 2}, observation = state
+ *       v = clamp(v + (a - 1) 0.001 - 0.0025 cos(3 p), -0.07, 0.07), p = clamp(p + v, -1.2, 0.6), v = 0 if p == -1.2 and v < 0
+ *       reward -1;  terminated = p >= 0.5 and v >= 0;  default max_steps 200
+ *       reset: p ~ U[-0.6, -0.4], v = 0
+ *   truncated = steps[e] (after the step) >= max_steps and not terminated.
+ *
+ * cusrl_classic_step, ONE launch, one thread per env: advances state and steps IN PLACE and writes next_observation [N, O] (the
+ * terminal observation for a finished env), reward [N, 1] and the one-byte flags terminated / truncated [N, 1]; touches nothing
+ * else.  A thread reads and writes only its own env's rows.  4-byte aligned pointers work (a state row moves as one access
+ * where `state` is aligned to a row, as S scalars otherwise: the same bits).
+ *
+ * cusrl_classic_reset, ONE launch, one thread per index slot k < rows.  live = count ? *count : rows, read on the device.
+ *   k < live:   env e = indices[k] is re-initialised: its draws are Philox4x32-10 with counter (e, episode[e]) and key `seed`,
+ *               uniforms u = (word >> 8) 2^-24 + 2^-25 mapped as lo + (hi - lo) u — a pure function of (seed, e, episode[e]),
+ *               whatever the launch shape and order; then episode[e] += 1 and steps[e] = 0, or with randomize_progress != 0 the
+ *               integer floor(max_steps * word / 2^32) of a second Philox call; row k of observation_out is the fresh observation.
+ *   k >= live:  row k is the CURRENT observation of env indices[k]; that env's state, steps and episode are not written.
+ * indices: int64 [rows], ids in [0, N) (an id outside is skipped, its row written as zeros); distinct within the first `live`
+ * (the trainer's step epilogue guarantees it).  Should an id at or above `live` repeat one below it, that row holds the env's
+ * observation from before or after this launch's reset — the caller drops such rows.
+ *
+ * N == 0 (step) / rows == 0 (reset) launch nothing.  CUSRL_E_INVALID, nothing launched: an unknown kind, a negative size,
+ * max_steps outside 1 .. INT32_MAX, a NULL or misaligned pointer among those the call uses (count may be NULL).
+ * CUSRL_E_UNSUPPORTED: more envs or slots than INT32_MAX * 64.
+ * The `_cpu` entries run the same __host__ __device__ bodies on the host (every pointer a HOST pointer, no stream): the host
+ * form of the environments and what the GPU tests compare against. */
+#define CUSRL_CLASSIC_CARTPOLE 0
+#define CUSRL_CLASSIC_PENDULUM 1
+#define CUSRL_CLASSIC_MOUNTAINCAR 2
+int cusrl_classic_step(int kind, const float *action, float *state, int32_t *steps, int64_t max_steps, float *next_observation,
+                       float *reward, uint8_t *terminated, uint8_t *truncated, int64_t N, void *stream);
+int cusrl_classic_step_cpu(int kind, const float *action, float *state, int32_t *steps, int64_t max_steps, float *next_observation,
+                           float *reward, uint8_t *terminated, uint8_t *truncated, int64_t N);
+int cusrl_classic_reset(int kind, uint64_t seed, const int64_t *indices, const int32_t *count, float *state, int32_t *steps,
+                        int64_t *episode, float *observation_out, int64_t rows, int randomize_progress, int64_t max_steps, int64_t N,
+                        void *stream);
+int cusrl_classic_reset_cpu(int kind, uint64_t seed, const int64_t *indices, const int32_t *count, float *state, int32_t *steps,
+                            int64_t *episode, float *observation_out, int64_t rows, int randomize_progress, int64_t max_steps,
+                            int64_t N);
+
 
 /* ---- a6 / a14 data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
