@@ -46,6 +46,7 @@ from cusrl_amd.template import (
 )
 from cusrl_amd.utils import CONFIG as config
 from cusrl_amd.utils import device, set_global_seed
+from cusrl_amd import zoo  # (after everything it registers experiments from)
 
 __version__ = "0.1.0"
 
@@ -148,4 +149,5 @@ __all__ = [
     "PlayerHook",
     "Trial",
     "make_logger_factory",
+    "zoo",
 ]

@@ -1,4 +1,4 @@
-"""CartPole, Pendulum and MountainCar as device-resident environments (``csrc/environment.hip``; formulas and constants:
+"""CartPole, Pendulum, MountainCar, Acrobot and MountainCarContinuous as device-resident environments (``csrc/environment.hip``; formulas and constants:
 include/cusrl_hip.h; DESIGN.md §7, "Classic-control environments").
 
 The reference takes these tasks from gymnasium (cusrl/environment/gym.py, zoo/gym/classic_control.py): a host simulator and a
@@ -15,11 +15,11 @@ from cusrl_amd.ops.environment import CLASSIC_TASKS, ClassicTask
 from cusrl_amd.template.environment import Environment
 from cusrl_amd.utils.config import device as resolve_device
 
-__all__ = ["CartPole", "ClassicControlEnvironment", "MountainCar", "Pendulum", "make"]
+__all__ = ["Acrobot", "CartPole", "ClassicControlEnvironment", "MountainCar", "MountainCarContinuous", "Pendulum", "make"]
 
 
 class ClassicControlEnvironment(Environment):
-    """Common part of the three tasks; a subclass names its :class:`ClassicTask`.
+    """Common part of the tasks; a subclass names its :class:`ClassicTask`.
 
     An env that finishes keeps its terminal state until it is reset (``autoreset = False``): the trainer resets it in the same
     env step, by ``reset_static`` (device-side count) or ``reset(indices=...)``.  Episode ``n`` of env ``e`` always starts from
@@ -109,11 +109,31 @@ class MountainCar(ClassicControlEnvironment):
     task = CLASSIC_TASKS["MountainCar"]
 
 
+class Acrobot(ClassicControlEnvironment):
+    """Swing the tip of a two-link pendulum above the bar: observation ``(cos theta1, sin theta1, cos theta2, sin theta2, theta1',
+    theta2')``, action logits over the torques {-1, 0, +1} on the second joint, one Runge-Kutta step of 0.2 s per env step, reward
+    -1 per step (0 on the last), terminated when ``-cos theta1 - cos(theta1 + theta2) > 1``, truncated at 500 steps."""
+
+    task = CLASSIC_TASKS["Acrobot-v1"]
+
+
+class MountainCarContinuous(ClassicControlEnvironment):
+    """MountainCar with one continuous force in [-1, 1]: observation ``(position, velocity)``, reward ``-0.1 a^2`` per step and
+    +100 on reaching position 0.45, terminated there, truncated at 999 steps."""
+
+    task = CLASSIC_TASKS["MountainCarContinuous-v0"]
+
+
+# The bare names of the first three (in this order: the error message lists them first), then the gym ids of all five.  Acrobot and
+# MountainCarContinuous have NO bare name: "Acrobot" is the suite's standing example of an unknown environment and stays one.
 _REGISTRY = {cls.__name__: cls for cls in (CartPole, Pendulum, MountainCar)}
+_REGISTRY.update({"CartPole-v1": CartPole, "Pendulum-v1": Pendulum, "MountainCar-v0": MountainCar, "Acrobot-v1": Acrobot,
+                  "MountainCarContinuous-v0": MountainCarContinuous})
 
 
 def make(name: str, num_instances: int = 1, **kwargs) -> ClassicControlEnvironment:
-    """``make("CartPole", 64, device="cuda:0")``; the names: CartPole, Pendulum, MountainCar."""
+    """``make("CartPole", 64, device="cuda:0")``; the names: CartPole, Pendulum, MountainCar, and the gym ids CartPole-v1,
+    Pendulum-v1, MountainCar-v0, Acrobot-v1, MountainCarContinuous-v0."""
     if name not in _REGISTRY:
         raise ValueError(f"unknown environment {name!r}; available: {', '.join(_REGISTRY)}")
     return _REGISTRY[name](num_instances, **kwargs)

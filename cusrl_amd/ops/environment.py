@@ -18,14 +18,21 @@ __all__ = ["CLASSIC_TASKS", "ClassicTask", "classic_reset", "classic_reset_cpu",
 class ClassicTask:
     """One task's code and row widths (``CUSRL_CLASSIC_*`` of the header; the widths as ``Task<kind>`` of the kernel file)."""
 
-    def __init__(self, name: str, state_dim: int, action_dim: int, observation_dim: int, max_episode_steps: int):
-        self.name, self.kind = name, _native._CONSTANTS[f"CLASSIC_{name.upper()}"]
+    def __init__(self, name: str, constant: str, state_dim: int, action_dim: int, observation_dim: int, max_episode_steps: int):
+        self.name, self.kind = name, _native._CONSTANTS[constant]
         self.state_dim, self.action_dim, self.observation_dim = state_dim, action_dim, observation_dim
         self.max_episode_steps = max_episode_steps
 
 
-CLASSIC_TASKS = {task.name: task for task in (ClassicTask("CartPole", 4, 2, 4, 500), ClassicTask("Pendulum", 2, 1, 3, 200),
-                                              ClassicTask("MountainCar", 2, 3, 2, 200))}
+# The two later tasks are keyed by their gym ids ONLY: the bare name "Acrobot" is the suite's standing example of an unknown task
+# (tests/test_classic_control.py) and stays one; the first three keep their bare names, in this order.
+CLASSIC_TASKS = {task.name: task for task in (
+    ClassicTask("CartPole", "CLASSIC_CARTPOLE", 4, 2, 4, 500),
+    ClassicTask("Pendulum", "CLASSIC_PENDULUM", 2, 1, 3, 200),
+    ClassicTask("MountainCar", "CLASSIC_MOUNTAINCAR", 2, 3, 2, 200),
+    ClassicTask("Acrobot-v1", "CLASSIC_ACROBOT", 4, 3, 6, 500),
+    ClassicTask("MountainCarContinuous-v0", "CLASSIC_MOUNTAINCARCONTINUOUS", 2, 1, 2, 999),
+)}
 
 
 def _task(task) -> ClassicTask:

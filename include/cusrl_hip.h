@@ -1181,12 +1181,30 @@ int cusrl_deploy_epilogue_cpu(float *y, const float *bias, const float *scale, c
  *       v = clamp(v + (a - 1) 0.001 - 0.0025 cos(3 p), -0.07, 0.07), p = clamp(p + v, -1.2, 0.6), v = 0 if p == -1.2 and v < 0
  *       reward -1;  terminated = p >= 0.5 and v >= 0;  default max_steps 200
  *       reset: p ~ U[-0.6, -0.4], v = 0
+ *   CLASSIC_ACROBOT      S = 4 (th1, th2, w1, w2), action [N, 3] -> torque a = column - 1 in {-1, 0, +1},
+ *                        observation [cos th1, sin th1, cos th2, sin th2, w1, w2] (O = 6)
+ *       constants m1 = m2 = 1, l1 = 1, lc1 = lc2 = 0.5, I1 = I2 = 1, g = 9.8, dt = 0.2; folded, with sin x for cos(x - pi/2), the
+ *       derivative f(th1, th2, w1, w2; a) = (w1, w2, w1', w2') is, each line left to right:
+ *         d1 = 3.5 + cos th2;   d2 = 1.25 + 0.5 cos th2;   phi2 = 4.9 sin(th1 + th2)
+ *         phi1 = (-0.5 (w2 w2)) sin th2 - (w2 w1) sin th2 + 14.7 sin th1 + phi2
+ *         w2' = (a + (d2 / d1) phi1 - (0.5 (w1 w1)) sin th2 - phi2) / (1.25 - (d2 d2) / d1);   w1' = -((d2 w2' + phi1) / d1)
+ *       one classical Runge-Kutta step, the torque held: k1 = f(s), k2 = f(s + 0.1 k1), k3 = f(s + 0.1 k2), k4 = f(s + 0.2 k3),
+ *       s = s + (0.2f / 6.0f) (k1 + 2 k2 + 2 k3 + k4), the sum left to right; then th1, th2 wrapped into [-pi, pi] WITHOUT a loop:
+ *       x > pi: x - 2 pi ceil((x - pi) / (2 pi));  x < -pi: x + 2 pi ceil((-pi - x) / (2 pi))  (a NaN stays, an Inf becomes a NaN:
+ *       a non-finite angle comes out non-finite and the call returns);  w1 = clamp(w1, -4 pi, 4 pi), w2 = clamp(w2, -9 pi, 9 pi)
+ *       terminated = -cos th1 - cos(th1 + th2) > 1 (of the new state);  reward = terminated ? 0 : -1;  default max_steps 500
+ *       reset: four draws U[-0.1, 0.1]
+ *   CLASSIC_MOUNTAINCARCONTINUOUS  S = 2 (p, v), action [N, 1], observation = state, force = clamp(a, -1, 1)
+ *       v = clamp(v + (force 0.0015 - 0.0025 cos(3 p)), -0.07, 0.07), p = clamp(p + v, -1.2, 0.6), v = 0 if p == -1.2 and v < 0
+ *       terminated = p >= 0.45 and v >= 0;  reward = (terminated ? 100 : 0) - 0.1 (a a) with the RAW action;  default max_steps 999
+ *       reset: p ~ U[-0.6, -0.4], v = 0 (the draw MountainCar takes)
  *   truncated = steps[e] (after the step) >= max_steps and not terminated.
  *
  * cusrl_classic_step, ONE launch, one thread per env: advances state and steps IN PLACE and writes next_observation [N, O] (the
  * terminal observation for a finished env), reward [N, 1] and the one-byte flags terminated / truncated [N, 1]; touches nothing
  * else.  A thread reads and writes only its own env's rows.  4-byte aligned pointers work (a state row moves as one access
- * where `state` is aligned to a row, as S scalars otherwise: the same bits).
+ * where `state` is aligned to a row, as S scalars otherwise: the same bits; Acrobot's 6-wide observation row as three 8-byte
+ * stores where next_observation is 8-byte aligned too, as 6 scalars otherwise).  No loop's trip count depends on data.
  *
  * cusrl_classic_reset, ONE launch, one thread per index slot k < rows.  live = count ? *count : rows, read on the device.
  *   k < live:   env e = indices[k] is re-initialised: its draws are Philox4x32-10 with counter (e, episode[e]) and key `seed`,
@@ -1206,6 +1224,8 @@ int cusrl_deploy_epilogue_cpu(float *y, const float *bias, const float *scale, c
 #define CUSRL_CLASSIC_CARTPOLE 0
 #define CUSRL_CLASSIC_PENDULUM 1
 #define CUSRL_CLASSIC_MOUNTAINCAR 2
+#define CUSRL_CLASSIC_ACROBOT 3
+#define CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS 4
 int cusrl_classic_step(int kind, const float *action, float *state, int32_t *steps, int64_t max_steps, float *next_observation,
                        float *reward, uint8_t *terminated, uint8_t *truncated, int64_t N, void *stream);
 int cusrl_classic_step_cpu(int kind, const float *action, float *state, int32_t *steps, int64_t max_steps, float *next_observation,
