@@ -10,37 +10,22 @@
 // is built with -ffp-contract=off); the bodies are __host__ __device__ and the `*_cpu` entries run the same bodies on the
 // host, so the two differ only where sinf / cosf do.  Plain vector stores only.  No loop's trip count depends on data: Acrobot's
 // angle wrap is a closed form (a `while` over a NaN, an Inf or a huge loaded angle would not end).
+//
+// Layout.  A TASK IS ONE BLOCK: `Task<kind>` holds the row widths and its own `observe`, `advance` and `initial_state`.  What runs
+// a task is written once over `Task<kind>`: `step_env` (one env of the step) and `reset_slot` (one index slot of the reset), each
+// called per thread by its kernel and per loop iteration by its `*_cpu` entry.  `for_task` is the one place that maps a runtime
+// kind to its `Task<>`.  A new task: one `Task<>` block, one line in `for_task`, one `#define` in the header.
 #include "common.hpp"
 #include "philox.hpp"
 
 #include <math.h>
 
+#include <type_traits>
+
 namespace cusrl {
 namespace {
 
-template <int kKind>
-struct Task;
-// (kObservationBytes: the widest access an observation row moves by where it is aligned to it; 4: scalars)
-template <>
-struct Task<CUSRL_CLASSIC_CARTPOLE> {  // state x, x', theta, theta'; action: logits over {push left, push right}
-    static constexpr int kState = 4, kAction = 2, kObservation = 4, kObservationBytes = 16;
-};
-template <>
-struct Task<CUSRL_CLASSIC_PENDULUM> {  // state theta, theta'; action: one torque; observation cos, sin, theta'
-    static constexpr int kState = 2, kAction = 1, kObservation = 3, kObservationBytes = 4;
-};
-template <>
-struct Task<CUSRL_CLASSIC_MOUNTAINCAR> {  // state position, velocity; action: logits over {left, none, right}
-    static constexpr int kState = 2, kAction = 3, kObservation = 2, kObservationBytes = 8;
-};
-template <>
-struct Task<CUSRL_CLASSIC_ACROBOT> {  // state theta1, theta2, theta1', theta2'; action: logits over torque {-1, 0, +1};
-    static constexpr int kState = 4, kAction = 3, kObservation = 6, kObservationBytes = 8;  // observation cos, sin, cos, sin, ', '
-};
-template <>
-struct Task<CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS> {  // state position, velocity; action: one force
-    static constexpr int kState = 2, kAction = 1, kObservation = 2, kObservationBytes = 8;
-};
+constexpr float kPi = 3.14159265358979323846f, kTwoPi = 6.28318530717958647692f;
 
 __host__ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
@@ -54,24 +39,110 @@ __host__ __device__ __forceinline__ int first_max(const float *a) {
     return best;
 }
 
+// ---- the tasks.  kState / kAction / kObservation: the row widths; kObservationBytes: the widest access an observation row moves
+// by where it is aligned to it (4: scalars); observe: state row -> observation row; advance: ONE transition, s advanced in place,
+// returns `terminated`; initial_state: the state of a fresh episode from one Philox call (documented ranges: include/cusrl_hip.h).
 template <int kKind>
-__host__ __device__ __forceinline__ void observe(const float *s, float *o) {
-    if constexpr (kKind == CUSRL_CLASSIC_PENDULUM) {
+struct Task;
+
+template <int kWidth>
+struct ObservesItsState {  // the observation is the state row
+    static constexpr int kState = kWidth, kObservation = kWidth, kObservationBytes = 4 * kWidth;
+    static __host__ __device__ __forceinline__ void observe(const float *s, float *o) {
+#pragma unroll
+        for (int j = 0; j < kWidth; ++j) o[j] = s[j];
+    }
+};
+
+template <>
+struct Task<CUSRL_CLASSIC_CARTPOLE> : ObservesItsState<4> {  // state x, x', theta, theta'; action: logits over {push left, push right}
+    static constexpr int kAction = 2;
+    static __host__ __device__ __forceinline__ bool advance(float *s, const float *a, float &reward) {
+        constexpr float kGravity = 9.8f, kTotalMass = 1.1f, kPoleMass = 0.1f, kLength = 0.5f, kPoleMassLength = 0.05f, kTau = 0.02f;
+        const float force = first_max<2>(a) == 1 ? 10.0f : -10.0f;
+        const float x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+        const float cos_theta = cosf(theta), sin_theta = sinf(theta);
+        const float temp = (force + kPoleMassLength * (theta_dot * theta_dot) * sin_theta) / kTotalMass;
+        const float theta_acc = (kGravity * sin_theta - cos_theta * temp) /
+                                (kLength * (4.0f / 3.0f - kPoleMass * (cos_theta * cos_theta) / kTotalMass));
+        const float x_acc = temp - kPoleMassLength * theta_acc * cos_theta / kTotalMass;
+        s[0] = x + kTau * x_dot;  // explicit Euler: every line uses the old derivatives
+        s[1] = x_dot + kTau * x_acc;
+        s[2] = theta + kTau * theta_dot;
+        s[3] = theta_dot + kTau * theta_acc;
+        reward = 1.0f;
+        return fabsf(s[0]) > 2.4f || fabsf(s[2]) > 0.20943951023931953f;  // 12 degrees
+    }
+    static __host__ __device__ __forceinline__ void initial_state(const Philox &r, float *s) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = -0.05f + 0.1f * philox_uniform(r.c[j]);
+    }
+};
+
+template <>
+struct Task<CUSRL_CLASSIC_PENDULUM> {  // state theta, theta'; action: one torque; observation cos, sin, theta'
+    static constexpr int kState = 2, kAction = 1, kObservation = 3, kObservationBytes = 4;
+    static __host__ __device__ __forceinline__ void observe(const float *s, float *o) {
         o[0] = cosf(s[0]);
         o[1] = sinf(s[0]);
         o[2] = s[1];
-    } else if constexpr (kKind == CUSRL_CLASSIC_ACROBOT) {
-        o[0] = cosf(s[0]);
-        o[1] = sinf(s[0]);
-        o[2] = cosf(s[1]);
-        o[3] = sinf(s[1]);
-        o[4] = s[2];
-        o[5] = s[3];
-    } else {
-#pragma unroll
-        for (int j = 0; j < Task<kKind>::kState; ++j) o[j] = s[j];
     }
-}
+    static __host__ __device__ __forceinline__ bool advance(float *s, const float *a, float &reward) {
+        constexpr float kDt = 0.05f;
+        const float u = clampf(a[0], -2.0f, 2.0f);
+        const float theta = s[0], theta_dot = s[1];
+        float wrapped = fmodf(theta + kPi, kTwoPi);  // Python's floor-mod: the sign of the divisor
+        if (wrapped < 0.0f) wrapped = wrapped + kTwoPi;
+        wrapped = wrapped - kPi;
+        reward = -(wrapped * wrapped + 0.1f * (theta_dot * theta_dot) + 0.001f * (u * u));  // of the OLD state
+        s[1] = clampf(theta_dot + (15.0f * sinf(theta) + 3.0f * u) * kDt, -8.0f, 8.0f);  // 3g / (2l) = 15, 3 / (m l^2) = 3
+        s[0] = theta + s[1] * kDt;
+        return false;
+    }
+    static __host__ __device__ __forceinline__ void initial_state(const Philox &r, float *s) {
+        s[0] = -kPi + kTwoPi * philox_uniform(r.c[0]);
+        s[1] = -1.0f + 2.0f * philox_uniform(r.c[1]);
+    }
+};
+
+// What the two mountain cars share: state position, velocity; the start; and everything after the raw velocity increment.  The
+// increment itself is each task's own: the two associate it differently, and each keeps its textbook order.
+struct MountainCarTrack : ObservesItsState<2> {
+    static __host__ __device__ __forceinline__ void move(float *s, float raw_velocity) {
+        float velocity = clampf(raw_velocity, -0.07f, 0.07f);
+        const float position = clampf(s[0] + velocity, -1.2f, 0.6f);
+        if (position == -1.2f && velocity < 0.0f) velocity = 0.0f;  // the left wall is inelastic
+        s[0] = position;
+        s[1] = velocity;
+    }
+    static __host__ __device__ __forceinline__ void initial_state(const Philox &r, float *s) {
+        s[0] = -0.6f + 0.2f * philox_uniform(r.c[0]);
+        s[1] = 0.0f;
+    }
+};
+
+template <>
+struct Task<CUSRL_CLASSIC_MOUNTAINCAR> : MountainCarTrack {  // action: logits over {left, none, right}
+    static constexpr int kAction = 3;
+    static __host__ __device__ __forceinline__ bool advance(float *s, const float *a, float &reward) {
+        const int push = first_max<3>(a);
+        move(s, s[1] + float(push - 1) * 0.001f - 0.0025f * cosf(3.0f * s[0]));
+        reward = -1.0f;
+        return s[0] >= 0.5f && s[1] >= 0.0f;
+    }
+};
+
+template <>
+struct Task<CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS> : MountainCarTrack {  // action: one force
+    static constexpr int kAction = 1;
+    static __host__ __device__ __forceinline__ bool advance(float *s, const float *a, float &reward) {
+        const float force = clampf(a[0], -1.0f, 1.0f);
+        move(s, s[1] + (force * 0.0015f - 0.0025f * cosf(3.0f * s[0])));
+        const bool ended = s[0] >= 0.45f && s[1] >= 0.0f;
+        reward = (ended ? 100.0f : 0.0f) - 0.1f * (a[0] * a[0]);  // the RAW action, not the clamped force
+        return ended;
+    }
+};
 
 // Acrobot's equations of motion with the unit constants folded (m1 = m2 = l1 = I1 = I2 = 1, lc1 = lc2 = 0.5, g = 9.8) and
 // sin x for cos(x - pi/2): d = (theta1', theta2', theta1'', theta2'') at s under a constant torque
@@ -92,42 +163,23 @@ __host__ __device__ __forceinline__ void acrobot_derivative(const float *s, floa
 
 // x into [-pi, pi] by whole turns, loop-free: a NaN stays a NaN, an Inf becomes one
 __host__ __device__ __forceinline__ float wrap_angle(float x) {
-    constexpr float kPi = 3.14159265358979323846f, kTwoPi = 6.28318530717958647692f;
     if (x > kPi) return x - kTwoPi * ceilf((x - kPi) / kTwoPi);
     if (x < -kPi) return x + kTwoPi * ceilf((-kPi - x) / kTwoPi);
     return x;
 }
 
-// One transition of one env: s is advanced in place; returns `terminated`.
-template <int kKind>
-__host__ __device__ __forceinline__ bool advance(float *s, const float *a, float &reward) {
-    if constexpr (kKind == CUSRL_CLASSIC_CARTPOLE) {
-        constexpr float kGravity = 9.8f, kTotalMass = 1.1f, kPoleMass = 0.1f, kLength = 0.5f, kPoleMassLength = 0.05f, kTau = 0.02f;
-        const float force = first_max<2>(a) == 1 ? 10.0f : -10.0f;
-        const float x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
-        const float cos_theta = cosf(theta), sin_theta = sinf(theta);
-        const float temp = (force + kPoleMassLength * (theta_dot * theta_dot) * sin_theta) / kTotalMass;
-        const float theta_acc = (kGravity * sin_theta - cos_theta * temp) /
-                                (kLength * (4.0f / 3.0f - kPoleMass * (cos_theta * cos_theta) / kTotalMass));
-        const float x_acc = temp - kPoleMassLength * theta_acc * cos_theta / kTotalMass;
-        s[0] = x + kTau * x_dot;  // explicit Euler: every line uses the old derivatives
-        s[1] = x_dot + kTau * x_acc;
-        s[2] = theta + kTau * theta_dot;
-        s[3] = theta_dot + kTau * theta_acc;
-        reward = 1.0f;
-        return fabsf(s[0]) > 2.4f || fabsf(s[2]) > 0.20943951023931953f;  // 12 degrees
-    } else if constexpr (kKind == CUSRL_CLASSIC_PENDULUM) {
-        constexpr float kPi = 3.14159265358979323846f, kTwoPi = 6.28318530717958647692f, kDt = 0.05f;
-        const float u = clampf(a[0], -2.0f, 2.0f);
-        const float theta = s[0], theta_dot = s[1];
-        float wrapped = fmodf(theta + kPi, kTwoPi);  // Python's floor-mod: the sign of the divisor
-        if (wrapped < 0.0f) wrapped = wrapped + kTwoPi;
-        wrapped = wrapped - kPi;
-        reward = -(wrapped * wrapped + 0.1f * (theta_dot * theta_dot) + 0.001f * (u * u));  // of the OLD state
-        s[1] = clampf(theta_dot + (15.0f * sinf(theta) + 3.0f * u) * kDt, -8.0f, 8.0f);  // 3g / (2l) = 15, 3 / (m l^2) = 3
-        s[0] = theta + s[1] * kDt;
-        return false;
-    } else if constexpr (kKind == CUSRL_CLASSIC_ACROBOT) {
+template <>
+struct Task<CUSRL_CLASSIC_ACROBOT> {  // state theta1, theta2, theta1', theta2'; action: logits over torque {-1, 0, +1};
+    static constexpr int kState = 4, kAction = 3, kObservation = 6, kObservationBytes = 8;  // observation cos, sin, cos, sin, ', '
+    static __host__ __device__ __forceinline__ void observe(const float *s, float *o) {
+        o[0] = cosf(s[0]);
+        o[1] = sinf(s[0]);
+        o[2] = cosf(s[1]);
+        o[3] = sinf(s[1]);
+        o[4] = s[2];
+        o[5] = s[3];
+    }
+    static __host__ __device__ __forceinline__ bool advance(float *s, const float *a, float &reward) {
         constexpr float kHalfDt = 0.1f, kDt = 0.2f, kSixthDt = 0.2f / 6.0f;  // (the fp32 quotient)
         const float torque = float(first_max<3>(a) - 1);
         float k1[4], k2[4], k3[4], k4[4], y[4];  // classical Runge-Kutta over [0, dt], the torque held
@@ -150,46 +202,24 @@ __host__ __device__ __forceinline__ bool advance(float *s, const float *a, float
         const bool ended = -cosf(s[0]) - cosf(s[0] + s[1]) > 1.0f;
         reward = ended ? 0.0f : -1.0f;
         return ended;
-    } else if constexpr (kKind == CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS) {
-        const float force = clampf(a[0], -1.0f, 1.0f);
-        float position = s[0], velocity = s[1];
-        velocity = clampf(velocity + (force * 0.0015f - 0.0025f * cosf(3.0f * position)), -0.07f, 0.07f);
-        position = clampf(position + velocity, -1.2f, 0.6f);
-        if (position == -1.2f && velocity < 0.0f) velocity = 0.0f;
-        s[0] = position;
-        s[1] = velocity;
-        const bool ended = position >= 0.45f && velocity >= 0.0f;
-        reward = (ended ? 100.0f : 0.0f) - 0.1f * (a[0] * a[0]);  // the RAW action, not the clamped force
-        return ended;
-    } else {
-        const int push = first_max<3>(a);
-        float position = s[0], velocity = s[1];
-        velocity = clampf(velocity + float(push - 1) * 0.001f - 0.0025f * cosf(3.0f * position), -0.07f, 0.07f);
-        position = clampf(position + velocity, -1.2f, 0.6f);
-        if (position == -1.2f && velocity < 0.0f) velocity = 0.0f;
-        s[0] = position;
-        s[1] = velocity;
-        reward = -1.0f;
-        return position >= 0.5f && velocity >= 0.0f;
     }
-}
-
-// The state of a fresh episode from one Philox call (documented ranges: include/cusrl_hip.h).
-template <int kKind>
-__host__ __device__ __forceinline__ void initial_state(const Philox &r, float *s) {
-    if constexpr (kKind == CUSRL_CLASSIC_CARTPOLE) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[j] = -0.05f + 0.1f * philox_uniform(r.c[j]);
-    } else if constexpr (kKind == CUSRL_CLASSIC_PENDULUM) {
-        s[0] = -3.14159265358979323846f + 6.28318530717958647692f * philox_uniform(r.c[0]);
-        s[1] = -1.0f + 2.0f * philox_uniform(r.c[1]);
-    } else if constexpr (kKind == CUSRL_CLASSIC_ACROBOT) {
+    static __host__ __device__ __forceinline__ void initial_state(const Philox &r, float *s) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) s[j] = -0.1f + 0.2f * philox_uniform(r.c[j]);
-    } else {  // MountainCar and MountainCarContinuous
-        s[0] = -0.6f + 0.2f * philox_uniform(r.c[0]);
-        s[1] = 0.0f;
     }
+};
+
+// The one map from a runtime kind to its Task<>: f(integral_constant<int, kind>) -> status; an unknown kind is CUSRL_E_INVALID.
+template <typename F>
+int for_task(int kind, F &&f) {
+    switch (kind) {
+        case CUSRL_CLASSIC_CARTPOLE: return f(std::integral_constant<int, CUSRL_CLASSIC_CARTPOLE>{});
+        case CUSRL_CLASSIC_PENDULUM: return f(std::integral_constant<int, CUSRL_CLASSIC_PENDULUM>{});
+        case CUSRL_CLASSIC_MOUNTAINCAR: return f(std::integral_constant<int, CUSRL_CLASSIC_MOUNTAINCAR>{});
+        case CUSRL_CLASSIC_ACROBOT: return f(std::integral_constant<int, CUSRL_CLASSIC_ACROBOT>{});
+        case CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS: return f(std::integral_constant<int, CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS>{});
+    }
+    return CUSRL_E_INVALID;
 }
 
 // counter = (env id, episode number with the stream in its two top bits), key = seed.  Stream 0: the state, 1: the progress.
@@ -199,32 +229,10 @@ __host__ __device__ __forceinline__ Philox episode_draw(uint64_t seed, int64_t e
                          uint32_t(seed >> 32));
 }
 
-// ---- one env of the step, rows already in registers: shared by the kernel and cusrl_classic_step_cpu
-template <int kKind>
-__host__ __device__ __forceinline__ void step_env(float *s, const float *a, int32_t &steps, int32_t max_steps, float *o, float &reward,
-                                                  uint8_t &terminated, uint8_t &truncated) {
-    const bool ended = advance<kKind>(s, a, reward);
-    steps = steps + 1;
-    terminated = ended ? 1 : 0;
-    truncated = (!ended && steps >= max_steps) ? 1 : 0;
-    observe<kKind>(s, o);
-}
-
-// ---- env `e` of a reset slot below `count`: s, steps and episode come back holding what to store
-template <int kKind>
-__host__ __device__ __forceinline__ void reset_env(uint64_t seed, int64_t e, float *s, int32_t &steps, int64_t &episode,
-                                                   int randomize_progress, int32_t max_steps) {
-    initial_state<kKind>(episode_draw(seed, e, episode, 0u), s);
-    steps = 0;
-    if (randomize_progress)  // floor(max_steps * word / 2^32): an integer in [0, max_steps)
-        steps = int32_t((uint64_t(episode_draw(seed, e, episode, 1u).c[0]) * uint64_t(uint32_t(max_steps))) >> 32);
-    episode = episode + 1;
-}
-
 // kVec: the state rows (and the observation rows of the tasks whose observation is the state) move as one 16- or 8-byte access,
 // Acrobot's 6-wide observation row as three 8-byte ones
 template <int kWidth, bool kVec>
-__device__ __forceinline__ void load_row(const float *p, float *v) {
+__host__ __device__ __forceinline__ void load_row(const float *p, float *v) {
     if constexpr (kVec && kWidth == 4) {
         const float4 r = *reinterpret_cast<const float4 *>(p);
         v[0] = r.x, v[1] = r.y, v[2] = r.z, v[3] = r.w;
@@ -237,7 +245,7 @@ __device__ __forceinline__ void load_row(const float *p, float *v) {
     }
 }
 template <int kWidth, bool kVec>
-__device__ __forceinline__ void store_row(float *p, const float *v) {
+__host__ __device__ __forceinline__ void store_row(float *p, const float *v) {
     if constexpr (kVec && kWidth == 4) {
         *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
     } else if constexpr (kVec && kWidth == 2) {
@@ -249,6 +257,48 @@ __device__ __forceinline__ void store_row(float *p, const float *v) {
 #pragma unroll
         for (int j = 0; j < kWidth; ++j) p[j] = v[j];
     }
+}
+
+// ---- one env of the step, rows already in registers: shared by the kernel and cusrl_classic_step_cpu
+template <int kKind>
+__host__ __device__ __forceinline__ void step_env(float *s, const float *a, int32_t &steps, int32_t max_steps, float *o, float &reward,
+                                                  uint8_t &terminated, uint8_t &truncated) {
+    const bool ended = Task<kKind>::advance(s, a, reward);
+    steps = steps + 1;
+    terminated = ended ? 1 : 0;
+    truncated = (!ended && steps >= max_steps) ? 1 : 0;
+    Task<kKind>::observe(s, o);
+}
+
+// ---- index slot k of the reset, through local rows: shared by the kernel and cusrl_classic_reset_cpu
+template <int kKind>
+__host__ __device__ __forceinline__ void reset_slot(int64_t k, uint64_t seed, const int64_t *indices, const int32_t *count, float *state,
+                                                    int32_t *steps, int64_t *episode, float *observation_out, int64_t rows,
+                                                    int randomize_progress, int32_t max_steps, int64_t N) {
+    using T = Task<kKind>;
+    const int64_t live = count ? int64_t(*count) : rows;  // (a count beyond `rows` covers every slot, a negative one none)
+    const int64_t e = indices[k];
+    float s[T::kState], o[T::kObservation];
+    if (e < 0 || e >= N) {  // not an env: nothing is touched, the slot's row is zeros
+#pragma unroll
+        for (int j = 0; j < T::kObservation; ++j) observation_out[k * T::kObservation + j] = 0.0f;
+        return;
+    }
+    if (k < live) {  // a new episode of env e
+        int64_t number = episode[e];
+        T::initial_state(episode_draw(seed, e, number, 0u), s);
+        int32_t progress = 0;
+        if (randomize_progress)  // floor(max_steps * word / 2^32): an integer in [0, max_steps)
+            progress = int32_t((uint64_t(episode_draw(seed, e, number, 1u).c[0]) * uint64_t(uint32_t(max_steps))) >> 32);
+        number = number + 1;
+        store_row<T::kState, false>(state + e * T::kState, s);
+        steps[e] = progress;
+        episode[e] = number;
+    } else {
+        load_row<T::kState, false>(state + e * T::kState, s);
+    }
+    T::observe(s, o);
+    store_row<T::kObservation, false>(observation_out + k * T::kObservation, o);
 }
 
 template <int kKind, bool kVec>
@@ -278,69 +328,22 @@ __global__ __launch_bounds__(kBlock) void classic_reset_kernel(uint64_t seed, co
                                                                const int32_t *__restrict__ count, float *state, int32_t *steps,
                                                                int64_t *episode, float *__restrict__ observation_out, int64_t rows,
                                                                int randomize_progress, int32_t max_steps, int64_t N) {
-    using T = Task<kKind>;
     const int64_t k = int64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (k >= rows) return;
-    const int64_t live = count ? int64_t(*count) : rows;  // (a count beyond `rows` covers every slot, a negative one none)
-    const int64_t e = indices[k];
-    float s[T::kState], o[T::kObservation];
-    if (e < 0 || e >= N) {  // not an env: nothing is touched, the slot's row is zeros
-#pragma unroll
-        for (int j = 0; j < T::kObservation; ++j) observation_out[k * T::kObservation + j] = 0.0f;
-        return;
-    }
-    if (k < live) {
-        int32_t progress;
-        int64_t number = episode[e];
-        reset_env<kKind>(seed, e, s, progress, number, randomize_progress, max_steps);
-        store_row<T::kState, false>(state + e * T::kState, s);
-        steps[e] = progress;
-        episode[e] = number;
-    } else {
-        load_row<T::kState, false>(state + e * T::kState, s);
-    }
-    observe<kKind>(s, o);
-    store_row<T::kObservation, false>(observation_out + k * T::kObservation, o);
+    reset_slot<kKind>(k, seed, indices, count, state, steps, episode, observation_out, rows, randomize_progress, max_steps, N);
 }
 
-template <int kKind>
-void step_rows_cpu(const float *action, float *state, int32_t *steps, int32_t max_steps, float *next_observation, float *reward,
-                   uint8_t *terminated, uint8_t *truncated, int64_t N) {
-    using T = Task<kKind>;
-    for (int64_t i = 0; i < N; ++i)
-        step_env<kKind>(state + i * T::kState, action + i * T::kAction, steps[i], max_steps, next_observation + i * T::kObservation,
-                        reward[i], terminated[i], truncated[i]);
-}
-
-template <int kKind>
-void reset_rows_cpu(uint64_t seed, const int64_t *indices, const int32_t *count, float *state, int32_t *steps, int64_t *episode,
-                    float *observation_out, int64_t rows, int randomize_progress, int32_t max_steps, int64_t N) {
-    using T = Task<kKind>;
-    const int64_t live = count ? int64_t(*count) : rows;
-    for (int64_t k = 0; k < rows; ++k) {
-        const int64_t e = indices[k];
-        if (e < 0 || e >= N) {
-            for (int j = 0; j < T::kObservation; ++j) observation_out[k * T::kObservation + j] = 0.0f;
-            continue;
-        }
-        if (k < live) reset_env<kKind>(seed, e, state + e * T::kState, steps[e], episode[e], randomize_progress, max_steps);
-        observe<kKind>(state + e * T::kState, observation_out + k * T::kObservation);
-    }
-}
-
-bool known(int kind) { return kind >= CUSRL_CLASSIC_CARTPOLE && kind <= CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS; }
-
-int check_step(int kind, const void *action, const void *state, const void *steps, int64_t max_steps, const void *next_observation,
+int check_step(const void *action, const void *state, const void *steps, int64_t max_steps, const void *next_observation,
                const void *reward, const void *terminated, const void *truncated, int64_t N) {
-    if (!known(kind) || N < 0 || max_steps < 1 || max_steps > INT32_MAX) return CUSRL_E_INVALID;
+    if (N < 0 || max_steps < 1 || max_steps > INT32_MAX) return CUSRL_E_INVALID;
     if (N > 0 && (!action || !state || !steps || !next_observation || !reward || !terminated || !truncated)) return CUSRL_E_INVALID;
     if (N > int64_t(INT32_MAX) * kBlock / 4) return CUSRL_E_UNSUPPORTED;
     return 0;
 }
 
-int check_reset(int kind, const void *indices, const void *state, const void *steps, const void *episode, const void *observation_out,
+int check_reset(const void *indices, const void *state, const void *steps, const void *episode, const void *observation_out,
                 int64_t rows, int64_t max_steps, int64_t N) {
-    if (!known(kind) || N < 0 || rows < 0 || max_steps < 1 || max_steps > INT32_MAX) return CUSRL_E_INVALID;
+    if (N < 0 || rows < 0 || max_steps < 1 || max_steps > INT32_MAX) return CUSRL_E_INVALID;
     if (rows > 0 && (N < 1 || !indices || !state || !steps || !episode || !observation_out)) return CUSRL_E_INVALID;
     if (rows > int64_t(INT32_MAX) * kBlock / 4 || N > int64_t(INT32_MAX) * kBlock / 4) return CUSRL_E_UNSUPPORTED;
     return 0;
@@ -360,120 +363,67 @@ void launch_step(const float *action, float *state, int32_t *steps, int32_t max_
                            next_observation, reward, terminated, truncated, N);
 }
 
+template <int kKind>
+void launch_reset(uint64_t seed, const int64_t *indices, const int32_t *count, float *state, int32_t *steps, int64_t *episode,
+                  float *observation_out, int64_t rows, int randomize_progress, int32_t max_steps, int64_t N, hipStream_t stream) {
+    hipLaunchKernelGGL(classic_reset_kernel<kKind>, dim3(uint32_t(ceil_div(rows, kBlock))), dim3(kBlock), 0, stream, seed, indices, count,
+                       state, steps, episode, observation_out, rows, randomize_progress, max_steps, N);
+}
+
 }  // namespace
 }  // namespace cusrl
 
 using namespace cusrl;
 
+// In every entry the kind is looked at first: an unknown one is CUSRL_E_INVALID whatever the other arguments are.
 extern "C" int cusrl_classic_step(int kind, const float *action, float *state, int32_t *steps, int64_t max_steps,
                                   float *next_observation, float *reward, uint8_t *terminated, uint8_t *truncated, int64_t N,
                                   void *stream) {
-    if (int rc = check_step(kind, action, state, steps, max_steps, next_observation, reward, terminated, truncated, N)) return rc;
-    if (N == 0) return 0;
-    if (!aligned(action, 4) || !aligned(state, 4) || !aligned(steps, 4) || !aligned(next_observation, 4) || !aligned(reward, 4))
-        return CUSRL_E_INVALID;
-    const int32_t limit = int32_t(max_steps);
-    switch (kind) {
-        case CUSRL_CLASSIC_CARTPOLE:
-            launch_step<CUSRL_CLASSIC_CARTPOLE>(action, state, steps, limit, next_observation, reward, terminated, truncated, N, as_stream(stream));
-            break;
-        case CUSRL_CLASSIC_PENDULUM:
-            launch_step<CUSRL_CLASSIC_PENDULUM>(action, state, steps, limit, next_observation, reward, terminated, truncated, N, as_stream(stream));
-            break;
-        case CUSRL_CLASSIC_MOUNTAINCAR:
-            launch_step<CUSRL_CLASSIC_MOUNTAINCAR>(action, state, steps, limit, next_observation, reward, terminated, truncated, N,
-                                                   as_stream(stream));
-            break;
-        case CUSRL_CLASSIC_ACROBOT:
-            launch_step<CUSRL_CLASSIC_ACROBOT>(action, state, steps, limit, next_observation, reward, terminated, truncated, N, as_stream(stream));
-            break;
-        default:
-            launch_step<CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS>(action, state, steps, limit, next_observation, reward, terminated, truncated, N,
-                                                             as_stream(stream));
-    }
-    return launch_status();
+    return for_task(kind, [&](auto task) {
+        if (int rc = check_step(action, state, steps, max_steps, next_observation, reward, terminated, truncated, N)) return rc;
+        if (N == 0) return 0;
+        if (!aligned(action, 4) || !aligned(state, 4) || !aligned(steps, 4) || !aligned(next_observation, 4) || !aligned(reward, 4))
+            return int(CUSRL_E_INVALID);
+        launch_step<task.value>(action, state, steps, int32_t(max_steps), next_observation, reward, terminated, truncated, N, as_stream(stream));
+        return launch_status();
+    });
 }
 
 extern "C" int cusrl_classic_step_cpu(int kind, const float *action, float *state, int32_t *steps, int64_t max_steps,
                                       float *next_observation, float *reward, uint8_t *terminated, uint8_t *truncated, int64_t N) {
-    if (int rc = check_step(kind, action, state, steps, max_steps, next_observation, reward, terminated, truncated, N)) return rc;
-    const int32_t limit = int32_t(max_steps);
-    switch (kind) {
-        case CUSRL_CLASSIC_CARTPOLE:
-            step_rows_cpu<CUSRL_CLASSIC_CARTPOLE>(action, state, steps, limit, next_observation, reward, terminated, truncated, N);
-            break;
-        case CUSRL_CLASSIC_PENDULUM:
-            step_rows_cpu<CUSRL_CLASSIC_PENDULUM>(action, state, steps, limit, next_observation, reward, terminated, truncated, N);
-            break;
-        case CUSRL_CLASSIC_MOUNTAINCAR:
-            step_rows_cpu<CUSRL_CLASSIC_MOUNTAINCAR>(action, state, steps, limit, next_observation, reward, terminated, truncated, N);
-            break;
-        case CUSRL_CLASSIC_ACROBOT:
-            step_rows_cpu<CUSRL_CLASSIC_ACROBOT>(action, state, steps, limit, next_observation, reward, terminated, truncated, N);
-            break;
-        default:
-            step_rows_cpu<CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS>(action, state, steps, limit, next_observation, reward, terminated, truncated, N);
-    }
-    return 0;
+    return for_task(kind, [&](auto task) {
+        using T = Task<task.value>;
+        if (int rc = check_step(action, state, steps, max_steps, next_observation, reward, terminated, truncated, N)) return rc;
+        for (int64_t i = 0; i < N; ++i)
+            step_env<task.value>(state + i * T::kState, action + i * T::kAction, steps[i], int32_t(max_steps),
+                                 next_observation + i * T::kObservation, reward[i], terminated[i], truncated[i]);
+        return 0;
+    });
 }
 
 extern "C" int cusrl_classic_reset(int kind, uint64_t seed, const int64_t *indices, const int32_t *count, float *state, int32_t *steps,
                                    int64_t *episode, float *observation_out, int64_t rows, int randomize_progress, int64_t max_steps,
                                    int64_t N, void *stream) {
-    if (int rc = check_reset(kind, indices, state, steps, episode, observation_out, rows, max_steps, N)) return rc;
-    if (rows == 0) return 0;
-    if (!aligned(indices, 8) || !aligned(episode, 8) || !aligned(state, 4) || !aligned(steps, 4) || !aligned(observation_out, 4) ||
-        (count && !aligned(count, 4)))
-        return CUSRL_E_INVALID;
-    const dim3 grid(uint32_t(ceil_div(rows, kBlock))), block(kBlock);
-    const int32_t limit = int32_t(max_steps);
-    const int randomize = randomize_progress != 0;
-    switch (kind) {
-        case CUSRL_CLASSIC_CARTPOLE:
-            hipLaunchKernelGGL(classic_reset_kernel<CUSRL_CLASSIC_CARTPOLE>, grid, block, 0, as_stream(stream), seed, indices, count, state,
-                               steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        case CUSRL_CLASSIC_PENDULUM:
-            hipLaunchKernelGGL(classic_reset_kernel<CUSRL_CLASSIC_PENDULUM>, grid, block, 0, as_stream(stream), seed, indices, count, state,
-                               steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        case CUSRL_CLASSIC_MOUNTAINCAR:
-            hipLaunchKernelGGL(classic_reset_kernel<CUSRL_CLASSIC_MOUNTAINCAR>, grid, block, 0, as_stream(stream), seed, indices, count,
-                               state, steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        case CUSRL_CLASSIC_ACROBOT:
-            hipLaunchKernelGGL(classic_reset_kernel<CUSRL_CLASSIC_ACROBOT>, grid, block, 0, as_stream(stream), seed, indices, count, state,
-                               steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        default:
-            hipLaunchKernelGGL(classic_reset_kernel<CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS>, grid, block, 0, as_stream(stream), seed, indices,
-                               count, state, steps, episode, observation_out, rows, randomize, limit, N);
-    }
-    return launch_status();
+    return for_task(kind, [&](auto task) {
+        if (int rc = check_reset(indices, state, steps, episode, observation_out, rows, max_steps, N)) return rc;
+        if (rows == 0) return 0;
+        if (!aligned(indices, 8) || !aligned(episode, 8) || !aligned(state, 4) || !aligned(steps, 4) || !aligned(observation_out, 4) ||
+            (count && !aligned(count, 4)))
+            return int(CUSRL_E_INVALID);
+        launch_reset<task.value>(seed, indices, count, state, steps, episode, observation_out, rows, randomize_progress != 0,
+                                 int32_t(max_steps), N, as_stream(stream));
+        return launch_status();
+    });
 }
 
 extern "C" int cusrl_classic_reset_cpu(int kind, uint64_t seed, const int64_t *indices, const int32_t *count, float *state,
                                        int32_t *steps, int64_t *episode, float *observation_out, int64_t rows, int randomize_progress,
                                        int64_t max_steps, int64_t N) {
-    if (int rc = check_reset(kind, indices, state, steps, episode, observation_out, rows, max_steps, N)) return rc;
-    const int32_t limit = int32_t(max_steps);
-    const int randomize = randomize_progress != 0;
-    switch (kind) {
-        case CUSRL_CLASSIC_CARTPOLE:
-            reset_rows_cpu<CUSRL_CLASSIC_CARTPOLE>(seed, indices, count, state, steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        case CUSRL_CLASSIC_PENDULUM:
-            reset_rows_cpu<CUSRL_CLASSIC_PENDULUM>(seed, indices, count, state, steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        case CUSRL_CLASSIC_MOUNTAINCAR:
-            reset_rows_cpu<CUSRL_CLASSIC_MOUNTAINCAR>(seed, indices, count, state, steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        case CUSRL_CLASSIC_ACROBOT:
-            reset_rows_cpu<CUSRL_CLASSIC_ACROBOT>(seed, indices, count, state, steps, episode, observation_out, rows, randomize, limit, N);
-            break;
-        default:
-            reset_rows_cpu<CUSRL_CLASSIC_MOUNTAINCARCONTINUOUS>(seed, indices, count, state, steps, episode, observation_out, rows, randomize,
-                                                                limit, N);
-    }
-    return 0;
+    return for_task(kind, [&](auto task) {
+        if (int rc = check_reset(indices, state, steps, episode, observation_out, rows, max_steps, N)) return rc;
+        for (int64_t k = 0; k < rows; ++k)
+            reset_slot<task.value>(k, seed, indices, count, state, steps, episode, observation_out, rows, randomize_progress != 0,
+                                   int32_t(max_steps), N);
+        return 0;
+    });
 }

@@ -16,7 +16,8 @@ __all__ = ["CLASSIC_TASKS", "ClassicTask", "classic_reset", "classic_reset_cpu",
 
 
 class ClassicTask:
-    """One task's code and row widths (``CUSRL_CLASSIC_*`` of the header; the widths as ``Task<kind>`` of the kernel file)."""
+    """One task's code and row widths (``CUSRL_CLASSIC_*`` of the header; the widths as in the task's ``Task<kind>`` block of the kernel file,
+    which also holds its formulas)."""
 
     def __init__(self, name: str, constant: str, state_dim: int, action_dim: int, observation_dim: int, max_episode_steps: int):
         self.name, self.kind = name, _native._CONSTANTS[constant]

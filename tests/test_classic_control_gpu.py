@@ -1,7 +1,8 @@
-"""The classic-control kernels (``csrc/environment.hip``) on the GPU: against the float64 formulas and the library's host
-restatement, the reset contract, the launch census, the captured rollout against the host-driven loop, and the project's first
-learning test — PPO on the device-resident CartPole against curves recorded from the reference
-(tests/golden/make_classic_control_golden.py).  The host form: tests/test_classic_control.py."""
+"""The classic-control kernels (``csrc/environment.hip``) on the GPU, all five tasks: against the float64 formulas and the
+library's host restatement, a misaligned state, canary rows around every operand, the reset contract, the launch census, the
+captured rollout against the host-driven loop, and the project's first learning test — PPO on the device-resident CartPole against
+curves recorded from the reference (tests/golden/make_classic_control_golden.py).  The host form: tests/test_classic_control.py.
+No row here holds a non-finite value: that run is host only."""
 
 import ctypes
 
@@ -10,7 +11,7 @@ import pytest
 import torch
 
 from _classic_control import (
-    HOST_ERROR, RANDOM_ROWS, SEED, TASKS, assert_exact_parts, inputs, reference_step, reset_cases, run_step, step_error,
+    HOST_ERROR, RANDOM_ROWS, TASKS, TRIG_COLUMNS, assert_exact_parts, inputs, reference_step, reset_cases, run_step, step_error,
 )
 
 pytestmark = pytest.mark.gpu
@@ -54,7 +55,9 @@ def _assert_against_both(name, result, float64, host):
     error = step_error(result, float64)
     print(f"{name}: kernel vs float64, scaled error {error:.3e} (asserted {4 * HOST_ERROR[name]:.1e}), rows {result['state'].shape[0]}")
     assert_exact_parts(result, float64, name)  # flags and step counter as the formulas give them ...
-    for key in ("terminated", "truncated", "steps", "reward"):  # ... and everything without a transcendental: the host form's bits
+    # ... and everything without a transcendental in front of it, the host form's bits: flags, counter, the rewards that are a
+    # function of the flag.  MountainCarContinuous's reward is too wherever the flag agrees: 100 or 0 minus 0.1 a a.
+    for key in ("terminated", "truncated", "steps", "reward"):
         assert torch.equal(result[key].cpu(), host[key]), (name, key)
     mask = torch.from_numpy(float64["saturated"])
     assert torch.equal(result["state"].cpu()[mask], host["state"][mask]), name  # a clamp that saturates is its bound
@@ -74,6 +77,7 @@ def test_kernel_against_float64_and_the_host_restatement(cusrl, references, name
 
 @pytest.mark.parametrize("name", NAMES)
 def test_a_state_one_float_off_a_16_byte_boundary_gives_the_same_bits(cusrl, references, name):
+    """The scalar path of the kernel (state rows and, for Acrobot, the observation rows) against the vector path."""
     from cusrl_amd import ops
 
     state, action, steps, max_steps = references[name]["inputs"]
@@ -92,27 +96,37 @@ def test_a_state_one_float_off_a_16_byte_boundary_gives_the_same_bits(cusrl, ref
     _assert_against_both(name, result, references[name]["float64"], references[name]["host"])
 
 
+@pytest.mark.parametrize("offset", [0, 1])
 @pytest.mark.parametrize("name", NAMES)
-def test_a_launch_stays_inside_its_rows(cusrl, references, name):
-    """The C entry on over-allocated buffers, canary rows before and after every operand: rows outside [0, N) keep their bits,
-    the rows inside equal the first launch's."""
+def test_a_launch_stays_inside_its_rows(cusrl, references, name, offset):
+    """The C entry on over-allocated buffers, canary rows before and after every operand: rows outside [0, N) keep their bits, the
+    rows inside equal the first launch's.  ``offset = 1``: the observation buffer starts one float further on, off the 8- or
+    16-byte boundary its vector stores need, so the rows (Acrobot's 6-wide ones among them) go out as scalars — the same bits as
+    the vector stores of ``offset = 0``.  (Pendulum's 3-wide rows are scalar stores at either offset.)"""
     from cusrl_amd import _native, ops
 
     state, action, steps, max_steps = references[name]["inputs"]
     first = _device_step(name, state, action, steps, max_steps)
     N, task, pad = state.shape[0], ops.CLASSIC_TASKS[name], 3
 
-    def padded(rows: torch.Tensor, canary):
+    def padded(rows: torch.Tensor, canary, shift=0):
         rows = rows.reshape(N, -1)
-        buffer = torch.full((N + 2 * pad, rows.shape[1]), canary, dtype=rows.dtype, device=DEV)
+        width = rows.shape[1]
+        flat = torch.full(((N + 2 * pad) * width + shift,), canary, dtype=rows.dtype, device=DEV)
+        buffer = flat[shift:].view(N + 2 * pad, width)
         buffer[pad : pad + N] = rows.to(DEV)
-        return buffer
+        return buffer, flat
 
-    buffers = dict(action=padded(action, 7.5), state=padded(state, -3.25), steps=padded(steps, 12345),
-                   observation=padded(torch.zeros(N, task.observation_dim), 9.75), reward=padded(torch.zeros(N, 1), 6.5),
-                   terminated=padded(torch.zeros(N, 1, dtype=torch.uint8), 77), truncated=padded(torch.zeros(N, 1, dtype=torch.uint8), 78))
+    buffers, flats = {}, {}
+    for key, rows, canary, shift in (
+            ("action", action, 7.5, 0), ("state", state, -3.25, 0), ("steps", steps, 12345, 0),
+            ("observation", torch.zeros(N, task.observation_dim), 9.75, offset), ("reward", torch.zeros(N, 1), 6.5, 0),
+            ("terminated", torch.zeros(N, 1, dtype=torch.uint8), 77, 0), ("truncated", torch.zeros(N, 1, dtype=torch.uint8), 78, 0)):
+        buffers[key], flats[key] = padded(rows, canary, shift)
     before = {key: value.clone() for key, value in buffers.items()}
     inner = {key: value[pad:].data_ptr() for key, value in buffers.items()}
+    odd = pad * task.observation_dim % 2  # (Pendulum alone: its 3 canary rows already end 4 bytes off)
+    assert inner["observation"] % 8 == 4 * ((offset + odd) % 2) and inner["state"] % (4 * task.state_dim) == 0
     status = _native.lib().cusrl_classic_step(task.kind, inner["action"], inner["state"], inner["steps"], max_steps, inner["observation"],
                                               inner["reward"], inner["terminated"], inner["truncated"], N,
                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -120,6 +134,7 @@ def test_a_launch_stays_inside_its_rows(cusrl, references, name):
     torch.cuda.synchronize()
     for key, value in buffers.items():
         assert torch.equal(value[:pad], before[key][:pad]) and torch.equal(value[pad + N :], before[key][pad + N :]), (name, key)
+    assert (flats["observation"][:offset] == 9.75).all()
     assert torch.equal(buffers["action"], before["action"])
     for key in ("state", "observation", "reward"):
         assert torch.equal(buffers[key][pad : pad + N], first[key].reshape(N, -1)), (name, key)
@@ -132,17 +147,19 @@ def test_a_launch_stays_inside_its_rows(cusrl, references, name):
 @pytest.mark.parametrize("name", NAMES)
 def test_reset_contract_and_the_host_forms_bits(cusrl, name, N):
     """Every reset case on the device, and state / steps / episode / observation bit-identical to the host restatement's.  The one
-    exception is stated in DESIGN.md §7: Pendulum's observation holds cos / sin of the fresh angle, the device's and not glibc's —
-    those two columns are held to the float64 values within the kernel bound instead (inside ``reset_cases``)."""
+    exception is stated in DESIGN.md §7: the observation columns that are cos / sin of a fresh angle (Pendulum's first two,
+    Acrobot's first four) are the device's and not glibc's — those are held to the float64 values within the kernel bound instead
+    (inside ``reset_cases``), the columns after them to the bits."""
     from cusrl_amd import ops
 
     device = reset_cases(ops.classic_reset, name, torch.device(DEV), N)
     host = reset_cases(ops.classic_reset_cpu, name, torch.device("cpu"), N)
     assert device.keys() == host.keys()
+    trig = TRIG_COLUMNS.get(name, 0)
     for case in device:
         for index, (a, b) in enumerate(zip(device[case], host[case])):
-            if name == "Pendulum" and isinstance(case, tuple) and index == 0:  # the observation rows
-                assert torch.equal(a[:, 2], b[:, 2]), (name, case)
+            if isinstance(case, tuple) and index == 0:  # the observation rows
+                assert torch.equal(a[:, trig:], b[:, trig:]), (name, case)
             else:
                 assert torch.equal(a, b), (name, case, index)
 
@@ -182,18 +199,20 @@ def _train(cusrl, name, capture):
     env = cusrl.environment.make(name, 8, device=DEV, max_episode_steps=16)
     common = dict(num_steps_per_update=T, sampler_epochs=2, sampler_mini_batches=2, compile=True, actor_hidden_dims=(64, 64),
                   critic_hidden_dims=(64, 64), activation_fn="Tanh", optimizer_kwargs={"capturable": True, "fused": True})
-    factory = cusrl.preset.PpoAgentFactory(action_space_type="discrete" if name == "CartPole" else "continuous", **common)
+    discrete = TASKS[name]["A"] > 1  # logits: CartPole, MountainCar, Acrobot; one torque or force: Pendulum, MountainCarContinuous
+    factory = cusrl.preset.PpoAgentFactory(action_space_type="discrete" if discrete else "continuous", **common)
     trainer = cusrl.Trainer(env, factory, num_iterations=4, verbose=False)
     trainer.capture_rollout = capture
     trainer.run_training_loop()
     return trainer
 
 
-@pytest.mark.parametrize("name", ["CartPole", "Pendulum"])
+@pytest.mark.parametrize("name", NAMES)
 def test_captured_rollout_is_bit_identical_to_the_host_driven_loop(cusrl, name):
     """8 envs, 16-step episodes, 12-step rollouts, 4 iterations from the same seed, host-driven against ``compile=True`` capture:
-    every buffer leaf, every parameter, the episode statistics and the env's own state / steps / episode — the first env with
-    per-instance state to go through the ``reset_static`` contract."""
+    every buffer leaf, every parameter, the episode statistics and the env's own state / steps / episode — the envs with
+    per-instance state that go through the ``reset_static`` contract.  The tasks with logits run the discrete preset, the other two
+    the continuous one.  CartPole's poles do fall within 16 steps, Pendulum never terminates."""
     T = 12
     host, captured = _train(cusrl, name, False), _train(cusrl, name, True)
     assert host._graphed_rollout is None and host._static_resets
@@ -211,7 +230,9 @@ def test_captured_rollout_is_bit_identical_to_the_host_driven_loop(cusrl, name):
     for attr in ("state", "steps", "episode"):
         assert torch.equal(getattr(host.environment, attr), getattr(captured.environment, attr)), attr
     assert (host.environment.episode > 1).all() and (host.environment.steps <= 16).all()
-    assert a.buffer["truncated"].any() and (a.buffer["terminated"].any() if name == "CartPole" else not a.buffer["terminated"].any())
+    assert a.buffer["truncated"].any()
+    if name in ("CartPole", "Pendulum"):
+        assert a.buffer["terminated"].any() == (name == "CartPole")
 
 
 def test_ppo_learns_cartpole_like_the_reference(cusrl, golden):
