@@ -66,6 +66,7 @@ from cusrl_amd.ops.recurrent import (
     gru_bias_partial_rows, gru_bias_partials_supported, gru_gates_backward, gru_gates_forward, lstm_gates_backward,
     lstm_gates_forward, rnn_cell_backward, rnn_cell_forward,
 )
+from cusrl_amd.ops.reward import reward_normalize_, reward_normalize_cpu_
 from cusrl_amd.ops.rollout import (
     PendingStepEpilogue, categorical_sample_logp, episode_stats, normal_sample_logp, play_epilogue, play_epilogue_workspace,
     step_epilogue, synthetic_env_step,

@@ -1237,6 +1237,41 @@ int cusrl_classic_reset_cpu(int kind, uint64_t seed, const int64_t *indices, con
                             int64_t *episode, float *observation_out, int64_t rows, int randomize_progress, int64_t max_steps,
                             int64_t N);
 
+/* ---- RewardNormalization.post_step (cusrl_amd/hook/mdp/reward.py): rewards divided by the running standard deviation of the
+ * discounted return, as gymnasium's NormalizeReward and SB3's VecNormalize(norm_reward=True) do; the reference has no such hook
+ * (its users scale IsaacLab rewards by hand); additive entries of ABI 7; csrc/reward_norm.hip ----
+ * Operands: reward [N, R] and G [N, R] contiguous fp32 (G: the discounted return per env and reward column), terminated and
+ * truncated [N] one-byte flags (done = terminated | truncated), stats [3, R] contiguous float64: row 0 the running mean, row 1
+ * the running variance, row 2 the running count of G, per column (a fresh triple is 0, 1, 1e-4).  ONE launch, in this order:
+ *   1. G[i, c] = G[i, c] * gamma + reward[i, c]                          fp32, the product and the sum rounded separately
+ *   2. update != 0, per column c, all in float64:
+ *        pivot = G[0, c] (the new one);  s = sum_i (G[i, c] - pivot);  q = sum_i (G[i, c] - pivot)^2;  d = s / N
+ *        batch_mean = pivot + d;  batch_var = q / N - d d, a negative one 0  (population variance; a NaN stays a NaN)
+ *        w_sum = count + N;  w_new = N / w_sum;  w_old = count / w_sum;  delta = batch_mean - mean
+ *        mean = mean + delta w_new;  var = var + ((batch_var - var) w_new + (delta delta) (w_old w_new));  count = w_sum
+ *      (the weighted parallel-variance merge of cusrl_amd/nn/rms.py merge_mean_var_).  update == 0: stats is only read.
+ *   3. scale = (float) sqrt(var[c] + epsilon), the float64 root rounded to fp32 once;  reward[i, c] = reward[i, c] / scale, one
+ *      correctly rounded fp32 division per element (never a multiplication by a reciprocal).  The mean is NOT subtracted.
+ *   4. has_clip != 0: v < -clip ? -clip : v, then v > clip ? clip : v (a NaN stays a NaN)
+ *   5. G[i, c] = 0 where done[i]
+ * Nothing is filtered: a NaN or Inf reward enters G and, with update != 0, its column's statistics — every reward of that column
+ * is then non-finite from this call on — and the call returns.  No loop's trip count depends on data.
+ * Launch shape and summation order: one block of 1024 threads per column.  Rows go in chunks of 4 consecutive rows; thread t
+ * owns the chunks t, t + 1024, t + 2048, ... and adds their rows to its own (s, q) in ascending row order; the 64 lanes of a wave
+ * are summed by the halving tree (lane l += lane l + 32, then 16, 8, 4, 2, 1), the 16 wave totals in wave order starting from 0.
+ * The order is a function of N alone: the same operands give the same bits every call.  With R == 1, reward and G 16-byte aligned
+ * and both flag arrays 4-byte aligned a whole chunk moves as one 16-byte access per array (the flags as 4 bytes), as scalars
+ * otherwise: the same bits.  No atomics, no hand-off between blocks, plain vector stores; no host synchronisation, so the launch
+ * may be captured.  N == 0 launches nothing.  CUSRL_E_INVALID, nothing launched: N < 0, R < 1, a NULL pointer with N > 0, a
+ * reward or G that is not 4-byte aligned, a stats that is not 8-byte aligned, has_clip != 0 with a clip that is negative or a
+ * NaN.  CUSRL_E_UNSUPPORTED: R above 65535, N * R beyond int64.
+ * cusrl_reward_normalize_cpu runs the same __host__ __device__ element, merge and scale bodies on the host and visits the rows
+ * in the order above (every pointer a HOST pointer, no stream): the hook's host form and what the GPU tests compare against. */
+int cusrl_reward_normalize(float *reward, float *G, const uint8_t *terminated, const uint8_t *truncated, double *stats, float gamma,
+                           double epsilon, float clip, int has_clip, int update, int64_t N, int64_t R, void *stream);
+int cusrl_reward_normalize_cpu(float *reward, float *G, const uint8_t *terminated, const uint8_t *truncated, double *stats,
+                               float gamma, double epsilon, float clip, int has_clip, int update, int64_t N, int64_t R);
+
 
 /* ---- a6 / a14 data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the

@@ -310,6 +310,13 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
     rows.measure(f"nan_to_num all-NaN + refill [N,{obs}]", lambda: ops.nan_to_num_(dirty.fill_(float("nan"))), N * obs * 12)
     rows.measure(f"refill alone (fill_) [N,{obs}]", lambda: dirty.fill_(float("nan")), N * obs * 4)
 
+    # ---- reward normalisation (RewardNormalization): one [N, 1] reward, its return and both flags, one block per reward column.
+    # Bytes: pass 1 reads and writes the return and reads the reward, pass 2 reads and writes the reward and reads the flags.
+    r1, g1 = f(N, 1), torch.zeros(N, 1, device=DEV)
+    flag1 = torch.zeros(N, 1, dtype=torch.bool, device=DEV)
+    triple = torch.tensor([[0.0], [1.0], [1e-4]], dtype=torch.float64, device=DEV)
+    rows.measure("reward normalize [N,1]", lambda: ops.reward_normalize_(r1, g1, flag1, flag1, triple, 0.99, 1e-8, 10.0), N * 22)
+
     # ---- reference points: a plain device copy of the same bytes (what the memory system gives a streaming kernel)
     big = torch.empty(max(S * 21 // 8, 1024), dtype=torch.float32, device=DEV)
     dst = torch.empty_like(big)
