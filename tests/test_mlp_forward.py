@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from _mlp_forward import _reference, stack
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -21,23 +23,7 @@ def ops():
 
 
 def _stack(K, H1, H2, A, seed, bias3=True):
-    g = torch.Generator().manual_seed(seed)
-    make = lambda *shape, scale: (torch.randn(*shape, generator=g) * scale).to(DEV)  # noqa: E731
-    return (make(H1, K, scale=K ** -0.5), make(H1, scale=0.3), make(H2, H1, scale=H1 ** -0.5), make(H2, scale=0.3),
-            make(A, H2, scale=H2 ** -0.5), make(A, scale=0.3) if bias3 else None)
-
-
-def _reference(x, layers):
-    """float64, plus the magnitude the fp32 sums accumulate: |w3| (|w2| relu(...) + |b2|) + |b3| — the yardstick of the bound."""
-    w1, b1, w2, b2, w3, b3 = [None if t is None else t.double().cpu() for t in layers]
-    x = x.double().cpu()
-    h1 = torch.relu(x @ w1.T + b1)
-    h2 = torch.relu(h1 @ w2.T + b2)
-    out = h2 @ w3.T + (0 if b3 is None else b3)
-    m1 = x.abs() @ w1.abs().T + b1.abs()
-    m2 = m1 @ w2.abs().T + b2.abs()
-    mag = m2 @ w3.abs().T + (0 if b3 is None else b3.abs())
-    return out, mag
+    return stack(K, H1, H2, A, seed, bias3, device=DEV)
 
 
 @pytest.mark.parametrize("rows,K,H1,H2,A", [
