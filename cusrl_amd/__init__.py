@@ -22,7 +22,8 @@ from cusrl_amd.nn import (
 )
 from cusrl_amd.nn import CausalMultiheadSelfAttention, CausalTransformerEncoderLayer, compute_segment_ids, get_alibi_slopes
 from cusrl_amd.nn import Cnn, CnnFactory, LearnablePositionalEncoding2D, SeparableConv2d, SinusoidalPositionalEncoding2D
-from cusrl_amd.nn import DeployedPolicy, ExpertPolicy, Identity, InferenceWrapper, StubModule
+from cusrl_amd.nn import DeployedPolicy, ExpertPolicy, Identity, InferenceWrapper, ObservationStacker, StubModule
+from cusrl_amd.environment import FrameStack
 from cusrl_amd.sampler import (
     AutoMiniBatchSampler, AutoRandomSampler, MiniBatchSampler, RandomSampler, TemporalMiniBatchSampler, TemporalRandomSampler,
 )
@@ -150,4 +151,6 @@ __all__ = [
     "Trial",
     "make_logger_factory",
     "zoo",
+    "FrameStack",
+    "ObservationStacker",
 ]

@@ -131,9 +131,15 @@ _REGISTRY.update({"CartPole-v1": CartPole, "Pendulum-v1": Pendulum, "MountainCar
                   "MountainCarContinuous-v0": MountainCarContinuous})
 
 
-def make(name: str, num_instances: int = 1, **kwargs) -> ClassicControlEnvironment:
+def make(name: str, num_instances: int = 1, *, frame_stack: int | None = None, **kwargs) -> Environment:
     """``make("CartPole", 64, device="cuda:0")``; the names: CartPole, Pendulum, MountainCar, and the gym ids CartPole-v1,
-    Pendulum-v1, MountainCar-v0, Acrobot-v1, MountainCarContinuous-v0."""
+    Pendulum-v1, MountainCar-v0, Acrobot-v1, MountainCarContinuous-v0.  ``frame_stack=S`` wraps the task in
+    ``FrameStack(env, S)`` (None: the bare task)."""
     if name not in _REGISTRY:
         raise ValueError(f"unknown environment {name!r}; available: {', '.join(_REGISTRY)}")
-    return _REGISTRY[name](num_instances, **kwargs)
+    env = _REGISTRY[name](num_instances, **kwargs)
+    if frame_stack is None:
+        return env
+    from cusrl_amd.environment.frame_stack import FrameStack
+
+    return FrameStack(env, frame_stack)

@@ -24,6 +24,7 @@ from cusrl_amd.nn.rnn import Gru, Lstm, Rnn
 from cusrl_amd.nn.separable_conv import SeparableConv2d
 from cusrl_amd.nn.sequential import Sequential, SequentialFactory
 from cusrl_amd.nn.simba import Simba, SimbaBlock, SimbaFactory
+from cusrl_amd.nn.stacker import ObservationStacker
 from cusrl_amd.nn.stub import Identity, StubModule
 from cusrl_amd.nn.transformer import TransformerDecoderLayer, TransformerEncoderLayer
 
@@ -93,6 +94,7 @@ __all__ = [
     "ExpertPolicy",
     "Identity",
     "InferenceWrapper",
+    "ObservationStacker",
     "StubModule",
 ]
 

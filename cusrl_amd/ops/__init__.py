@@ -46,6 +46,10 @@ from cusrl_amd.ops.deploy import deploy_epilogue_, deploy_epilogue_cpu_, deploy_
 from cusrl_amd.ops.environment import (
     CLASSIC_TASKS, ClassicTask, classic_reset, classic_reset_cpu, classic_step, classic_step_cpu,
 )
+from cusrl_amd.ops.frame_stack import (
+    frame_stack_columns, frame_stack_padding, frame_stack_push, frame_stack_push_cpu, frame_stack_reset, frame_stack_reset_cpu,
+    frame_stack_supported,
+)
 from cusrl_amd.ops.gate import GateCombine, Glu, gate_backward, gate_combine, gate_supported, glu, glu_backward, glu_supported
 from cusrl_amd.ops.gradient import (
     DeferredColumns, adam_norm_workspace, adam_step, adam_step_normed, adam_step_window, assemble_gradients, clip_grad_norm_,

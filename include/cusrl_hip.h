@@ -1272,6 +1272,53 @@ int cusrl_reward_normalize(float *reward, float *G, const uint8_t *terminated, c
 int cusrl_reward_normalize_cpu(float *reward, float *G, const uint8_t *terminated, const uint8_t *truncated, double *stats,
                                float gamma, double epsilon, float clip, int has_clip, int update, int64_t N, int64_t R);
 
+/* ---- frame stacking: the observation history of cusrl_amd.nn.ObservationStacker and cusrl_amd.environment.FrameStack
+ * (gymnasium's FrameStackObservation(env, stack_size, padding_type); the reference has no such wrapper; additive entries of
+ * ABI 7; csrc/frame_stack.hip) ----
+ * Operands: the history H [N, S, K], persistent contiguous fp32, slot 0 the oldest observation and slot S - 1 the newest; a
+ * stacked observation is the same memory order, [N, S * K]: out[n, s * K + k].  The source rows are [.., K0] contiguous fp32.
+ * columns: int32 [K] device vector of distinct indices into K0, the columns that are kept, in their order (NULL: K == K0, every
+ * column in place; an entry outside [0, K0) reads nothing and stacks +0.0).  padding: how a fresh history is filled from its
+ * first observation v — CUSRL_FRAME_STACK_PAD_RESET: every slot is v; CUSRL_FRAME_STACK_PAD_ZERO: slots 0 .. S - 2 are +0.0 and
+ * slot S - 1 is v.  Both launches only MOVE 32-bit words: NaN payloads, -0.0 and +-Inf pass bit for bit, no arithmetic is done.
+ *
+ * cusrl_frame_stack_push, ONE launch: for every row n, H[n, s] = H[n, s + 1] for s < S - 1, then H[n, S - 1] = obs[n, columns];
+ * out [N, S * K] is the new H, a buffer of its own (out overlapping H is refused).  fresh != NULL (N one-byte flags): a row
+ * whose flag is set is not shifted but refilled from obs[n] by the padding rule, and the launch clears that flag; the other
+ * flags are not written.  One lane owns one column (n, k) through all S slots and walks them in ascending order, reading slot
+ * s + 1 before it writes slot s: no lane reads a word another lane writes, whatever S is.  A block takes whole rows; the lanes of
+ * a row read its flag in front of the block's barrier and the flag is cleared behind it, by that block alone.
+ *
+ * cusrl_frame_stack_reset, ONE launch, one lane per (slot j, column k): live = count ? *count : L, read on the device (clamped
+ * to 0 .. L; count NULL: every slot is valid — the host path and the all-env reset).  indices: int64 [L] env ids; reset_obs
+ * [L, K0], row j belonging to env indices[j]; out [L, S * K].
+ *   j < live:   H[indices[j]] is refilled from reset_obs[j, columns] by the padding rule; out[j] is the refilled row.  The ids of
+ *               the first `live` slots are distinct (the trainer's step epilogue guarantees it).
+ *   j >= live:  a stale but valid env id whose row the caller drops: H is NOT written, out[j] is what H[indices[j]] holds.
+ * A stale slot may name the same env as a valid one: stale lanes never write H, so the history is what the valid slot wrote, and
+ * the stale out row — the env's history from before or after this launch's refill, word by word — is dropped by the caller.
+ * An id outside [0, N) is skipped: no history is touched and its out row is +0.0.
+ *
+ * Both: 4-byte aligned pointers work; with columns == NULL, K % 4 == 0 and H, the source and out 16-byte aligned a lane moves
+ * four adjacent columns as one 16-byte word, otherwise one column: the same bits either way.  Grid-stride loops over at most 2048
+ * blocks of 256 threads.  The source must not overlap H or out.  Plain vector stores, no atomics, no host synchronisation: the
+ * launches may be captured.  N == 0 (push) / L == 0 (reset) launch nothing.  CUSRL_E_INVALID, nothing launched: a negative N
+ * or L, S, K or K0 below 1, columns == NULL with K != K0, an unknown padding code, a NULL or misaligned pointer among those the
+ * call uses (columns, fresh and count may be NULL), out overlapping H.  CUSRL_E_UNSUPPORTED: S, K or K0 above INT32_MAX, a
+ * byte count beyond int64.
+ * The `_cpu` entries restate the two kernels on the host, word by word (every pointer a HOST pointer, no stream; slots in
+ * ascending j): the host form of the two classes and what the GPU tests compare the kernels' bits against. */
+#define CUSRL_FRAME_STACK_PAD_RESET 0
+#define CUSRL_FRAME_STACK_PAD_ZERO 1
+int cusrl_frame_stack_push(float *H, const float *obs, const int32_t *columns, uint8_t *fresh, float *out, int64_t N, int64_t S,
+                           int64_t K, int64_t K0, int padding, void *stream);
+int cusrl_frame_stack_push_cpu(float *H, const float *obs, const int32_t *columns, uint8_t *fresh, float *out, int64_t N, int64_t S,
+                               int64_t K, int64_t K0, int padding);
+int cusrl_frame_stack_reset(float *H, const int64_t *indices, const int32_t *count, const float *reset_obs, const int32_t *columns,
+                            float *out, int64_t L, int64_t N, int64_t S, int64_t K, int64_t K0, int padding, void *stream);
+int cusrl_frame_stack_reset_cpu(float *H, const int64_t *indices, const int32_t *count, const float *reset_obs, const int32_t *columns,
+                                float *out, int64_t L, int64_t N, int64_t S, int64_t K, int64_t K0, int padding);
+
 
 /* ---- a6 / a14 data-parallel exchange over RCCL / xGMI — cusrl/utils/distributed.py:58-63, 101-110, 145-183 ----
  * One process per GPU (cusrl/utils/config.py:31-44); a communicator spans all ranks of the job and binds to the
