@@ -1,9 +1,6 @@
 // Reward-side hooks of a captured env step and the auxiliary objectives of a minibatch step as
 // single launches:
 //   cusrl_reward_shaping        RewardShaping.post_step         cusrl/hook/mdp/reward.py:43-47   (mul_, add_, clamp_)
-//   cusrl_amp_prepare           AdversarialMotionPrior.post_step cusrl/hook/auxiliary/amp.py:112-128
-//                               state[idx] || next_state[idx], dataset[indices], two running-statistics updates, two
-//                               normalisations: TWO launches instead of cat + index + 2 x (stats, finalize, merge) + 2 x normalise
 //   cusrl_amp_style_reward_mean the style reward (amp.py:130-134) + the mean the metric records, one launch
 //   cusrl_mse_loss_fwd_bwd      nn.MSELoss(predictor(x), target(x)) of RandomNetworkDistillation.objective (rnd.py:78-81):
 //                               loss and d loss / d prediction in one pass
@@ -14,8 +11,7 @@
 //                               the observation AND the state in one launch, storing only what it replaced
 // All of these are a few hundred KB per launch at 4096 envs: latency-bound chains of tiny kernels in the reference's form,
 // so what counts is the NUMBER of dependent launches inside the captured step (>= 1.5 us each + their own latency).
-#include <string.h>
-
+// (AMP's transition preparation, cusrl_amp_prepare, is a running-statistics update: csrc/normalization.hip.)
 #include "common.hpp"
 #include "loss_reduce.hpp"
 #include "philox.hpp"
@@ -37,9 +33,8 @@ __global__ __launch_bounds__(kBlock) void reward_shaping_kernel(float *__restric
 }
 
 // --------------------------------------------------------------------------------------------- observation sanitiser
-// tensor.nan_to_num_(nan, posinf, neginf) of up to TWO fp32 arrays in one launch, classified on the bit pattern: exponent all
-// ones and a mantissa -> `nan` (any sign, any payload), +Inf -> `posinf`, -Inf -> `neginf`; every other pattern (-0.0,
-// denormals, +-FLT_MAX) is never rewritten, so no floating-point mode can touch it.  STORE ON CHANGE: a lane writes its 16
+// tensor.nan_to_num_(nan, posinf, neginf) of up to TWO fp32 arrays in one launch, classified on the bit pattern by
+// nan_to_num_word (common.hpp): a finite pattern is never rewritten.  STORE ON CHANGE: a lane writes its 16
 // bytes (or its scalar) back only when a value in it was replaced by a different pattern — on clean input, the common case, the
 // launch is a pure read stream of 4 B per element.  No element is touched by two threads: nothing to order.
 // Per array: a scalar head up to the first 16-byte boundary (<= 3 elements; observation tensors can be offset views, only
@@ -50,8 +45,7 @@ constexpr int kSanitizeMaxBlocks = 2048;                      // 8 blocks per CU
 constexpr int64_t kSanitizeSpan = int64_t(kBlock) * 2 * 4;    // elements of one array one block covers per pass
 
 __device__ __forceinline__ bool sanitize_word(uint32_t &bits, uint32_t nan, uint32_t posinf, uint32_t neginf) {
-    if ((bits & 0x7f800000u) != 0x7f800000u) return false;  // finite
-    const uint32_t to = (bits & 0x007fffffu) ? nan : ((bits >> 31) ? neginf : posinf);
+    const uint32_t to = nan_to_num_word(bits, nan, posinf, neginf);
     const bool changed = to != bits;  // (posinf = +Inf leaves an infinity alone: nothing to store)
     bits = to;
     return changed;
@@ -95,172 +89,6 @@ __global__ __launch_bounds__(kBlock) void nan_to_num2_kernel(uint32_t *__restric
     const int64_t tid = int64_t(blockIdx.x) * kBlock + threadIdx.x, stride = int64_t(gridDim.x) * kBlock;
     if (na > 0) sanitize_array<NT>(a, na, tid, stride, nan, posinf, neginf);
     if (nb > 0) sanitize_array<NT>(b, nb, tid, stride, nan, posinf, neginf);
-}
-
-// --------------------------------------------------------------------------------------------- AMP transition preparation
-// Two launches: (A) every block assembles its slice of the agent rows and fetches its slice of the expert rows (raw, into the
-// output buffers) and leaves fp64 {sum, sumsq} per channel of both; block 0 also snapshots the running statistics.
-// (B) every block folds the <= 64 partial rows itself (L2-resident, fixed order), replays the two Chan merges from the
-// snapshot — so no block depends on another block's result — normalises its slice in place; block 0 publishes the new
-// running statistics.  (A single-workgroup form of the whole step measured 118 us: one CU's latency chain.)
-constexpr int kPrepMaxC = 128;
-constexpr int kPrepMaxBlocks = 64;
-constexpr int kPrepItems = 8;  // elements per thread and tensor
-
-// workspace layout (doubles): [P][2 tensors][C][2] partial sums, then the snapshot: mean[C], var[C], count, then the
-// pivots: agent[C], expert[C].  The sums are of x - pivot (row 0's agent / expert value of the channel, as in
-// masked_col_stats_kernel): no cancellation of E[x^2] - E[x]^2 when |mean| >> std.
-__device__ __forceinline__ int64_t prep_snapshot_offset(int P, int C) { return int64_t(P) * 2 * C * 2; }
-
-// row 0's value of channel c of the agent rows and of the expert rows
-__device__ __forceinline__ void prep_pivots(const float *__restrict__ state, const float *__restrict__ next_state,
-                                            const int32_t *__restrict__ columns, int K, const float *__restrict__ agent_raw,
-                                            const float *__restrict__ dataset, const int64_t *__restrict__ indices,
-                                            const float *__restrict__ expert_raw, int C, int c, double &pa, double &pe) {
-    const int k = c < K ? c : c - K;
-    pa = double(agent_raw ? agent_raw[c] : (c < K ? state : next_state)[columns ? columns[k] : k]);
-    pe = double(expert_raw ? expert_raw[c] : dataset[indices[0] * C + c]);
-}
-
-__global__ __launch_bounds__(kBlock) void amp_assemble_kernel(
-    const float *__restrict__ state, const float *__restrict__ next_state, int state_pitch,
-    const int32_t *__restrict__ columns, int K, const float *__restrict__ agent_raw, const float *__restrict__ dataset,
-    const int64_t *__restrict__ indices, const float *__restrict__ expert_raw, int E, int C,
-    const float *__restrict__ mean, const float *__restrict__ var, const double *__restrict__ count,
-    float *__restrict__ agent_out, float *__restrict__ expert_out, double *__restrict__ work) {
-    __shared__ double red[kBlock][4];
-    const int threads = int(gridDim.x) * kBlock;
-    const int stride = threads / C * C;  // a lane stays on one channel (threads >= kBlock > C)
-    const int tid = int(blockIdx.x) * kBlock + threadIdx.x;
-    double sa = 0.0, qa = 0.0, se = 0.0, qe = 0.0;
-    if (tid < stride) {
-        const int c = tid % C;
-        const int k = c < K ? c : c - K;
-        const int col = agent_raw ? 0 : (columns ? columns[k] : k);
-        const float *__restrict__ side = c < K ? state : next_state;
-        double pa, pe;
-        prep_pivots(state, next_state, columns, K, agent_raw, dataset, indices, expert_raw, C, c, pa, pe);
-        // rounds of kPrepItems elements: every index, then every row element is requested before the first store (the
-        // launch is a chain of dependent memory round trips: index -> dataset row -> store); out-of-range items are clamped
-        for (int i0 = tid; i0 < E; i0 += stride * kPrepItems) {
-            int idx[kPrepItems], row[kPrepItems];
-            int64_t pick[kPrepItems];
-            float a[kPrepItems], e[kPrepItems];
-#pragma unroll
-            for (int j = 0; j < kPrepItems; ++j) {
-                idx[j] = min(i0 + j * stride, E - 1);
-                row[j] = idx[j] / C;  // 32-bit: E <= 2^20
-                if (!expert_raw) pick[j] = indices[row[j]];
-            }
-#pragma unroll
-            for (int j = 0; j < kPrepItems; ++j) {
-                // torch.cat([state[..., idx], next_state[..., idx]], -1)  amp.py:116-120;  dataset[randint]  amp.py:160-163
-                const int i = row[j] * C + c;  // the clamped item re-reads this lane's channel of the last row
-                a[j] = agent_raw ? agent_raw[i] : side[int64_t(row[j]) * state_pitch + col];
-                e[j] = expert_raw ? expert_raw[i] : dataset[pick[j] * C + c];
-            }
-#pragma unroll
-            for (int j = 0; j < kPrepItems; ++j) {
-                const int i = i0 + j * stride;
-                if (i < E) {
-                    agent_out[i] = a[j];
-                    expert_out[i] = e[j];
-                    const double da = double(a[j]) - pa, de = double(e[j]) - pe;
-                    sa += da, qa += da * da;
-                    se += de, qe += de * de;
-                }
-            }
-        }
-    }
-    red[threadIdx.x][0] = sa, red[threadIdx.x][1] = qa, red[threadIdx.x][2] = se, red[threadIdx.x][3] = qe;
-    __syncthreads();
-    // channel c of this block = lanes whose global id is congruent to c mod C
-    if (int(threadIdx.x) < C) {
-        const int base = int(blockIdx.x) * kBlock;
-        const int first = (int(threadIdx.x) - base % C + C) % C;
-        double t[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int l = first; l < kBlock; l += C)
-            for (int j = 0; j < 4; ++j) t[j] += red[l][j];
-        double *out = work + (int64_t(blockIdx.x) * 2 * C + threadIdx.x) * 2;
-        out[0] = t[0], out[1] = t[1];
-        out[int64_t(C) * 2] = t[2], out[int64_t(C) * 2 + 1] = t[3];
-    }
-    if (blockIdx.x == 0) {  // the statistics every block of launch B merges into (nothing in THIS launch writes them)
-        double *snap = work + prep_snapshot_offset(int(gridDim.x), C);
-        for (int c = threadIdx.x; c < C; c += kBlock) {
-            snap[c] = double(mean[c]), snap[C + c] = double(var[c]);
-            prep_pivots(state, next_state, columns, K, agent_raw, dataset, indices, expert_raw, C, c, snap[2 * C + 1 + c],
-                        snap[3 * C + 1 + c]);
-        }
-        if (threadIdx.x == 0) snap[2 * C] = *count;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void amp_normalize_kernel(const double *__restrict__ work, int P, int E, int C, int rows,
-                                                               float eps, double max_count, float clamp,
-                                                               float *__restrict__ mean, float *__restrict__ var,
-                                                               float *__restrict__ std, double *__restrict__ count,
-                                                               float *__restrict__ agent_out, float *__restrict__ expert_out) {
-    __shared__ float s_mean[kPrepMaxC], s_std[kPrepMaxC];
-    __shared__ double fold[kBlock][4];
-    {
-        // partial rows spread over the block: lane (group, c) folds rows group, group + G, ...; then one lane per channel
-        // folds the G groups — both in fixed order
-        const int groups = kBlock / C, c = threadIdx.x % C, group = threadIdx.x / C;
-        double t[4] = {0.0, 0.0, 0.0, 0.0};
-        if (group < groups)
-            for (int p = group; p < P; p += groups) {
-                const double *row = work + (int64_t(p) * 2 * C + c) * 2;
-                t[0] += row[0], t[1] += row[1];
-                t[2] += row[int64_t(C) * 2], t[3] += row[int64_t(C) * 2 + 1];
-            }
-        for (int j = 0; j < 4; ++j) fold[threadIdx.x][j] = t[j];
-    }
-    __syncthreads();
-    if (int(threadIdx.x) < C) {
-        const int c = threadIdx.x, groups = kBlock / C;
-        const double *snap = work + prep_snapshot_offset(P, C);
-        float m = float(snap[c]), v = float(snap[C + c]);
-        double running = snap[2 * C];
-        // transition_rms.update(agent); transition_rms.update(expert)   amp.py:122-124 — the arithmetic of
-        // masked_stats_finalize_kernel + rms_merge_kernel (population variance; Chan merge, weights count : rows, fp32)
-        for (int which = 0; which < 2; ++which) {
-            double s = 0.0, q = 0.0;
-            for (int g = 0; g < groups; ++g) s += fold[g * C + c][2 * which], q += fold[g * C + c][2 * which + 1];
-            const double n = double(rows), d = s / n, bm = snap[2 * C + 1 + which * C + c] + d;
-            double bv = q / n - d * d;
-            if (bv < 0.0) bv = 0.0;
-            const float batch_mean = float(bm), batch_var = float(bv);
-            const double w_sum = running + n;
-            const float w_new = float(n / w_sum), w_cross = float((running / w_sum) * (n / w_sum));
-            const float delta = batch_mean - m;
-            const float nm = m + delta * w_new;
-            const float nv = v + ((batch_var - v) * w_new + (delta * delta) * w_cross);
-            m = nm, v = nv;
-            running = w_sum;
-            if (max_count > 0.0 && running > max_count) running = max_count;
-        }
-        const float sd = sqrtf(v + eps);
-        s_mean[c] = m, s_std[c] = sd;
-        if (blockIdx.x == 0) {
-            mean[c] = m, var[c] = v, std[c] = sd;
-            if (c == 0) *count = running;
-        }
-    }
-    __syncthreads();
-    // normalise both with the statistics after BOTH updates   amp.py:125-128, rms.py:198-203
-    const int threads = int(gridDim.x) * kBlock;
-    const int stride = threads / C * C;
-    const int tid = int(blockIdx.x) * kBlock + threadIdx.x;
-    if (tid < stride) {
-        const float m = s_mean[tid % C], sd = s_std[tid % C];
-        for (int i = tid; i < E; i += stride) {
-            float a = (agent_out[i] - m) / sd, e = (expert_out[i] - m) / sd;
-            if (clamp > 0.0f) a = fminf(fmaxf(a, -clamp), clamp), e = fminf(fmaxf(e, -clamp), clamp);
-            agent_out[i] = a;
-            expert_out[i] = e;
-        }
-    }
 }
 
 // --------------------------------------------------------------------------------------------- AMP style reward + its mean
@@ -544,12 +372,6 @@ extern "C" int cusrl_reward_shaping(float *reward, float scale, float shift, flo
     return launch_status();
 }
 
-static uint32_t float_bits(float value) {
-    uint32_t bits;
-    memcpy(&bits, &value, sizeof bits);
-    return bits;
-}
-
 extern "C" int cusrl_nan_to_num2(float *a, int64_t na, float *b, int64_t nb, float nan, float posinf, float neginf,
                                  void *stream) {
     if (na < 0 || nb < 0) return CUSRL_E_INVALID;
@@ -566,43 +388,10 @@ extern "C" int cusrl_nan_to_num2(float *a, int64_t na, float *b, int64_t nb, flo
     uint32_t *wa = reinterpret_cast<uint32_t *>(a), *wb = reinterpret_cast<uint32_t *>(nb > 0 ? b : nullptr);
     if (streaming)
         hipLaunchKernelGGL(nan_to_num2_kernel<true>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), wa, na, wb, nb,
-                           float_bits(nan), float_bits(posinf), float_bits(neginf));
+                           float_as_word(nan), float_as_word(posinf), float_as_word(neginf));
     else
         hipLaunchKernelGGL(nan_to_num2_kernel<false>, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), wa, na, wb, nb,
-                           float_bits(nan), float_bits(posinf), float_bits(neginf));
-    return launch_status();
-}
-
-extern "C" int64_t cusrl_amp_prepare_max_elements(void) { return int64_t(1) << 20; }
-
-static int prep_blocks(int64_t elements) {
-    const int64_t want = ceil_div(elements, int64_t(kBlock) * kPrepItems);
-    return int(want < 1 ? 1 : (want > kPrepMaxBlocks ? kPrepMaxBlocks : want));
-}
-
-extern "C" int64_t cusrl_amp_prepare_workspace(int64_t N, int64_t C) {
-    if (N <= 0 || C <= 0) return 0;
-    return int64_t(prep_blocks(N * C)) * 2 * C * 2 + 4 * C + 1;  // doubles
-}
-
-extern "C" int cusrl_amp_prepare(const float *state, const float *next_state, int64_t state_pitch, const int32_t *columns,
-                                 int64_t K, const float *agent_raw, const float *dataset, const int64_t *indices,
-                                 const float *expert_raw, int64_t N, int64_t C, float *mean, float *var, float *std,
-                                 double *count, float eps, double max_count, float clamp, float *agent_out,
-                                 float *expert_out, double *workspace, void *stream) {
-    if (N <= 0 || C <= 0) return CUSRL_E_INVALID;
-    if (!mean || !var || !std || !count || !agent_out || !expert_out || !workspace) return CUSRL_E_INVALID;
-    if (!agent_raw && (!state || !next_state || 2 * K != C || state_pitch < K || state_pitch > INT32_MAX)) return CUSRL_E_INVALID;
-    if (!expert_raw && (!dataset || !indices)) return CUSRL_E_INVALID;
-    if (C > kPrepMaxC || N * C > cusrl_amp_prepare_max_elements()) return CUSRL_E_UNSUPPORTED;
-    const int P = prep_blocks(N * C);
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(amp_assemble_kernel, dim3(P), dim3(kBlock), 0, s, state, next_state, int(state_pitch), columns, int(K),
-                       agent_raw, dataset, indices, expert_raw, int(N * C), int(C), mean, var, count, agent_out, expert_out,
-                       workspace);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL(amp_normalize_kernel, dim3(P), dim3(kBlock), 0, s, workspace, P, int(N * C), int(C), int(N), eps,
-                       max_count, clamp, mean, var, std, count, agent_out, expert_out);
+                           float_as_word(nan), float_as_word(posinf), float_as_word(neginf));
     return launch_status();
 }
 

@@ -7,6 +7,7 @@
 // aligned, one element otherwise.  Each lane loads its operands before it stores, so `out` may be `x` and `dx` may be `dy`
 // (which is why those two carry no __restrict__).
 #include "common.hpp"
+#include "running_stats.hpp"
 
 namespace cusrl {
 namespace {
@@ -17,7 +18,7 @@ constexpr int kAffineMaxBlocks = 2048;  // 8 blocks per CU; the grid strides ove
 
 template <int kOp>
 __device__ __forceinline__ float affine(float v, float m, float s) {
-    if (kOp == kNormalize) return (v - m) / s;
+    if (kOp == kNormalize) return normalized(v, m, s);
     if (kOp == kDenormalize) return v * s + m;  // (two roundings: -ffp-contract=off)
     if (kOp == kDivide) return v / s;
     return v * s;

@@ -39,6 +39,16 @@ inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintp
 
 __device__ __forceinline__ bool aligned_ptr16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// tensor.nan_to_num of one fp32 word, classified on the bit pattern: exponent all ones and a mantissa -> `nan` (any sign, any
+// payload), +Inf -> `posinf`, -Inf -> `neginf`; every other pattern (-0.0, denormals, +-FLT_MAX) comes back as it is, so no
+// floating-point mode can touch it.  The sanitiser's (aux_hooks.hip) and the deploy prologue's (deploy.hip) one classification.
+__host__ __device__ __forceinline__ uint32_t float_as_word(float value) { return __builtin_bit_cast(uint32_t, value); }
+__host__ __device__ __forceinline__ float word_as_float(uint32_t bits) { return __builtin_bit_cast(float, bits); }
+__host__ __device__ __forceinline__ uint32_t nan_to_num_word(uint32_t bits, uint32_t nan, uint32_t posinf, uint32_t neginf) {
+    if ((bits & 0x7f800000u) != 0x7f800000u) return bits;  // finite
+    return (bits & 0x007fffffu) ? nan : ((bits >> 31) ? neginf : posinf);
+}
+
 // ---- 16-byte accesses with the non-temporal hint (streams nobody reads again soon); clang's builtins take native vectors ----
 typedef float native_float4 __attribute__((ext_vector_type(4)));
 

@@ -1,16 +1,15 @@
 // The two elementwise ends of a deployed policy's step (cusrl_amd/nn/deployed.py; DESIGN.md, "Deployment"; contracts:
 // include/cusrl_hip.h).  A deployed policy at batch 1 .. 4096 is launch latency, so what stands in front of the first GEMM is
 // ONE launch and what stands behind the last one is ONE launch:
-//   prologue   x = clamp((nan_to_num(obs) - mean) / std, -c, c)       the sanitiser's bit classification (csrc/aux_hooks.hip)
-//                                                                     and the normaliser's arithmetic (csrc/normalization.hip),
+//   prologue   x = clamp((nan_to_num(obs) - mean) / std, -c, c)       the sanitiser's bit classification (csrc/common.hpp)
+//                                                                     and the normaliser's element (csrc/running_stats.hpp),
 //                                                                     in their order, each an optional part
 //   epilogue   a = clip((y + bias) * scale + shift, lo, hi), in place  + the memory rows of finished envs zeroed
 // Every step is one rounded fp32 operation (the library is built with -ffp-contract=off), the division is the correctly
 // rounded one, so a 16-byte lane and a scalar lane give the same bits and the host restatements (`*_cpu`, below) give them too.
 // A lane loads its operands before it stores, so the prologue's out may be obs itself.  Plain vector stores only.
 #include "common.hpp"
-
-#include <string.h>
+#include "running_stats.hpp"
 
 namespace cusrl {
 namespace {
@@ -22,31 +21,11 @@ struct Replace {
     int on;
 };
 
-// tensor.nan_to_num on the bit pattern: exponent all ones and a mantissa -> nan (any sign, any payload), +Inf -> posinf,
-// -Inf -> neginf; every other pattern passes untouched (sanitize_word of csrc/aux_hooks.hip)
-__host__ __device__ __forceinline__ uint32_t replace_word(uint32_t bits, const Replace &r) {
-    if ((bits & 0x7f800000u) != 0x7f800000u) return bits;
-    return (bits & 0x007fffffu) ? r.nan : ((bits >> 31) ? r.neginf : r.posinf);
-}
-
-__host__ __device__ __forceinline__ float word_as_float(uint32_t bits) {
-    float value;
-    memcpy(&value, &bits, sizeof value);
-    return value;
-}
-
-__host__ __device__ __forceinline__ uint32_t float_as_word(float value) {
-    uint32_t bits;
-    memcpy(&bits, &value, sizeof bits);
-    return bits;
-}
-
-// one element of the prologue: rms_normalize_kernel's expression behind the sanitiser's classification
+// one element of the prologue: the sanitiser's word, then normalize_clamp — its division behind the prologue's own switch
 __host__ __device__ __forceinline__ float prologue_apply(float v, float m, float s, const Replace &r, int normalize, float clamp) {
-    if (r.on) v = word_as_float(replace_word(float_as_word(v), r));
-    if (normalize) v = (v - m) / s;
-    if (clamp > 0.0f) v = fminf(fmaxf(v, -clamp), clamp);
-    return v;
+    if (r.on) v = word_as_float(nan_to_num_word(float_as_word(v), r.nan, r.posinf, r.neginf));
+    if (normalize) v = normalized(v, m, s);
+    return symmetric_clamp(v, clamp);
 }
 
 // kWidth 4: K % 4 == 0, the 4 elements of a lane are 4 adjacent channels of one row; kWidth 1: one element per lane

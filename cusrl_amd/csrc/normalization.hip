@@ -1,15 +1,25 @@
 // Running observation statistics for gfx950: masked column mean / variance of one env step,
 // Chan merge into the running statistics, and the normalise-and-clamp pass — three launches, no host round trip
-// (the reference: ~15 torch launches and a boolean-mask select that synchronises, twice per env step).
+// (the reference: ~15 torch launches and a boolean-mask select that synchronises, twice per env step).  Over the same pivots,
+// partial rows and merge, AMP's transition preparation for C <= 128 (amp.py:112-128): cusrl_amp_prepare, TWO
+// launches instead of cat + index + 2 x (stats, finalize, merge) + 2 x normalise.
+//
+// One body per computation — what several kernels must agree on bit for bit is a function they all call (running_stats.hpp):
+//   shifted_mean_var  float64 shifted sums -> mean, population variance  masked_stats_finalize_kernel, amp_normalize_kernel, merge_and_scale
+//   chan_merge<T>     a batch into the running mean / variance           rms_merge_kernel, amp_normalize_kernel (float), merge_and_scale (double)
+//   capped_count      the max_count cap of the running count             rms_merge_kernel, amp_normalize_kernel
+//   normalize_clamp   (x - mean) / std, then +-clamp                     rms_normalize_kernel, amp_normalize_kernel, prologue_apply, affine
+// (merge_and_scale: reward_norm.hip; prologue_apply: deploy.hip, its own switch around the division; affine: column_affine.hip, the
+// division alone.)  The SUMMATION ORDERS are not shared: each kernel's folds decide the last bits of its float64 sums.
 #include "common.hpp"
+#include "running_stats.hpp"
 
 namespace cusrl {
 
 constexpr int kRmsMaxBlocks = 256;
 
 // partials[block][c][{sum, sumsq}] for c < C, partials[block][C][0] = number of selected rows in this block's rows.
-// The sums are of x - x[0][c] (row 0's value of the channel, selected or not, the pivot every block reads): shifted sums
-// keep q / n - (s / n)^2 free of the cancellation of E[x^2] - E[x]^2 when |mean| >> std, and a constant channel exact.
+// The sums are of x - x[0][c] (row 0's value of the channel, selected or not, the pivot every block reads: shifted_mean_var).
 // C < kBlock: lanes keep one channel each (below); C >= kBlock: masked_col_stats_wide_kernel.
 __global__ __launch_bounds__(kBlock) void masked_col_stats_kernel(const float *__restrict__ x,
                                                                   const uint8_t *__restrict__ mask, int64_t rows, int C,
@@ -142,10 +152,9 @@ __global__ __launch_bounds__(kBlock) void masked_stats_finalize_kernel(const dou
                 n += folded[g * columns + width][0];
             }
             if (n > 0.0) {
-                const double d = s / n;  // mean - pivot
-                const double v = q / n - d * d;  // population variance (correction = 0)
-                mean[c] = float(double(x[c]) + d);
-                var[c] = float(v < 0.0 ? 0.0 : v);
+                const MeanVar batch = shifted_mean_var(s, q, n, double(x[c]));
+                mean[c] = float(batch.mean);
+                var[c] = float(batch.var);
             } else {
                 mean[c] = 0.0f;
                 var[c] = 1.0f;
@@ -164,22 +173,11 @@ __global__ __launch_bounds__(kBlock) void rms_merge_kernel(float *__restrict__ m
     const double w_old_count = *count, w_new_count = *batch_count;
     __syncthreads();  // every lane has read the counts before lane 0 updates them
     if (w_new_count <= 0.0) return;
-    const double w_sum = w_old_count + w_new_count;
-    const float w_new = float(w_new_count / w_sum);
-    const float w_cross = float((w_old_count / w_sum) * (w_new_count / w_sum));
     for (int c = threadIdx.x; c < C; c += kBlock) {
-        const float delta = batch_mean[c] - mean[c];
-        const float m = mean[c] + delta * w_new;
-        const float v = var[c] + ((batch_var[c] - var[c]) * w_new + (delta * delta) * w_cross);
-        mean[c] = m;
-        var[c] = v;
-        std[c] = sqrtf(v + eps);
+        chan_merge(mean[c], var[c], w_old_count, batch_mean[c], batch_var[c], w_new_count);
+        std[c] = sqrtf(var[c] + eps);
     }
-    if (threadIdx.x == 0) {
-        double total = w_sum;
-        if (max_count > 0.0 && total > max_count) total = max_count;
-        *count = total;
-    }
+    if (threadIdx.x == 0) *count = capped_count(w_old_count + w_new_count, max_count);
 }
 
 __global__ __launch_bounds__(kBlock) void rms_normalize_kernel(const float *__restrict__ x, const float *__restrict__ mean,
@@ -194,19 +192,169 @@ __global__ __launch_bounds__(kBlock) void rms_normalize_kernel(const float *__re
             const float4 v = reinterpret_cast<const float4 *>(x)[i];
             const float4 m = *reinterpret_cast<const float4 *>(mean + c);
             const float4 s = *reinterpret_cast<const float4 *>(std + c);
-            float r[4] = {(v.x - m.x) / s.x, (v.y - m.y) / s.y, (v.z - m.z) / s.z, (v.w - m.w) / s.w};
-            if (clamp > 0.0f) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) r[j] = fminf(fmaxf(r[j], -clamp), clamp);
-            }
-            reinterpret_cast<float4 *>(out)[i] = make_float4(r[0], r[1], r[2], r[3]);
+            reinterpret_cast<float4 *>(out)[i] =
+                make_float4(normalize_clamp(v.x, m.x, s.x, clamp), normalize_clamp(v.y, m.y, s.y, clamp),
+                            normalize_clamp(v.z, m.z, s.z, clamp), normalize_clamp(v.w, m.w, s.w, clamp));
         }
     } else {
         for (int64_t i = tid; i < E; i += stride) {
             const int c = int(i % C);
-            float r = (x[i] - mean[c]) / std[c];
-            if (clamp > 0.0f) r = fminf(fmaxf(r, -clamp), clamp);
-            out[i] = r;
+            out[i] = normalize_clamp(x[i], mean[c], std[c], clamp);
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------------------- AMP transition preparation
+// Two launches: (A) every block assembles its slice of the agent rows and fetches its slice of the expert rows (raw, into the
+// output buffers) and leaves fp64 {sum, sumsq} per channel of both; block 0 also snapshots the running statistics.
+// (B) every block folds the <= 64 partial rows itself (L2-resident, fixed order), replays the two Chan merges from the
+// snapshot — so no block depends on another block's result — normalises its slice in place; block 0 publishes the new
+// running statistics.  (A single-workgroup form of the whole step measured 118 us: one CU's latency chain.)
+constexpr int kPrepMaxC = 128;
+constexpr int kPrepMaxBlocks = 64;
+constexpr int kPrepItems = 8;  // elements per thread and tensor
+
+// workspace layout (doubles): [P][2 tensors][C][2] partial sums, then the snapshot: mean[C], var[C], count, then the
+// pivots: agent[C], expert[C].  The sums are of x - pivot (row 0's agent / expert value of the channel, as in masked_col_stats_kernel).
+__device__ __forceinline__ int64_t prep_snapshot_offset(int P, int C) { return int64_t(P) * 2 * C * 2; }
+
+// row 0's value of channel c of the agent rows and of the expert rows
+__device__ __forceinline__ void prep_pivots(const float *__restrict__ state, const float *__restrict__ next_state,
+                                            const int32_t *__restrict__ columns, int K, const float *__restrict__ agent_raw,
+                                            const float *__restrict__ dataset, const int64_t *__restrict__ indices,
+                                            const float *__restrict__ expert_raw, int C, int c, double &pa, double &pe) {
+    const int k = c < K ? c : c - K;
+    pa = double(agent_raw ? agent_raw[c] : (c < K ? state : next_state)[columns ? columns[k] : k]);
+    pe = double(expert_raw ? expert_raw[c] : dataset[indices[0] * C + c]);
+}
+
+__global__ __launch_bounds__(kBlock) void amp_assemble_kernel(
+    const float *__restrict__ state, const float *__restrict__ next_state, int state_pitch,
+    const int32_t *__restrict__ columns, int K, const float *__restrict__ agent_raw, const float *__restrict__ dataset,
+    const int64_t *__restrict__ indices, const float *__restrict__ expert_raw, int E, int C,
+    const float *__restrict__ mean, const float *__restrict__ var, const double *__restrict__ count,
+    float *__restrict__ agent_out, float *__restrict__ expert_out, double *__restrict__ work) {
+    __shared__ double red[kBlock][4];
+    const int threads = int(gridDim.x) * kBlock;
+    const int stride = threads / C * C;  // a lane stays on one channel (threads >= kBlock > C)
+    const int tid = int(blockIdx.x) * kBlock + threadIdx.x;
+    double sa = 0.0, qa = 0.0, se = 0.0, qe = 0.0;
+    if (tid < stride) {
+        const int c = tid % C;
+        const int k = c < K ? c : c - K;
+        const int col = agent_raw ? 0 : (columns ? columns[k] : k);
+        const float *__restrict__ side = c < K ? state : next_state;
+        double pa, pe;
+        prep_pivots(state, next_state, columns, K, agent_raw, dataset, indices, expert_raw, C, c, pa, pe);
+        // rounds of kPrepItems elements: every index, then every row element is requested before the first store (the
+        // launch is a chain of dependent memory round trips: index -> dataset row -> store); out-of-range items are clamped
+        for (int i0 = tid; i0 < E; i0 += stride * kPrepItems) {
+            int idx[kPrepItems], row[kPrepItems];
+            int64_t pick[kPrepItems];
+            float a[kPrepItems], e[kPrepItems];
+#pragma unroll
+            for (int j = 0; j < kPrepItems; ++j) {
+                idx[j] = min(i0 + j * stride, E - 1);
+                row[j] = idx[j] / C;  // 32-bit: E <= 2^20
+                if (!expert_raw) pick[j] = indices[row[j]];
+            }
+#pragma unroll
+            for (int j = 0; j < kPrepItems; ++j) {
+                // torch.cat([state[..., idx], next_state[..., idx]], -1)  amp.py:116-120;  dataset[randint]  amp.py:160-163
+                const int i = row[j] * C + c;  // the clamped item re-reads this lane's channel of the last row
+                a[j] = agent_raw ? agent_raw[i] : side[int64_t(row[j]) * state_pitch + col];
+                e[j] = expert_raw ? expert_raw[i] : dataset[pick[j] * C + c];
+            }
+#pragma unroll
+            for (int j = 0; j < kPrepItems; ++j) {
+                const int i = i0 + j * stride;
+                if (i < E) {
+                    agent_out[i] = a[j];
+                    expert_out[i] = e[j];
+                    const double da = double(a[j]) - pa, de = double(e[j]) - pe;
+                    sa += da, qa += da * da;
+                    se += de, qe += de * de;
+                }
+            }
+        }
+    }
+    red[threadIdx.x][0] = sa, red[threadIdx.x][1] = qa, red[threadIdx.x][2] = se, red[threadIdx.x][3] = qe;
+    __syncthreads();
+    // channel c of this block = lanes whose global id is congruent to c mod C
+    if (int(threadIdx.x) < C) {
+        const int base = int(blockIdx.x) * kBlock;
+        const int first = (int(threadIdx.x) - base % C + C) % C;
+        double t[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int l = first; l < kBlock; l += C)
+            for (int j = 0; j < 4; ++j) t[j] += red[l][j];
+        double *out = work + (int64_t(blockIdx.x) * 2 * C + threadIdx.x) * 2;
+        out[0] = t[0], out[1] = t[1];
+        out[int64_t(C) * 2] = t[2], out[int64_t(C) * 2 + 1] = t[3];
+    }
+    if (blockIdx.x == 0) {  // the statistics every block of launch B merges into (nothing in THIS launch writes them)
+        double *snap = work + prep_snapshot_offset(int(gridDim.x), C);
+        for (int c = threadIdx.x; c < C; c += kBlock) {
+            snap[c] = double(mean[c]), snap[C + c] = double(var[c]);
+            prep_pivots(state, next_state, columns, K, agent_raw, dataset, indices, expert_raw, C, c, snap[2 * C + 1 + c],
+                        snap[3 * C + 1 + c]);
+        }
+        if (threadIdx.x == 0) snap[2 * C] = *count;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void amp_normalize_kernel(const double *__restrict__ work, int P, int E, int C, int rows,
+                                                               float eps, double max_count, float clamp,
+                                                               float *__restrict__ mean, float *__restrict__ var,
+                                                               float *__restrict__ std, double *__restrict__ count,
+                                                               float *__restrict__ agent_out, float *__restrict__ expert_out) {
+    __shared__ float s_mean[kPrepMaxC], s_std[kPrepMaxC];
+    __shared__ double fold[kBlock][4];
+    {
+        // partial rows spread over the block: lane (group, c) folds rows group, group + G, ...; then one lane per channel
+        // folds the G groups — both in fixed order
+        const int groups = kBlock / C, c = threadIdx.x % C, group = threadIdx.x / C;
+        double t[4] = {0.0, 0.0, 0.0, 0.0};
+        if (group < groups)
+            for (int p = group; p < P; p += groups) {
+                const double *row = work + (int64_t(p) * 2 * C + c) * 2;
+                t[0] += row[0], t[1] += row[1];
+                t[2] += row[int64_t(C) * 2], t[3] += row[int64_t(C) * 2 + 1];
+            }
+        for (int j = 0; j < 4; ++j) fold[threadIdx.x][j] = t[j];
+    }
+    __syncthreads();
+    if (int(threadIdx.x) < C) {
+        const int c = threadIdx.x, groups = kBlock / C;
+        const double *snap = work + prep_snapshot_offset(P, C);
+        float m = float(snap[c]), v = float(snap[C + c]);
+        double running = snap[2 * C];
+        // transition_rms.update(agent); transition_rms.update(expert)   amp.py:122-124 — what masked_stats_finalize_kernel and
+        // rms_merge_kernel do per update (population variance; Chan merge, weights count : rows, fp32)
+        for (int which = 0; which < 2; ++which) {
+            double s = 0.0, q = 0.0;
+            for (int g = 0; g < groups; ++g) s += fold[g * C + c][2 * which], q += fold[g * C + c][2 * which + 1];
+            const double n = double(rows);
+            const MeanVar batch = shifted_mean_var(s, q, n, snap[2 * C + 1 + which * C + c]);
+            running = capped_count(chan_merge(m, v, running, float(batch.mean), float(batch.var), n), max_count);
+        }
+        const float sd = sqrtf(v + eps);
+        s_mean[c] = m, s_std[c] = sd;
+        if (blockIdx.x == 0) {
+            mean[c] = m, var[c] = v, std[c] = sd;
+            if (c == 0) *count = running;
+        }
+    }
+    __syncthreads();
+    // normalise both with the statistics after BOTH updates   amp.py:125-128, rms.py:198-203
+    const int threads = int(gridDim.x) * kBlock;
+    const int stride = threads / C * C;
+    const int tid = int(blockIdx.x) * kBlock + threadIdx.x;
+    if (tid < stride) {
+        const float m = s_mean[tid % C], sd = s_std[tid % C];
+        for (int i = tid; i < E; i += stride) {
+            const float a = normalize_clamp(agent_out[i], m, sd, clamp), e = normalize_clamp(expert_out[i], m, sd, clamp);
+            agent_out[i] = a;
+            expert_out[i] = e;
         }
     }
 }
@@ -264,5 +412,38 @@ extern "C" int cusrl_rms_normalize(const float *x, const float *mean, const floa
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(rms_normalize_kernel, dim3(uint32_t(blocks)), dim3(kBlock), 0, as_stream(stream), x, mean, std,
                        clamp, out, E, int(C), vec4);
+    return launch_status();
+}
+
+extern "C" int64_t cusrl_amp_prepare_max_elements(void) { return int64_t(1) << 20; }
+
+static int prep_blocks(int64_t elements) {
+    const int64_t want = ceil_div(elements, int64_t(kBlock) * kPrepItems);
+    return int(want < 1 ? 1 : (want > kPrepMaxBlocks ? kPrepMaxBlocks : want));
+}
+
+extern "C" int64_t cusrl_amp_prepare_workspace(int64_t N, int64_t C) {
+    if (N <= 0 || C <= 0) return 0;
+    return int64_t(prep_blocks(N * C)) * 2 * C * 2 + 4 * C + 1;  // doubles
+}
+
+extern "C" int cusrl_amp_prepare(const float *state, const float *next_state, int64_t state_pitch, const int32_t *columns,
+                                 int64_t K, const float *agent_raw, const float *dataset, const int64_t *indices,
+                                 const float *expert_raw, int64_t N, int64_t C, float *mean, float *var, float *std,
+                                 double *count, float eps, double max_count, float clamp, float *agent_out,
+                                 float *expert_out, double *workspace, void *stream) {
+    if (N <= 0 || C <= 0) return CUSRL_E_INVALID;
+    if (!mean || !var || !std || !count || !agent_out || !expert_out || !workspace) return CUSRL_E_INVALID;
+    if (!agent_raw && (!state || !next_state || 2 * K != C || state_pitch < K || state_pitch > INT32_MAX)) return CUSRL_E_INVALID;
+    if (!expert_raw && (!dataset || !indices)) return CUSRL_E_INVALID;
+    if (C > kPrepMaxC || N * C > cusrl_amp_prepare_max_elements()) return CUSRL_E_UNSUPPORTED;
+    const int P = prep_blocks(N * C);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(amp_assemble_kernel, dim3(P), dim3(kBlock), 0, s, state, next_state, int(state_pitch), columns, int(K),
+                       agent_raw, dataset, indices, expert_raw, int(N * C), int(C), mean, var, count, agent_out, expert_out,
+                       workspace);
+    if (int rc = launch_status()) return rc;
+    hipLaunchKernelGGL(amp_normalize_kernel, dim3(P), dim3(kBlock), 0, s, workspace, P, int(N * C), int(C), int(N), eps,
+                       max_count, clamp, mean, var, std, count, agent_out, expert_out);
     return launch_status();
 }

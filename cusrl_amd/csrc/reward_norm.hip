@@ -13,6 +13,7 @@
 // __host__ __device__; cusrl_reward_normalize_cpu runs them on the host and adds in the kernel's tree order, so the two differ only
 // where the device's float64 division and square root would.  Plain vector stores only.  No loop's trip count depends on data.
 #include "common.hpp"
+#include "running_stats.hpp"
 
 #include <math.h>
 
@@ -43,24 +44,16 @@ __host__ __device__ __forceinline__ float scaled_reward(float r, float scale, fl
 }
 
 // Column c's sums into its running triple (stats points at mean[c]; var and count are R and 2 R further on), then the scale of
-// the column's rewards.  update == 0: the triple is only read.
+// the column's rewards: RunningMeanStd's two bodies (running_stats.hpp), the merge in float64.  update == 0: the triple is only read.
 __host__ __device__ __forceinline__ float merge_and_scale(double *stats, int64_t R, Moments m, int64_t N, float pivot, double epsilon,
                                                           int update) {
     double mean = stats[0], var = stats[R];
     if (update) {
-        const double count = stats[2 * R], n = double(N);
-        const double d = m.s / n;
-        const double batch_mean = double(pivot) + d;
-        double batch_var = m.q / n - d * d;
-        batch_var = batch_var < 0.0 ? 0.0 : batch_var;
-        const double w_sum = count + n;
-        const double w_new = n / w_sum, w_old = count / w_sum;
-        const double delta = batch_mean - mean;
-        mean = mean + delta * w_new;
-        var = var + ((batch_var - var) * w_new + (delta * delta) * (w_old * w_new));
+        const double n = double(N);
+        const MeanVar batch = shifted_mean_var(m.s, m.q, n, double(pivot));
+        stats[2 * R] = chan_merge(mean, var, stats[2 * R], batch.mean, batch.var, n);
         stats[0] = mean;
         stats[R] = var;
-        stats[2 * R] = w_sum;
     }
     return float(sqrt(var + epsilon));
 }

@@ -19,6 +19,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch  # noqa: E402
 
 from cusrl_amd import ops  # noqa: E402
+from cusrl_amd.nn.rms import RunningMeanStd  # noqa: E402
 
 PEAK = 8000.0
 DEV = "cuda:0"
@@ -316,6 +317,23 @@ def bench_size(N, T=24, obs=48, act=12, mbs=4, only=None, iters=None):
     flag1 = torch.zeros(N, 1, dtype=torch.bool, device=DEV)
     triple = torch.tensor([[0.0], [1.0], [1e-4]], dtype=torch.float64, device=DEV)
     rows.measure("reward normalize [N,1]", lambda: ops.reward_normalize_(r1, g1, flag1, flag1, triple, 0.99, 1e-8, 10.0), N * 22)
+
+    # ---- running statistics (ObservationNormalization's per-step chain, one launch set per row) and AMP's fused preparation of a
+    # [N, 2 * 6] transition.  Bytes: the statistics pass reads the observation once; the merge moves seven [obs] vectors; the
+    # normalise pass reads and writes the observation; the preparation reads and writes both [N, C] tensors in each of its two
+    # launches and reads one int64 index per row.
+    ob = f(N, obs)
+    rms = RunningMeanStd(obs).to(DEV)
+    batch_mean, batch_var, batch_count = ops.masked_col_stats(ob)
+    rows.measure(f"masked_col_stats [N,{obs}]", lambda: ops.masked_col_stats(ob), N * obs * 4)
+    rows.measure(f"rms_merge [{obs}]", lambda: ops.rms_merge_(rms.mean, rms.var, rms.std, rms._count, batch_mean, batch_var, batch_count,
+                                                             rms.epsilon, rms.max_count), obs * 28)
+    rows.measure(f"rms_normalize [N,{obs}]", lambda: ops.rms_normalize(ob, rms.mean, rms.std, rms.clamp), N * obs * 8)
+    amp_rms, next_ob = RunningMeanStd(12).to(DEV), f(N, obs)
+    dataset, picks = f(1000, 12), torch.randint(0, 1000, (N,), device=DEV)
+    if ops.amp_prepare_supported(N, 12):
+        rows.measure("amp_prepare [N,12]", lambda: ops.amp_prepare(amp_rms, state=ob, next_state=next_ob, width=6, dataset=dataset,
+                                                                   indices=picks), N * (2 * 16 * 12 + 8))
 
     # ---- reference points: a plain device copy of the same bytes (what the memory system gives a streaming kernel)
     big = torch.empty(max(S * 21 // 8, 1024), dtype=torch.float32, device=DEV)

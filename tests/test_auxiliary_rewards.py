@@ -249,6 +249,13 @@ def check_amp_prepare(rows, state_dim, columns, offset=0.0, spread=1.0, max_coun
         np.testing.assert_allclose(rms.var.cpu().numpy(), var, rtol=1e-5, atol=1e-6)
         np.testing.assert_allclose(rms.std.cpu().numpy(), std, rtol=1e-5, atol=1e-6)
         assert rms.count == count
+        # the fused kernels and the per-op kernel share one normalise element: given the published statistics, the raw rows
+        # through rms_normalize are the returned rows bit for bit
+        index = torch.from_numpy(picked).to(dev)
+        raw_agent = torch.cat((torch.from_numpy(state).to(dev)[:, index], torch.from_numpy(nxt).to(dev)[:, index]), dim=1)
+        raw_expert = torch.from_numpy(dataset).to(dev)[torch.from_numpy(picks).to(dev)]
+        assert torch.equal(ops.rms_normalize(raw_agent, rms.mean, rms.std, rms.clamp), agent)
+        assert torch.equal(ops.rms_normalize(raw_expert, rms.mean, rms.std, rms.clamp), expert)
 
 
 @pytest.mark.gpu
