@@ -29,15 +29,9 @@
 // Numerics: fp32 MFMA accumulation (the instruction the library's fp32 GEMMs use); the summation order differs from the
 // library's, results agree to a few ulp of the accumulated magnitude.  The sampling epilogue evaluates action and log-prob with
 // the expressions and the order of cusrl_normal_sample_logp (rollout.hip), so given the same mean it is bit-identical to it.
-#include "common.hpp"
+#include "mlp_tail.hpp"  // the accumulator type, relu4 and the tile's tail (wave-order sum, stores, sampling epilogue)
 
 namespace cusrl {
-
-typedef float mfma_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMlpWaves = 4;
-constexpr int kMlpThreads = kMlpWaves * kWave;
-constexpr int kMlpRows = 16;  // rows of one tile (the N dimension of the MFMA)
 
 struct MlpForwardArgs {
     const float *x;
@@ -49,14 +43,6 @@ struct MlpForwardArgs {
     int64_t rows;
     int K, A;
 };
-
-__device__ __forceinline__ float log_sqrt_2pi_f() { return 0.91893853320467274178f; }
-
-// relu as torch evaluates it: a NaN stays a NaN (v <= 0 is false for it), -0 becomes +0
-__device__ __forceinline__ mfma_f32x4 relu4(mfma_f32x4 v) {
-    v[0] = v[0] <= 0.f ? 0.f : v[0], v[1] = v[1] <= 0.f ? 0.f : v[1], v[2] = v[2] <= 0.f ? 0.f : v[2], v[3] = v[3] <= 0.f ? 0.f : v[3];
-    return v;
-}
 
 // T1 / T2: 16-feature tiles of the first / second hidden layer per wave (H1 = 64 T1, H2 = 64 T2); KB: 16-wide k-blocks of the
 // input (K <= 16 KB, K % 4 == 0).
@@ -120,18 +106,11 @@ __global__ __launch_bounds__(kMlpThreads) void mlp2_forward_kernel(const MlpForw
     // sampling epilogue (wave 0): this lane's four std values once, its four eps values requested at the top of every tile
     float sigma[4] = {1.f, 1.f, 1.f, 1.f}, noise[4] = {0.f, 0.f, 0.f, 0.f};
     const bool sampling = wave == 0 && p.eps != nullptr;
-    if (sampling) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) sigma[reg] = p.std[min(4 * kk + reg, A - 1)];
-    }
+    if (sampling) mlp_tail_sigma(p.std, A, kk, sigma);
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row0 = tile * kMlpRows;
-        if (sampling) {
-            const int64_t first = min(row0 + i, p.rows - 1) * A;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) noise[reg] = p.eps[first + min(4 * kk + reg, A - 1)];
-        }
+        if (sampling) mlp_tail_noise(p.eps, p.rows, A, row0, lane, noise);
         float4 xb[KB];
 #pragma unroll
         for (int t = 0; t < KB; ++t) xb[t] = 16 * t + 4 * kk < K ? ahead[t] : zero4;
@@ -178,57 +157,7 @@ __global__ __launch_bounds__(kMlpThreads) void mlp2_forward_kernel(const MlpForw
         }
         partial[wave][lane] = make_float4(head[0], head[1], head[2], head[3]);
         __syncthreads();
-        if (wave == 0) {
-            // out^T[a = 4 kk + reg][m = i]: waves added in wave order (fixed)
-            float4 sum = partial[0][lane];
-#pragma unroll
-            for (int w = 1; w < kMlpWaves; ++w) {
-                const float4 v = partial[w][lane];
-                sum.x += v.x, sum.y += v.y, sum.z += v.z, sum.w += v.w;
-            }
-            const bool live = row0 + i < p.rows;
-            const int a0 = 4 * kk;
-            const int64_t at = (row0 + i) * A + a0;
-            const float mu[4] = {sum.x, sum.y, sum.z, sum.w};
-            if (live && p.out) {
-                if (A % 4 == 0) {
-                    if (a0 < A) *reinterpret_cast<float4 *>(p.out + at) = sum;
-                } else {
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg)
-                        if (a0 + reg < A) p.out[at + reg] = mu[reg];
-                }
-            }
-            if (p.eps) {
-                // Normal.rsample + log_prob with the expressions of normal_sample_logp_kernel (rollout.hip): a lane evaluates its
-                // four actions, lane kk == 0 of a row adds the row's terms up in action order (its own, then the other three
-                // lanes' through shuffles): the association of the one-lane-per-row kernel
-                float term[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int a = a0 + reg;
-                    if (a < A) {
-                        const float sg = sigma[reg];
-                        const float act = mu[reg] + noise[reg] * sg;
-                        const float diff = act - mu[reg];
-                        term[reg] = -(diff * diff) / (2.0f * (sg * sg)) - logf(sg) - log_sqrt_2pi_f();
-                        if (live) {
-                            p.action[at + reg] = act;
-                            if (p.std_out) p.std_out[at + reg] = sg;
-                        }
-                    }
-                }
-                float lp = 0.f;
-#pragma unroll
-                for (int src = 0; src < 4; ++src)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const float t = __shfl(term[reg], i + 16 * src, kWave);
-                        if (4 * src + reg < A) lp += t;
-                    }
-                if (live && kk == 0) p.logp[row0 + i] = lp;
-            }
-        }
+        if (wave == 0) mlp_tail(p, partial, row0, lane, sigma, noise);
     }
 }
 

@@ -10,7 +10,7 @@ import torch
 from torch import Tensor, nn
 
 from cusrl_amd.nn.distribution import Distribution, NormalDist
-from cusrl_amd.nn.module import Linear, Module, ModuleFactory, fused_inference_layers
+from cusrl_amd.nn.module import Linear, Module, ModuleFactory, fused_inference_forward, fused_inference_layers
 
 __all__ = ["Actor", "Value"]
 
@@ -44,11 +44,11 @@ class Actor(Module):
         self.pending_noise: Tensor | None = None
         self.noise_shape: tuple[int, int] | None = None  # of the last fused explore pass (what an ahead-of-time draw must look like)
 
-    def _fused_layers(self, observation, memory, backbone_kwargs, distribution_kwargs):
+    def _fused_layers(self, observation, memory, backbone_kwargs, distribution_kwargs, three_layer: bool = False):
         if (not self.fused_inference or type(self.distribution) is not NormalDist or self.backbone_kwargs or self.distribution_kwargs
                 or distribution_kwargs or any(key != "sequential" for key in (backbone_kwargs or ()))):
             return None
-        return fused_inference_layers(self.backbone, self.distribution.mean_head, observation, memory)
+        return fused_inference_layers(self.backbone, self.distribution.mean_head, observation, memory, three_layer=three_layer)
 
     def clear_intermediate_repr(self):
         super().clear_intermediate_repr()
@@ -68,11 +68,9 @@ class Actor(Module):
         """``forward_type``: "forward" -> (dist_params, memory); "explore" -> (dist_params, (action, logp), memory);
         "act" / "act_deterministic" -> (action, memory)  (actor.py:69-92)."""
         if forward_type == "forward":
-            if (layers := self._fused_layers(observation, memory, backbone_kwargs, distribution_kwargs)) is not None:
-                from cusrl_amd import ops
-
+            if (layers := self._fused_layers(observation, memory, backbone_kwargs, distribution_kwargs, three_layer=True)) is not None:
                 self.intermediate_repr.pop("backbone.output", None)
-                mean = ops.mlp2_forward(observation, layers)
+                mean = fused_inference_forward(observation, layers)
                 return {"mean": mean, "std": self.distribution.std(mean)}, memory
             latent, memory = self._encode(observation, memory, done, backbone_kwargs)
             dist_kwargs = {**self.distribution_kwargs, **(distribution_kwargs or {})}
@@ -81,11 +79,9 @@ class Actor(Module):
             forward_type, deterministic = "act", True
         if forward_type not in ("explore", "act"):
             raise ValueError(f"Unsupported 'forward_type' value: {forward_type!r}")
-        if not deterministic and (layers := self._fused_layers(observation, memory, backbone_kwargs, distribution_kwargs)) is not None:
+        if not deterministic and (layers := self._fused_layers(observation, memory, backbone_kwargs, distribution_kwargs, three_layer=True)) is not None:
             # acting: backbone, mean head, Normal.rsample and its log-prob from ONE launch; eps from torch's generator exactly
             # as the unfused path draws it (distribution.py NormalDist.sample)
-            from cusrl_amd import ops
-
             self.intermediate_repr.pop("backbone.output", None)
             vector = self.distribution.std_vector()
             shape = (observation.shape[0], vector.numel())
@@ -94,10 +90,14 @@ class Actor(Module):
                 eps = torch.empty(shape, dtype=torch.float32, device=observation.device).normal_()
             elif tuple(eps.shape) != shape or eps.dtype != torch.float32 or eps.device != observation.device or not eps.is_contiguous():
                 raise RuntimeError(f"exploration noise drawn ahead for another pass: {tuple(eps.shape)} vs {shape}")
-            action, logp, mean, repeated = ops.mlp2_forward(observation, layers, std=vector, eps=eps)
+            action, logp, mean, repeated = fused_inference_forward(observation, layers, std=vector, eps=eps)
             if forward_type == "act":
                 return action, memory
             return {"mean": mean, "std": repeated}, (action, logp), memory
+        if not deterministic and not torch.is_grad_enabled():
+            # an act step that is not the fused explore pass takes no noise drawn ahead: a shape left by an earlier fused pass
+            # (a (512, 256, 128) stack is fused only outside a capture) would have the rollout draw noise this path never reads
+            self.noise_shape = None
         latent, memory = self._encode(observation, memory, None, backbone_kwargs)
         dist_kwargs = {**self.distribution_kwargs, **(distribution_kwargs or {})}
         if deterministic:
@@ -165,11 +165,9 @@ class Value(Module):
                 raise ValueError("Action must be provided when 'action_aware' is True")
             state = torch.cat([state, action], dim=-1)
         if (self.fused_inference and not self.backbone_kwargs and not kwargs
-                and (layers := fused_inference_layers(self.backbone, self.value_head, state, memory)) is not None):
-            from cusrl_amd import ops
-
+                and (layers := fused_inference_layers(self.backbone, self.value_head, state, memory, three_layer=True)) is not None):
             self.intermediate_repr.pop("backbone.output", None)
-            return ops.mlp2_forward(state, layers), memory  # the no-grad pass (value targets) as one launch
+            return fused_inference_forward(state, layers), memory  # the no-grad pass (value targets) as one launch
         kwargs = {**self.backbone_kwargs, **kwargs}
         if done is not None:
             kwargs["done"] = done

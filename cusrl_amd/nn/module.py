@@ -5,10 +5,11 @@ what is hand-written here is the backward's non-GEMM work (ReLU masks, bias colu
 
 from __future__ import annotations
 
+import functools
 from collections.abc import Iterable, Sequence
 from contextlib import contextmanager
 from dataclasses import dataclass
-from typing import Any
+from typing import Any, NamedTuple
 
 import torch
 from torch import nn
@@ -17,7 +18,7 @@ from torch.nn.functional import linear
 from cusrl_amd.utils import switches
 from cusrl_amd.utils.nest import iterate_nested
 
-__all__ = ["Linear", "LinearFp32", "fused_inference_layers", "linear_act", "Mlp", "Module", "ModuleFactory", "disable_autocast",
+__all__ = ["InferenceStack3", "Linear", "LinearFp32", "fused_inference_forward", "fused_inference_layers", "linear_act", "Mlp", "Module", "ModuleFactory", "disable_autocast",
            "double_differentiable", "is_unit_gradient", "register_unit_gradient", "resolve_activation_fn", "saved_gradients"]
 
 
@@ -296,21 +297,55 @@ class LinearFp32(nn.Linear):
 _FUSED_INFERENCE = switches.read("FUSED_INFERENCE")
 
 
-def fused_inference_layers(backbone, head: nn.Linear, input, memory=None):
+class InferenceStack3(NamedTuple):
+    """What ``ops.mlp3_forward`` evaluates: ``(w1, b1, w2, b2, w3, b3, w4, b4)``, the activation's name and ELU's alpha."""
+
+    layers: tuple
+    activation: str
+    alpha: float
+
+
+def fused_inference_layers(backbone, head: nn.Linear, input, memory=None, three_layer: bool = False):
     """``(w1, b1, w2, b2, w3, b3)`` when ``head(backbone(input))`` can be evaluated by ``ops.mlp2_forward`` right now: no gradient
     asked for, a feed-forward Linear / ReLU / Linear / ReLU backbone (``Mlp.inference_stack``) in front of a linear head, a
-    contiguous fp32 ``[B, K]`` device input outside autocast, shapes the kernel takes; else None."""
+    contiguous fp32 ``[B, K]`` device input outside autocast, shapes the kernel takes; else None.  A caller that evaluates the
+    result with :func:`fused_inference_forward` passes ``three_layer=True`` and also gets an :class:`InferenceStack3` for three
+    Linear + ReLU / ELU / Tanh pairs (``Mlp.inference_stack3``) of the widths ``ops.mlp3_forward`` takes."""
     if (not _FUSED_INFERENCE or torch.is_grad_enabled() or memory is not None or not isinstance(backbone, Mlp)
             or not isinstance(head, nn.Linear) or not isinstance(input, torch.Tensor) or not input.is_cuda or input.dim() != 2
             or input.dtype != torch.float32 or torch.is_autocast_enabled("cuda")):
         return None
-    stack = backbone.inference_stack()
-    if stack is None:
-        return None
     from cusrl_amd import ops
 
-    layers = (*stack, head.weight, head.bias)
-    return layers if ops.mlp2_forward_supported(input, layers) else None
+    stack = backbone.inference_stack()
+    if stack is not None:
+        layers = (*stack, head.weight, head.bias)
+        return layers if ops.mlp2_forward_supported(input, layers) else None
+    stack = backbone.inference_stack3() if three_layer else None
+    if stack is None:
+        return None
+    *weights, activation, alpha = stack
+    # (512, 256, 128) streams W2 for every row tile: measured faster than the chain only where the chain is bound by its eight
+    # launches — eager calls of at most one 16-row tile per CU; inside a captured graph and over a whole buffer the chain wins
+    # (DESIGN.md §7), and keeps those
+    if weights[0].shape[0] == 512 and (input.shape[0] > 16 * _compute_units(input.device) or torch.cuda.is_current_stream_capturing()):
+        return None
+    layers = (*weights, head.weight, head.bias)
+    return InferenceStack3(layers, activation, alpha) if ops.mlp3_forward_supported(input, layers, activation) else None
+
+
+@functools.lru_cache(maxsize=None)
+def _compute_units(device: torch.device) -> int:
+    return torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def fused_inference_forward(input, layers, std=None, eps=None):
+    """Evaluate what :func:`fused_inference_layers` returned: ``ops.mlp2_forward`` or ``ops.mlp3_forward``, one launch."""
+    from cusrl_amd import ops
+
+    if isinstance(layers, InferenceStack3):
+        return ops.mlp3_forward(input, layers.layers, layers.activation, layers.alpha, std=std, eps=eps)
+    return ops.mlp2_forward(input, layers, std=std, eps=eps)
 
 
 class ModuleFactory:
@@ -459,3 +494,17 @@ class Mlp(Module):
                 and type(layers[3]) is nn.ReLU and layers[0].bias is not None and layers[2].bias is not None):
             return layers[0].weight, layers[0].bias, layers[2].weight, layers[2].bias
         return None
+
+    def inference_stack3(self):
+        """``(w1, b1, w2, b2, w3, b3, activation_name, alpha)`` when this is exactly three Linear + activation pairs with biases,
+        one activation type among ReLU / ELU / Tanh and no Dropout (``ends_with_activation=True``): what ``ops.mlp3_forward``
+        evaluates — with the head behind it — in one launch when no gradient is asked for; None for anything else."""
+        layers = self.layers
+        if len(layers) != 6 or type(layers[1]) not in (nn.ReLU, nn.ELU, nn.Tanh):
+            return None
+        linears, activations = layers[0::2], layers[1::2]
+        if (any(type(m) is not Linear or m.bias is None for m in linears) or any(type(m) is not type(layers[1]) for m in activations)
+                or len({getattr(m, "alpha", 1.0) for m in activations}) != 1):
+            return None
+        weights = [t for m in linears for t in (m.weight, m.bias)]
+        return (*weights, type(layers[1]).__name__, float(getattr(layers[1], "alpha", 1.0)))

@@ -1,5 +1,5 @@
 """MLP pieces: ReLU-backward + bias gradient, first-layer backward, narrow heads, the one-launch inference pass
-(``csrc/mlp_epilogue.hip``, ``input_layer.hip``, ``narrow_linear.hip``, ``mlp_forward.hip``)."""
+(``csrc/mlp_epilogue.hip``, ``input_layer.hip``, ``narrow_linear.hip``, ``mlp_forward.hip``, ``mlp3_forward.hip``)."""
 
 from __future__ import annotations
 
@@ -124,6 +124,61 @@ def mlp2_forward(input: torch.Tensor, layers, std: torch.Tensor | None = None, e
         b2.data_ptr(), w2.shape[0], w3.data_ptr(), _ptr(b3), out_features, out.data_ptr(),
         _ptr(std) if sampling else None, _ptr(eps), _ptr(action), _ptr(logp), _ptr(repeated),
         nbytes=lambda: rows * 4 * (K + out_features * (4 if sampling else 1)) + 4 * (w1.numel() + w2.numel() + w3.numel()),
+    )
+    if sampling:
+        return action, logp, out, repeated
+    return out
+
+
+_MLP3_ACTIVATIONS = {name: _native._CONSTANTS["ACT_" + name.upper()] for name in ("ReLU", "ELU", "Tanh")}
+
+
+def mlp3_forward_supported(input: torch.Tensor, layers, activation: str = "ELU") -> bool:
+    """``layers`` = ``(w1, b1, w2, b2, w3, b3, w4, b4)`` (``b4`` may be None) of three Linear + ``activation`` pairs
+    (``"ReLU"``, ``"ELU"`` or ``"Tanh"``) and a linear head whose shapes the one-launch pass takes
+    (``cusrl_mlp3_forward_supported``), over a contiguous fp32 ``[B, K]`` device matrix."""
+    *hidden, w4, b4 = layers
+    tensors = [input, *hidden, w4] + ([b4] if b4 is not None else [])
+    if activation not in _MLP3_ACTIVATIONS or len(hidden) != 6 or input.dim() != 2 or input.shape[0] == 0 or any(
+            (not t.is_cuda) or t.dtype != torch.float32 or (not t.is_contiguous()) or t.data_ptr() % 16 for t in tensors):
+        return False
+    fan_in = input.shape[1]
+    for weight, bias in ((hidden[0], hidden[1]), (hidden[2], hidden[3]), (hidden[4], hidden[5]), (w4, b4)):
+        if weight.dim() != 2 or weight.shape[1] != fan_in or (bias is not None and bias.numel() != weight.shape[0]):
+            return False
+        fan_in = weight.shape[0]
+    return bool(_native.lib().cusrl_mlp3_forward_supported(input.shape[1], hidden[0].shape[0], hidden[2].shape[0],
+                                                           hidden[4].shape[0], w4.shape[0]))
+
+
+def mlp3_forward(input: torch.Tensor, layers, activation: str = "ELU", alpha: float = 1.0, std: torch.Tensor | None = None,
+                 eps: torch.Tensor | None = None, repeat_std: bool = True):
+    """``w4 act(w3 act(w2 act(w1 x + b1) + b2) + b3) + b4`` in ONE launch (``cusrl_mlp3_forward``), no autograd; ``alpha`` is
+    ELU's.  Returns what :func:`mlp2_forward` returns: the head's output ``[B, out]``, or with ``std`` and ``eps`` the acting
+    path's ``(action, logp [B, 1], mean, repeated std or None)``."""
+    w1, b1, w2, b2, w3, b3, w4, b4 = layers
+    if activation not in _MLP3_ACTIVATIONS:
+        raise ValueError(f"mlp3_forward: activation '{activation}' is none of {sorted(_MLP3_ACTIVATIONS)}")
+    input = _f32(input, "input")
+    rows, K = input.shape
+    out_features = w4.shape[0]
+    out = torch.empty((rows, out_features), dtype=torch.float32, device=input.device)
+    sampling = eps is not None
+    action = logp = repeated = None
+    if sampling:
+        std, eps = _f32(std, "std"), _f32(eps, "eps")
+        if std.numel() != out_features or eps.shape != out.shape:
+            raise ValueError("mlp3_forward: one std per output and one eps per output element are required")
+        action = torch.empty_like(out)
+        logp = torch.empty((rows, 1), dtype=torch.float32, device=input.device)
+        repeated = torch.empty_like(out) if repeat_std else None
+    _observed(
+        "cusrl_mlp3_forward", input.data_ptr(), rows, K, w1.data_ptr(), b1.data_ptr(), w1.shape[0], w2.data_ptr(),
+        b2.data_ptr(), w2.shape[0], w3.data_ptr(), b3.data_ptr(), w3.shape[0], w4.data_ptr(), _ptr(b4), out_features,
+        _MLP3_ACTIVATIONS[activation], float(alpha), out.data_ptr(),
+        _ptr(std) if sampling else None, _ptr(eps), _ptr(action), _ptr(logp), _ptr(repeated),
+        nbytes=lambda: rows * 4 * (K + out_features * (4 if sampling else 1))
+        + 4 * (w1.numel() + w2.numel() + w3.numel() + w4.numel()),
     )
     if sampling:
         return action, logp, out, repeated

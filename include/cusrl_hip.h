@@ -519,6 +519,22 @@ int cusrl_mlp2_forward(const float *input, int64_t rows, int64_t in_features, co
                        void *stream);
 int cusrl_mlp2_forward_supported(int64_t in_features, int64_t hidden1, int64_t hidden2, int64_t out_features);
 
+/* ---- inference pass of a three-hidden-layer ReLU / ELU / Tanh MLP + head, one launch (csrc/mlp3_forward.hip) ----
+ * output[b, :] = w4 act(w3 act(w2 act(w1 input[b, :] + b1) + b2) + b3) + b4, act = CUSRL_ACT_RELU | CUSRL_ACT_ELU (with `alpha`) |
+ * CUSRL_ACT_TANH evaluated with the expressions of cusrl_bias_act — the (512, 256, 128) / (128, 128, 128) "ELU" networks of the
+ * robotics experiments, WITHOUT autograd, in the places cusrl_mlp2_forward serves (acting, value targets, statistics).  Replaces
+ * four library GEMMs, three activation launches (+ the sampling launch).  Weights are torch.nn.Linear's, row-major; b4 may be
+ * NULL.  Sampling epilogue and its operands exactly as for cusrl_mlp2_forward (one shared body: the same bits for the same mean).
+ * A row's result does not depend on the rows evaluated with it.
+ * Supported (cusrl_mlp3_forward_supported): in % 4 == 0, 4 <= in <= 64; (hidden1, hidden2, hidden3) in {(512, 256, 128),
+ * (256, 128, 64), (128, 128, 128)}; 1 <= out <= 16; input / weights / b1..b3 16-byte aligned (output too when out % 4 == 0).
+ * Anything else, another activation code included: CUSRL_E_UNSUPPORTED, nothing launched, nothing written. */
+int cusrl_mlp3_forward(const float *input, int64_t rows, int64_t in_features, const float *w1, const float *b1, int64_t hidden1,
+                       const float *w2, const float *b2, int64_t hidden2, const float *w3, const float *b3, int64_t hidden3,
+                       const float *w4, const float *b4, int64_t out_features, int activation, float alpha, float *output,
+                       const float *std, const float *eps, float *action, float *logp, float *std_out, void *stream);
+int cusrl_mlp3_forward_supported(int64_t in_features, int64_t hidden1, int64_t hidden2, int64_t hidden3, int64_t out_features);
+
 /* ---- gradient-norm clipping (hook/on_policy/gradient_clipping.py:67-83 -> torch.nn.utils.clip_grad_norm_) ----
  * norm_out[0] = ||grad||_2 (pre-clip, the `grad_norm/default` metric); grad *= min(max_norm / (norm + 1e-6), 1).
  * max_norm < 0: measure only.  grad: float[n], 16-byte aligned (the flat gradient buffer every .grad aliases);
