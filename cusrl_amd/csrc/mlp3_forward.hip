@@ -38,27 +38,6 @@ struct Mlp3ForwardArgs {
     float alpha;
 };
 
-template <int ACT>
-__device__ __forceinline__ mfma_f32x4 act4(mfma_f32x4 v, float alpha) {
-    if constexpr (ACT == CUSRL_ACT_RELU) {
-        return relu4(v);
-    } else {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            if constexpr (ACT == CUSRL_ACT_ELU) v[reg] = v[reg] > 0.0f ? v[reg] : alpha * expm1f(v[reg]);  // torch's formula
-            else v[reg] = tanhf(v[reg]);
-        }
-        return v;
-    }
-}
-
-__device__ __forceinline__ float pick(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
-
-__device__ __forceinline__ mfma_f32x4 from_bias(const float *b) {
-    const float4 v = *reinterpret_cast<const float4 *>(b);
-    return mfma_f32x4{v.x, v.y, v.z, v.w};
-}
-
 // T1 / T2 / T3: 16-feature tiles of the hidden layers per wave (H = 64 T); KB: 16-wide k-blocks of the input; R: 16-row
 // sub-tiles evaluated per pass of the weights; CH: k-blocks per streamed chunk of W2 (0: W2 resident).
 template <int ACT, int T1, int T2, int T3, int KB, int R, int CH>

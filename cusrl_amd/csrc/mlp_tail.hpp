@@ -1,8 +1,9 @@
-// What the one-launch MLP inference passes share (mlp_forward.hip: two hidden layers, mlp3_forward.hip: three): the MFMA
-// accumulator type, the workgroup shape, ReLU as torch evaluates it, and the TAIL of a 16-row tile — the head's four per-wave
-// partial sums added in wave order, the store of the mean, and the acting path's sampling epilogue (Normal.rsample + log_prob
-// with the expressions and the association of cusrl_normal_sample_logp, rollout.hip).  One body: both kernels give the same
-// bits for the same mean.
+// What the one-launch MLP inference passes share (mlp_forward.hip: two hidden layers, mlp3_forward.hip: three,
+// mlp2_wave_forward.hip: two small ones in one wave): the MFMA accumulator type, the workgroup shape, the activations as torch
+// evaluates them, and the TAIL of a 16-row tile — the head's four per-wave partial sums added in wave order (mlp_tail; a kernel
+// whose head is complete inside one wave skips that), then mlp_tail_body: the store of the mean and the acting path's sampling
+// epilogue (Normal.rsample + log_prob with the expressions and the association of cusrl_normal_sample_logp, rollout.hip).  One
+// body: all three kernels give the same bits for the same mean.
 #pragma once
 
 #include "common.hpp"
@@ -23,6 +24,28 @@ __device__ __forceinline__ mfma_f32x4 relu4(mfma_f32x4 v) {
     return v;
 }
 
+// the activation on a tile's accumulator registers, with the expressions of cusrl_bias_act (bias_act.hip)
+template <int ACT>
+__device__ __forceinline__ mfma_f32x4 act4(mfma_f32x4 v, float alpha) {
+    if constexpr (ACT == CUSRL_ACT_RELU) {
+        return relu4(v);
+    } else {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            if constexpr (ACT == CUSRL_ACT_ELU) v[reg] = v[reg] > 0.0f ? v[reg] : alpha * expm1f(v[reg]);  // torch's formula
+            else v[reg] = tanhf(v[reg]);
+        }
+        return v;
+    }
+}
+
+__device__ __forceinline__ float pick(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+
+__device__ __forceinline__ mfma_f32x4 from_bias(const float *b) {
+    const float4 v = *reinterpret_cast<const float4 *>(b);
+    return mfma_f32x4{v.x, v.y, v.z, v.w};
+}
+
 // sampling epilogue operands of a lane (kk = lane >> 4 owns actions 4 kk .. 4 kk + 3 of row lane & 15): its four std values,
 // once per launch; its four eps values, once per tile (indices clamped: lanes past A or past the last row re-read valid ones)
 __device__ __forceinline__ void mlp_tail_sigma(const float *std, int A, int kk, float (&sigma)[4]) {
@@ -36,20 +59,13 @@ __device__ __forceinline__ void mlp_tail_noise(const float *eps, int64_t rows, i
     for (int reg = 0; reg < 4; ++reg) noise[reg] = eps[first + min(4 * (lane >> 4) + reg, A - 1)];
 }
 
-// Run by wave 0 behind the barrier that publishes `partial` ([wave][lane]: out^T[a = 4 kk + reg][m = i] of every wave's slice
-// of the head's contraction).  Args: out, eps, action, logp, std_out, rows, A as in MlpForwardArgs.
+// Everything behind the head's sum: `sum` is out^T[a = 4 kk + reg][m = i] of this lane, complete.  Args: out, eps, action, logp,
+// std_out, rows, A as in MlpForwardArgs.
 template <class Args>
-__device__ __forceinline__ void mlp_tail(const Args &p, const float4 (*partial)[kWave], int64_t row0, int lane,
-                                         const float (&sigma)[4], const float (&noise)[4]) {
+__device__ __forceinline__ void mlp_tail_body(const Args &p, const float4 sum, int64_t row0, int lane, const float (&sigma)[4],
+                                              const float (&noise)[4]) {
     const int i = lane & 15, kk = lane >> 4;
     const int A = p.A;
-    // out^T[a = 4 kk + reg][m = i]: waves added in wave order (fixed)
-    float4 sum = partial[0][lane];
-#pragma unroll
-    for (int w = 1; w < kMlpWaves; ++w) {
-        const float4 v = partial[w][lane];
-        sum.x += v.x, sum.y += v.y, sum.z += v.z, sum.w += v.w;
-    }
     const bool live = row0 + i < p.rows;
     const int a0 = 4 * kk;
     const int64_t at = (row0 + i) * A + a0;
@@ -92,6 +108,20 @@ __device__ __forceinline__ void mlp_tail(const Args &p, const float4 (*partial)[
             }
         if (live && kk == 0) p.logp[row0 + i] = lp;
     }
+}
+
+// Run by wave 0 behind the barrier that publishes `partial` ([wave][lane]: out^T[a = 4 kk + reg][m = i] of every wave's slice
+// of the head's contraction): the waves added in wave order (fixed), then the body above.
+template <class Args>
+__device__ __forceinline__ void mlp_tail(const Args &p, const float4 (*partial)[kWave], int64_t row0, int lane,
+                                         const float (&sigma)[4], const float (&noise)[4]) {
+    float4 sum = partial[0][lane];
+#pragma unroll
+    for (int w = 1; w < kMlpWaves; ++w) {
+        const float4 v = partial[w][lane];
+        sum.x += v.x, sum.y += v.y, sum.z += v.z, sum.w += v.w;
+    }
+    mlp_tail_body(p, sum, row0, lane, sigma, noise);
 }
 
 }  // namespace cusrl

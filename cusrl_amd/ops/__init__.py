@@ -63,8 +63,8 @@ from cusrl_amd.ops.loss import (
     value_loss_fwd_bwd,
 )
 from cusrl_amd.ops.mlp import (
-    _HEAD_PAD, input_layer_backward, input_layer_supported, mlp2_forward, mlp2_forward_supported, mlp3_forward,
-    mlp3_forward_supported, narrow_linear_backward, narrow_linear_forward, narrow_linear_forward_supported, narrow_linear_supported,
+    _HEAD_PAD, input_layer_backward, input_layer_supported, mlp2_forward, mlp2_forward_supported, mlp2_wave_forward,
+    mlp2_wave_forward_supported, mlp3_forward, mlp3_forward_supported, narrow_linear_backward, narrow_linear_forward, narrow_linear_forward_supported, narrow_linear_supported,
     relu_backward_bias,
 )
 from cusrl_amd.ops.recurrent import (

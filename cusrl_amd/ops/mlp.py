@@ -185,6 +185,57 @@ def mlp3_forward(input: torch.Tensor, layers, activation: str = "ELU", alpha: fl
     return out
 
 
+def mlp2_wave_forward_supported(input: torch.Tensor, layers, activation: str = "Tanh") -> bool:
+    """``layers`` = ``(w1, b1, w2, b2, w3, b3)`` (``b3`` may be None) of two Linear + ``activation`` pairs (``"ReLU"``, ``"ELU"``
+    or ``"Tanh"``) and a linear head whose shapes the wave-resident pass takes (``cusrl_mlp2_wave_forward_supported``: hidden
+    widths 32 / 64, any input width up to 64), over a contiguous fp32 ``[B, K]`` device matrix.  ``input`` and ``w1`` may sit
+    at any float address (their alignment picks the kernel's read path); the other tensors are 16-byte aligned."""
+    w1, b1, w2, b2, w3, b3 = layers
+    tensors = [input, w1, b1, w2, b2, w3] + ([b3] if b3 is not None else [])
+    if activation not in _MLP3_ACTIVATIONS or input.dim() != 2 or input.shape[0] == 0 or any(
+            (not t.is_cuda) or t.dtype != torch.float32 or (not t.is_contiguous()) for t in tensors) or any(
+            t.data_ptr() % 16 for t in tensors[2:6]):
+        return False
+    fan_in = input.shape[1]
+    for weight, bias in ((w1, b1), (w2, b2), (w3, b3)):
+        if weight.dim() != 2 or weight.shape[1] != fan_in or (bias is not None and bias.numel() != weight.shape[0]):
+            return False
+        fan_in = weight.shape[0]
+    return bool(_native.lib().cusrl_mlp2_wave_forward_supported(w1.shape[1], w1.shape[0], w2.shape[0], w3.shape[0]))
+
+
+def mlp2_wave_forward(input: torch.Tensor, layers, activation: str = "Tanh", alpha: float = 1.0, std: torch.Tensor | None = None,
+                      eps: torch.Tensor | None = None, repeat_std: bool = True):
+    """``w3 act(w2 act(w1 x + b1) + b2) + b3`` in ONE launch of one-wave workgroups (``cusrl_mlp2_wave_forward``), no autograd;
+    ``alpha`` is ELU's.  Returns what :func:`mlp2_forward` returns: the head's output ``[B, out]``, or with ``std`` and ``eps``
+    the acting path's ``(action, logp [B, 1], mean, repeated std or None)``."""
+    w1, b1, w2, b2, w3, b3 = layers
+    if activation not in _MLP3_ACTIVATIONS:
+        raise ValueError(f"mlp2_wave_forward: activation '{activation}' is none of {sorted(_MLP3_ACTIVATIONS)}")
+    input = _f32(input, "input")
+    rows, K = input.shape
+    out_features = w3.shape[0]
+    out = torch.empty((rows, out_features), dtype=torch.float32, device=input.device)
+    sampling = eps is not None
+    action = logp = repeated = None
+    if sampling:
+        std, eps = _f32(std, "std"), _f32(eps, "eps")
+        if std.numel() != out_features or eps.shape != out.shape:
+            raise ValueError("mlp2_wave_forward: one std per output and one eps per output element are required")
+        action = torch.empty_like(out)
+        logp = torch.empty((rows, 1), dtype=torch.float32, device=input.device)
+        repeated = torch.empty_like(out) if repeat_std else None
+    _observed(
+        "cusrl_mlp2_wave_forward", input.data_ptr(), rows, K, w1.data_ptr(), b1.data_ptr(), w1.shape[0], w2.data_ptr(),
+        b2.data_ptr(), w2.shape[0], w3.data_ptr(), _ptr(b3), out_features, _MLP3_ACTIVATIONS[activation], float(alpha),
+        out.data_ptr(), _ptr(std) if sampling else None, _ptr(eps), _ptr(action), _ptr(logp), _ptr(repeated),
+        nbytes=lambda: rows * 4 * (K + out_features * (4 if sampling else 1)) + 4 * (w1.numel() + w2.numel() + w3.numel()),
+    )
+    if sampling:
+        return action, logp, out, repeated
+    return out
+
+
 def narrow_linear_backward(grad_output: torch.Tensor, input: torch.Tensor, weight: torch.Tensor,
                            need_input_grad: bool = True, relu_input: bool = False, defer: bool = False):
     """``(grad_output @ weight, grad_output.T @ input, grad_output.sum(0))`` of a linear layer with at most 16

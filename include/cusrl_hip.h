@@ -535,6 +535,25 @@ int cusrl_mlp3_forward(const float *input, int64_t rows, int64_t in_features, co
                        const float *std, const float *eps, float *action, float *logp, float *std_out, void *stream);
 int cusrl_mlp3_forward_supported(int64_t in_features, int64_t hidden1, int64_t hidden2, int64_t hidden3, int64_t out_features);
 
+/* ---- inference pass of a SMALL two-hidden-layer ReLU / ELU / Tanh MLP + head, one launch (csrc/mlp2_wave_forward.hip) ----
+ * output[b, :] = w3 act(w2 act(w1 input[b, :] + b1) + b2) + b3, act = CUSRL_ACT_RELU | CUSRL_ACT_ELU (with `alpha`) |
+ * CUSRL_ACT_TANH evaluated with the expressions of cusrl_bias_act — the (64, 64) "Tanh" networks of the classic-control
+ * experiments over 2- to 6-wide observations, WITHOUT autograd, in the places cusrl_mlp2_forward serves (acting, value targets,
+ * statistics).  Replaces three library GEMMs, two activation launches (+ the sampling launch).  One wave holds all three weight
+ * matrices and carries a 16-row tile from the input to the head in its registers: no LDS, no barrier.  Weights are
+ * torch.nn.Linear's, row-major; b3 may be NULL.  Sampling epilogue and its operands exactly as for cusrl_mlp2_forward (one shared
+ * body: the same bits for the same mean).  A row's result depends neither on the rows evaluated with it nor on the alignment of
+ * `input` / `w1`: with in % 4 == 0 and both 16-byte aligned they are read 16 bytes at a time, else 4 bytes at a time, into the
+ * same sums.
+ * Supported (cusrl_mlp2_wave_forward_supported): 1 <= in <= 64 (any, no multiple-of-4 condition); hidden1, hidden2 in {32, 64};
+ * 1 <= out <= 16; b1 / w2 / b2 / w3 16-byte aligned (output too when out % 4 == 0).  Disjoint from cusrl_mlp2_forward's set.
+ * Anything else, another activation code included: CUSRL_E_UNSUPPORTED, nothing launched, nothing written. */
+int cusrl_mlp2_wave_forward(const float *input, int64_t rows, int64_t in_features, const float *w1, const float *b1,
+                            int64_t hidden1, const float *w2, const float *b2, int64_t hidden2, const float *w3, const float *b3,
+                            int64_t out_features, int activation, float alpha, float *output, const float *std, const float *eps,
+                            float *action, float *logp, float *std_out, void *stream);
+int cusrl_mlp2_wave_forward_supported(int64_t in_features, int64_t hidden1, int64_t hidden2, int64_t out_features);
+
 /* ---- gradient-norm clipping (hook/on_policy/gradient_clipping.py:67-83 -> torch.nn.utils.clip_grad_norm_) ----
  * norm_out[0] = ||grad||_2 (pre-clip, the `grad_norm/default` metric); grad *= min(max_norm / (norm + 1e-6), 1).
  * max_norm < 0: measure only.  grad: float[n], 16-byte aligned (the flat gradient buffer every .grad aliases);
