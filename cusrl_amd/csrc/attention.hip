@@ -23,67 +23,24 @@
 //
 // LDS rows are padded to an odd stride (head_dim | 1): lanes that walk different rows at one column hit different banks.
 // The region is dynamic and nothing static sits in front of it.
-#include <math.h>
-
-#include <initializer_list>
 #include <type_traits>
 
-#include "common.hpp"
+#include "attention_common.hpp"  // kOwn, kTile, Rows, Shape, Span, Mask, softmax_step and the host's size rules
 
 namespace cusrl {
 namespace {
 
-constexpr int kOwn = 16;    // rows a workgroup owns
-constexpr int kTile = 32;   // rows of the streamed side per step
 constexpr int kGroup = 16;  // lanes per owned row (kOwn * kGroup == kBlock)
 constexpr int kPerLane = kTile / kGroup;                    // scores per lane and tile
 constexpr int kAcc = CUSRL_MAX_SDPA_HEAD_DIM / kGroup;      // output columns per lane
 constexpr int64_t kSdpaMaxBlocks = 1 << 16;                 // the grid strides over what is left
 static_assert(kOwn * kGroup == kBlock, "one lane group per owned row");
 
-struct Rows {  // [N, L, H, D] with element (n, l, h, d) at p + n * sn + l * sl + h * D + d
-    const float *p;
-    int64_t sn, sl;
-};
-
-struct Shape {
-    int64_t N, H, Lq, Lk;
-    int D;
-    float scale;
-};
-
-struct Span {  // tiles [begin, begin + kTile), ... of the streamed side up to `end`
-    int64_t begin, end;
-};
-
 // The two visibilities.  score(): the score of query i < Lq against key j < Lk, or -inf where i must not see j.  keys(): the
 // key tiles that can hold a key visible to a query of q0 ... q0 + kOwn - 1; queries(): the query tiles that can hold a query
 // that sees a key of j0 ... j0 + kOwn - 1.  Every (i, j) outside those spans scores -inf.  kSkipsKeys: whether the key-major
 // pass may be told to start behind key 0 (its key_from); where it may not, key_from is the constant 0 in the kernel.
-
-struct Mask {  // dense: element strides (n, h, q, k) of the keep-mask or of the bias (at most one of the two is present)
-    const uint8_t *keep;
-    const float *bias;
-    int64_t sn, sh, sq, sk;
-    int causal;
-    static constexpr bool kSkipsKeys = false;
-
-    // scale * (q . k) + bias
-    __device__ __forceinline__ float score(float qk, float scale, int64_t n, int64_t h, int64_t i, int64_t j, int64_t) const {
-        if (causal && j > i) return -INFINITY;
-        float s = qk * scale;
-        if (keep || bias) {
-            const int64_t at = n * sn + h * sh + i * sq + j * sk;
-            if (keep && !keep[at]) return -INFINITY;
-            if (bias) s = s + bias[at];
-        }
-        return s;
-    }
-    // (top-left causal: keys past the tile's last query are masked for every row of it)
-    __device__ __forceinline__ Span keys(int64_t q0, const Shape &s) const { return {0, causal ? min(s.Lk, q0 + kOwn) : s.Lk}; }
-    // (top-left causal: queries in front of the tile's first key see none of its keys)
-    __device__ __forceinline__ Span queries(int64_t j0, const Shape &s) const { return {causal ? j0 / kTile * kTile : 0, s.Lq}; }
-};
+// (Mask, the dense one: attention_common.hpp.)
 
 struct Band {  // Lk = Lq + W, the first W keys are the cache, and query i sees keys i ... i + W
     const uint8_t *valid;  // [N, Lq + W] contiguous, nonzero = a key that exists; or NULL
@@ -147,25 +104,6 @@ __device__ __forceinline__ float dot(const float *a, const float *b, int D) {
     float s = 0.0f;
     for (int d = 0; d < D; ++d) s = fmaf(a[d], b[d], s);
     return s;
-}
-
-// One step of a row's online softmax: m becomes max(m, top), where top is the largest of the step's scores over the whole row
-// group; the scores become exp(score - m) in place (0 for -inf) and the factor that rescales what the row has accumulated
-// so far is returned.  A row that has seen no key yet keeps m = -inf, weights of 0 and a factor of 1.
-template <int kScores>
-__device__ __forceinline__ float softmax_step(float &m, float top, float (&score)[kScores]) {
-    const float m_new = fmaxf(m, top);
-    float alpha = 1.0f;
-    if (m_new != -INFINITY) {
-        alpha = (m == -INFINITY) ? 0.0f : expf(m - m_new);
-#pragma unroll
-        for (int c = 0; c < kScores; ++c) score[c] = (score[c] == -INFINITY) ? 0.0f : expf(score[c] - m_new);
-    } else {
-#pragma unroll
-        for (int c = 0; c < kScores; ++c) score[c] = 0.0f;
-    }
-    m = m_new;
-    return alpha;
 }
 
 // exp(s - lse) for a visible score of a row with a visible key, exactly 0 otherwise (never exp(-inf - (-inf))).
@@ -422,12 +360,6 @@ __global__ __launch_bounds__(kStepBlock) void band_step_kernel(Rows q, Rows k, R
 }
 
 // --------------------------------------------------------------------------------------------------------------- host
-bool rows_vectorise(std::initializer_list<Rows> tensors, int D) {  // 16-byte loads: every row of every tensor starts on one
-    for (const Rows &t : tensors)
-        if (!aligned(t.p, 16) || t.sn % 4 || t.sl % 4) return false;
-    return D % 4 == 0;
-}
-
 // launch(width) with the kernels' kWidth as a compile-time constant: 4 where the operands vectorise, else 1.
 template <typename Launch>
 void with_width(bool vec, Launch launch) {
@@ -437,20 +369,9 @@ void with_width(bool vec, Launch launch) {
         launch(std::integral_constant<int, 1>{});
 }
 
-bool sizes_fit(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {  // every contiguous extent within int64
-    const int64_t L = Lq > Lk ? Lq : Lk;
-    if (H > INT64_MAX / D) return false;
-    if (L > INT64_MAX / (H * D)) return false;
-    return N == 0 || L * H * D <= INT64_MAX / N;
-}
-
 uint32_t grid_for(int64_t items) { return uint32_t(items < kSdpaMaxBlocks ? items : kSdpaMaxBlocks); }
 
 size_t lds_bytes(int rows, int extra, int D) { return (size_t(rows) * (D | 1) + extra) * sizeof(float); }
-
-bool valid_sizes(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {
-    return N >= 0 && H >= 1 && Lq >= 1 && Lk >= 1 && D >= 1 && D <= CUSRL_MAX_SDPA_HEAD_DIM;
-}
 
 bool valid_band_sizes(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
     return N >= 0 && H >= 1 && Lq >= 1 && W >= 1 && D >= 1 && D <= CUSRL_MAX_SDPA_HEAD_DIM;

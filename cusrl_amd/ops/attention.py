@@ -5,6 +5,8 @@ backward call, on the ``[N, L, H, D]`` layout the attention modules produce — 
 from __future__ import annotations
 
 import math
+import threading
+from contextlib import contextmanager
 
 import torch
 from torch.nn.functional import scaled_dot_product_attention
@@ -77,6 +79,35 @@ def sdpa_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: b
     return not _differentiated_inside_double_differentiable((q, k, v))
 
 
+# ``matrix_core_attention()``: per thread, whether ``sdpa`` calls that leave ``matrix_core=None`` ask for the MFMA forward
+_matrix_core = threading.local()
+
+
+@contextmanager
+def matrix_core_attention(enabled: bool = True):
+    """Inside the context, :func:`sdpa` calls that leave ``matrix_core=None`` behave as ``matrix_core=enabled`` — how the attention
+    modules reach ``cusrl_sdpa_fwd_mfma`` with no constructor changing: ``with ops.matrix_core_attention(): layer(x)``.
+    Thread-local, nestable, the previous state restored on exit."""
+    previous = getattr(_matrix_core, "enabled", False)
+    _matrix_core.enabled = bool(enabled)
+    try:
+        yield
+    finally:
+        _matrix_core.enabled = previous
+
+
+def sdpa_mfma_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False) -> bool:
+    """Does ``cusrl_sdpa_fwd_mfma`` take this call right now?  :func:`sdpa_supported`, the shapes the library accepts
+    (``cusrl_sdpa_fwd_mfma_supported``: ``D % 4 == 0``, ``4 <= D <= 128``) and the 16-byte rule on the ``[N, L, H, D]`` views:
+    every base 16-byte aligned, ``n`` / ``l`` strides multiples of 4."""
+    if not sdpa_supported(q, k, v, attn_mask, dropout_p, is_causal):
+        return False
+    if not _native.lib().cusrl_sdpa_fwd_mfma_supported(q.shape[-3], k.shape[-3], q.shape[-1]):
+        return False
+    views = [_one_batch_dimension(t) for t in (q, k, v)]
+    return all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 for t in views)
+
+
 def _sdpa_expression(q, k, v, attn_mask, dropout_p, is_causal):
     """The reference's call (cusrl/nn/layer/mha.py:133-140), so every error is torch's own."""
     return scaled_dot_product_attention(q.transpose(-2, -3), k.transpose(-2, -3), v.transpose(-2, -3), attn_mask=attn_mask,
@@ -111,12 +142,14 @@ def _backward_operands(q, dout, key_rows: int, workspace_floats: int):
     return dout, dq, dk, dv, torch.empty(int(workspace_floats), dtype=torch.float32, device=q.device)
 
 
-def _launch_sdpa_fwd(q, k, v, mask=None, is_causal: bool = False):
-    """One ``cusrl_sdpa_fwd`` launch on ``[N, L, H, D]`` operands: ``(out [N, Lq, H, D], lse [N, H, Lq])``."""
+def _launch_sdpa_fwd(q, k, v, mask=None, is_causal: bool = False, matrix_core: bool = False):
+    """One ``cusrl_sdpa_fwd`` launch (``matrix_core``: one ``cusrl_sdpa_fwd_mfma`` launch, on operands
+    :func:`sdpa_mfma_supported` accepted) on ``[N, L, H, D]`` operands: ``(out [N, Lq, H, D], lse [N, H, Lq])``."""
     N, Lq, H, D = q.shape
     Lk = k.shape[1]
     out, lse = _forward_outputs(q)
-    _checked.cusrl_sdpa_fwd(*_rows_arguments(q, k, v), *_mask_arguments(mask, N, H, Lq, Lk), int(is_causal), 1.0 / math.sqrt(D),
+    launch = _checked.cusrl_sdpa_fwd_mfma if matrix_core else _checked.cusrl_sdpa_fwd
+    launch(*_rows_arguments(q, k, v), *_mask_arguments(mask, N, H, Lq, Lk), int(is_causal), 1.0 / math.sqrt(D),
                             out.data_ptr(), lse.data_ptr(), N, H, Lq, Lk, D, _stream())
     return out, lse
 
@@ -134,14 +167,15 @@ def sdpa_backward(q, k, v, out, lse, dout, mask=None, is_causal: bool = False):
 
 
 class Sdpa(torch.autograd.Function):
-    """``apply(q, k, v, mask | None, is_causal) -> out`` on ``[N, L, H, D]`` operands :func:`sdpa_supported` accepted: one
-    ``cusrl_sdpa_fwd`` launch forward, one ``cusrl_sdpa_bwd`` call backward.  Saved: ``q``, ``k``, ``v``, ``out``, the row
+    """``apply(q, k, v, mask | None, is_causal[, matrix_core]) -> out`` on ``[N, L, H, D]`` operands :func:`sdpa_supported`
+    accepted: one ``cusrl_sdpa_fwd`` launch forward (``matrix_core``: one ``cusrl_sdpa_fwd_mfma`` launch, on operands
+    :func:`sdpa_mfma_supported` accepted), one ``cusrl_sdpa_bwd`` call backward either way.  Saved: ``q``, ``k``, ``v``, ``out``, the row
     statistics ``lse [N, H, Lq]`` and the mask as it was given — nothing of size ``Lq x Lk``; the backward recomputes the
     probabilities."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, is_causal):
-        out, lse = _launch_sdpa_fwd(q, k, v, mask, is_causal)
+    def forward(ctx, q, k, v, mask, is_causal, matrix_core=False):
+        out, lse = _launch_sdpa_fwd(q, k, v, mask, is_causal, matrix_core)
         ctx.save_for_backward(q, k, v, out, lse, *(() if mask is None else (mask,)))
         ctx.is_causal = is_causal
         return out
@@ -151,22 +185,29 @@ class Sdpa(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, out, lse, *mask = ctx.saved_tensors
         dq, dk, dv = sdpa_backward(q, k, v, out, lse, dout, mask[0] if mask else None, ctx.is_causal)
-        return dq, dk, dv, None, None
+        return dq, dk, dv, None, None, None
 
 
-def sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False) -> torch.Tensor:
+def sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, matrix_core: bool | None = None) -> torch.Tensor:
     """``softmax(q k^T / sqrt(D) + mask) v`` per head on the ``[N, L, H, D]`` layout, returned in the same layout.  One launch
     where :func:`sdpa_supported` says so (the forward launch alone when no gradient is asked for);
     ``F.scaled_dot_product_attention`` on the transposed views everywhere else: CPU tensors, float64, autocast, dropout,
-    ``D`` beyond the kernel's, a mask together with ``is_causal``."""
+    ``D`` beyond the kernel's, a mask together with ``is_causal``.
+
+    ``matrix_core``: True takes the fp32-MFMA forward ``cusrl_sdpa_fwd_mfma`` where :func:`sdpa_mfma_supported` says so and goes
+    on as above where it does not; None (the default) reads :func:`matrix_core_attention`, which is off outside the context;
+    False never takes it.  Its results agree with the other forward's to rounding, not to the bit (include/cusrl_hip.h)."""
     if not sdpa_supported(q, k, v, attn_mask, dropout_p, is_causal):
         return _sdpa_expression(q, k, v, attn_mask, dropout_p, is_causal)
+    if matrix_core is None:
+        matrix_core = getattr(_matrix_core, "enabled", False)
+    matrix_core = bool(matrix_core) and sdpa_mfma_supported(q, k, v, attn_mask, dropout_p, is_causal)
     shape = q.shape
     q, k, v = (_one_batch_dimension(t) for t in (q, k, v))
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
-        out = Sdpa.apply(q, k, v, attn_mask, bool(is_causal))
+        out = Sdpa.apply(q, k, v, attn_mask, bool(is_causal), matrix_core)
     else:
-        out, _ = _launch_sdpa_fwd(q, k, v, attn_mask, bool(is_causal))
+        out, _ = _launch_sdpa_fwd(q, k, v, attn_mask, bool(is_causal), matrix_core)
     return out.view(shape)
 
 

@@ -1044,6 +1044,21 @@ int cusrl_sdpa_bwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, const
                    float scale, float *dq, float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t Lk,
                    int64_t D, void *stream);
 int64_t cusrl_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D);
+/* cusrl_sdpa_fwd_mfma, ONE launch (csrc/attention_mfma.hip): the forward of cusrl_sdpa_fwd - its argument list, layout, masks,
+ * formulas for out and lse, and its handling of a query row with every key masked - on v_mfma_f32_16x16x4_f32, for long keys and
+ * large heads.  out and lse feed cusrl_sdpa_bwd as cusrl_sdpa_fwd's do.  What differs is the ORDER of the two sums: the score's sum
+ * over d runs in blocks of 16, within a block d = 4 kk + j over the four k slots kk of MFMA j = 0 .. 3; the sum over keys runs in
+ * sub-tiles of 16 keys, key 4 kk + j in slot kk of MFMA j.  So the results agree with cusrl_sdpa_fwd's to rounding, not to the bit;
+ * they are the same bits on every call, and a query row's bits do not depend on its lane, wave, workgroup, batch position or Lq.
+ * Supported: cusrl_sdpa_fwd_mfma_supported(Lq, Lk, D) (nonzero for Lq, Lk >= 1 and D % 4 == 0, 4 <= D <= 128) and the 16-byte
+ * rule above for q, k, v - every strided base 16-byte aligned, stride_n and stride_l multiples of 4 - and a 16-byte aligned out.
+ * CUSRL_E_INVALID for what cusrl_sdpa_fwd calls invalid; CUSRL_E_UNSUPPORTED for a valid call outside the supported set (another D,
+ * a misaligned view, an extent beyond int64); nothing is launched or written in either case.  N == 0 is a successful no-op. */
+int cusrl_sdpa_fwd_mfma(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n, int64_t k_stride_l,
+                        const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *keep_mask, const float *bias,
+                        int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q, int64_t mask_stride_k, int causal,
+                        float scale, float *out, float *lse, int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D, void *stream);
+int cusrl_sdpa_fwd_mfma_supported(int64_t Lq, int64_t Lk, int64_t D);
 int cusrl_rope_apply(const float *x, int64_t x_stride_n, int64_t x_stride_l, const float *cos_rows, const float *sin_rows,
                      float *out, int64_t N, int64_t L, int64_t H, int64_t D, int transpose, void *stream);
 

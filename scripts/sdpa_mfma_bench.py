@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""The fp32-MFMA attention forward (cusrl_sdpa_fwd_mfma) next to the VALU forward (cusrl_sdpa_fwd) on the same tensors: the
+``[N, L, H, D]`` shapes below (``Lq = Lk = L``), causal and unmasked, and one line with a bool mask.  Each path is timed inside a
+replayed graph of LAUNCHES launches (host clock around replays that end in a synchronise), the two alternating for ROUNDS rounds in
+one process; a line gives the median of each in us per call, the spread (max - min) / median over the rounds, the rate over the
+4 N H L^2 D operations of the two products (half of them under the causal mask) and the verdict: a path counts as faster only where
+the ratio of the medians exceeds 1 + the larger of the two spreads.  The outputs of the two paths are compared first.
+
+    python scripts/sdpa_mfma_bench.py [--rounds 3]
+"""
+import argparse
+import statistics
+import sys
+import time
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+import torch  # noqa: E402
+
+from cusrl_amd import ops  # noqa: E402
+from cusrl_amd.ops.attention import _launch_sdpa_fwd  # noqa: E402
+
+SHAPES = ((256, 16, 4, 16), (64, 128, 4, 32), (16, 512, 8, 64), (4, 2048, 8, 128))  # [N, L, H, D]
+CASES = [(shape, mask) for shape in SHAPES for mask in ("none", "causal")] + [((16, 512, 8, 64), "bool")]
+LAUNCHES = 10
+
+
+def captured(fn):
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        fn()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        for _ in range(LAUNCHES):
+            fn()
+    graph.replay()
+    torch.cuda.synchronize()
+    return graph
+
+
+def replay_time(graph, seconds=0.2):
+    """us per call over at least ``seconds`` of replays."""
+    replays, elapsed = 0, 0.0
+    t0 = time.perf_counter()
+    while elapsed < seconds:
+        for _ in range(5):
+            graph.replay()
+        torch.cuda.synchronize()
+        replays, elapsed = replays + 5, time.perf_counter() - t0
+    return elapsed / replays / LAUNCHES * 1e6
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--rounds", type=int, default=3)
+    rounds = parser.parse_args().rounds
+    dev = "cuda:0"
+    torch.manual_seed(0)
+    for (N, L, H, D), kind in CASES:
+        q, k, v = (torch.randn(N, L, H, D, device=dev) for _ in range(3))
+        mask = torch.rand(L, L, device=dev) < 0.7 if kind == "bool" else None
+        causal = kind == "causal"
+        assert ops.sdpa_mfma_supported(q, k, v, mask, 0.0, causal)
+        paths = {"mfma": lambda: _launch_sdpa_fwd(q, k, v, mask, causal, True), "valu": lambda: _launch_sdpa_fwd(q, k, v, mask, causal, False)}
+        with torch.no_grad():
+            (out_m, lse_m), (out_v, lse_v) = paths["mfma"](), paths["valu"]()
+            differ = float((out_m - out_v).abs().max() / out_v.abs().max())
+            graphs = {path: captured(fn) for path, fn in paths.items()}
+            times = {path: [] for path in paths}
+            for _ in range(rounds):  # the two paths alternate within a round
+                for path in paths:
+                    times[path].append(replay_time(graphs[path]))
+        med = {path: statistics.median(times[path]) for path in paths}
+        spread = {path: (max(times[path]) - min(times[path])) / med[path] for path in paths}
+        ratio, noise = med["valu"] / med["mfma"], max(spread.values())
+        verdict = "mfma faster" if ratio > 1 + noise else "valu faster" if 1 / ratio > 1 + noise else "within spread"
+        flops = 4.0 * N * H * L * L * D * (0.5 if causal else 1.0)
+        print(f"[{N:3d},{L:5d},{H:2d},{D:4d}] {kind:6s}  mfma {med['mfma']:9.2f} us (spread {spread['mfma']:5.1%}, {flops / med['mfma'] / 1e6:6.2f} TFLOP/s)  "
+              f"valu {med['valu']:9.2f} us (spread {spread['valu']:5.1%}, {flops / med['valu'] / 1e6:6.2f} TFLOP/s)  valu / mfma {ratio:5.2f}  {verdict}"
+              f"  max |out difference| {differ:.1e} of the largest entry", flush=True)
+        del graphs
+
+
+if __name__ == "__main__":
+    main()
