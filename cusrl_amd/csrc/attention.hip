@@ -25,7 +25,7 @@
 // The region is dynamic and nothing static sits in front of it.
 #include <type_traits>
 
-#include "attention_common.hpp"  // kOwn, kTile, Rows, Shape, Span, Mask, softmax_step and the host's size rules
+#include "attention_common.hpp"  // kOwn, kTile, Rows, Shape, Span, Mask, softmax_step, probability and the host's size rules
 
 namespace cusrl {
 namespace {
@@ -105,9 +105,6 @@ __device__ __forceinline__ float dot(const float *a, const float *b, int D) {
     for (int d = 0; d < D; ++d) s = fmaf(a[d], b[d], s);
     return s;
 }
-
-// exp(s - lse) for a visible score of a row with a visible key, exactly 0 otherwise (never exp(-inf - (-inf))).
-__device__ __forceinline__ float probability(float s, float lse) { return (s == -INFINITY || lse == -INFINITY) ? 0.0f : expf(s - lse); }
 
 // Store a lane's output columns of one owned row: dst row `row` of a contiguous [N, L, H, D] tensor.
 __device__ __forceinline__ void store_columns(float *dst, const float (&acc)[kAcc], int g, int D) {

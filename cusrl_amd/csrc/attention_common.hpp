@@ -1,6 +1,7 @@
-// What the attention translation units share (attention.hip: the VALU bodies; attention_mfma.hip: the fp32-MFMA forward): the
-// operand and shape structs, the dense visibility `Mask` with the two tile constants its spans are written in, the online-softmax
-// step, and the host's size and 16-byte rules.  Moved here from attention.hip as they stood; formulas: include/cusrl_hip.h.
+// What the attention translation units share (attention.hip: the VALU bodies; attention_mfma.hip and attention_mfma_bwd.hip: the
+// fp32-MFMA forward and backward): the operand and shape structs, the dense visibility `Mask` with the two tile constants its spans
+// are written in, the online-softmax step, the backward's `probability`, and the host's size and 16-byte rules.  Moved here from
+// attention.hip as they stood; formulas: include/cusrl_hip.h.
 #pragma once
 
 #include <math.h>
@@ -72,6 +73,9 @@ __device__ __forceinline__ float softmax_step(float &m, float top, float (&score
     m = m_new;
     return alpha;
 }
+
+// exp(s - lse) for a visible score of a row with a visible key, exactly 0 otherwise (never exp(-inf - (-inf))).
+__device__ __forceinline__ float probability(float s, float lse) { return (s == -INFINITY || lse == -INFINITY) ? 0.0f : expf(s - lse); }
 
 // --------------------------------------------------------------------------------------------------------------- host
 inline bool rows_vectorise(std::initializer_list<Rows> tensors, int D) {  // 16-byte loads: every row of every tensor starts on one

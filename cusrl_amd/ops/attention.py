@@ -80,32 +80,48 @@ def sdpa_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: b
 
 
 # ``matrix_core_attention()``: per thread, whether ``sdpa`` calls that leave ``matrix_core=None`` ask for the MFMA forward
+# (``enabled``) and those that leave ``matrix_core_backward=None`` for the MFMA backward (``backward``)
 _matrix_core = threading.local()
 
 
 @contextmanager
-def matrix_core_attention(enabled: bool = True):
-    """Inside the context, :func:`sdpa` calls that leave ``matrix_core=None`` behave as ``matrix_core=enabled`` — how the attention
-    modules reach ``cusrl_sdpa_fwd_mfma`` with no constructor changing: ``with ops.matrix_core_attention(): layer(x)``.
-    Thread-local, nestable, the previous state restored on exit."""
-    previous = getattr(_matrix_core, "enabled", False)
-    _matrix_core.enabled = bool(enabled)
+def matrix_core_attention(enabled: bool = True, backward: bool = False):
+    """Inside the context, :func:`sdpa` calls that leave ``matrix_core=None`` behave as ``matrix_core=enabled`` and those that leave
+    ``matrix_core_backward=None`` as ``matrix_core_backward=backward`` — how the attention modules reach ``cusrl_sdpa_fwd_mfma`` and
+    ``cusrl_sdpa_bwd_mfma`` with no constructor changing: ``with ops.matrix_core_attention(backward=True): layer(x)``.
+    Thread-local, nestable, both fields restored on exit."""
+    previous = getattr(_matrix_core, "enabled", False), getattr(_matrix_core, "backward", False)
+    _matrix_core.enabled, _matrix_core.backward = bool(enabled), bool(backward)
     try:
         yield
     finally:
-        _matrix_core.enabled = previous
+        _matrix_core.enabled, _matrix_core.backward = previous
+
+
+def _sixteen_byte_rule(*tensors) -> bool:
+    """Every ``[N, L, H, D]`` view's base 16-byte aligned, its ``n`` / ``l`` strides multiples of 4."""
+    return all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 for t in tensors)
+
+
+def _mfma_supported(entry: str, q, k, v, attn_mask, dropout_p, is_causal) -> bool:
+    if not sdpa_supported(q, k, v, attn_mask, dropout_p, is_causal):
+        return False
+    if not getattr(_native.lib(), entry)(q.shape[-3], k.shape[-3], q.shape[-1]):
+        return False
+    return _sixteen_byte_rule(*(_one_batch_dimension(t) for t in (q, k, v)))
 
 
 def sdpa_mfma_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False) -> bool:
     """Does ``cusrl_sdpa_fwd_mfma`` take this call right now?  :func:`sdpa_supported`, the shapes the library accepts
     (``cusrl_sdpa_fwd_mfma_supported``: ``D % 4 == 0``, ``4 <= D <= 128``) and the 16-byte rule on the ``[N, L, H, D]`` views:
     every base 16-byte aligned, ``n`` / ``l`` strides multiples of 4."""
-    if not sdpa_supported(q, k, v, attn_mask, dropout_p, is_causal):
-        return False
-    if not _native.lib().cusrl_sdpa_fwd_mfma_supported(q.shape[-3], k.shape[-3], q.shape[-1]):
-        return False
-    views = [_one_batch_dimension(t) for t in (q, k, v)]
-    return all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 for t in views)
+    return _mfma_supported("cusrl_sdpa_fwd_mfma_supported", q, k, v, attn_mask, dropout_p, is_causal)
+
+
+def sdpa_bwd_mfma_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False) -> bool:
+    """Does ``cusrl_sdpa_bwd_mfma`` take the backward of this call?  What :func:`sdpa_mfma_supported` asks, with the library's
+    ``cusrl_sdpa_bwd_mfma_supported``; ``dout`` is held to the 16-byte rule when it arrives (:func:`sdpa_backward`)."""
+    return _mfma_supported("cusrl_sdpa_bwd_mfma_supported", q, k, v, attn_mask, dropout_p, is_causal)
 
 
 def _sdpa_expression(q, k, v, attn_mask, dropout_p, is_causal):
@@ -154,41 +170,48 @@ def _launch_sdpa_fwd(q, k, v, mask=None, is_causal: bool = False, matrix_core: b
     return out, lse
 
 
-def sdpa_backward(q, k, v, out, lse, dout, mask=None, is_causal: bool = False):
+def sdpa_backward(q, k, v, out, lse, dout, mask=None, is_causal: bool = False, matrix_core: bool = False):
     """The ``cusrl_sdpa_bwd`` call by itself: ``(dq, dk, dv)``, contiguous ``[N, L, H, D]``.  ``q``, ``k``, ``v`` and ``dout`` may
-    be strided as :func:`sdpa_supported` allows; ``out`` and ``lse`` are the forward's."""
+    be strided as :func:`sdpa_supported` allows; ``out`` and ``lse`` are the forward's — either forward's.  ``matrix_core``: the
+    ``cusrl_sdpa_bwd_mfma`` call in its place where the library takes the shapes and ``q``, ``k``, ``v``, ``out`` and ``dout`` (after
+    the rows-layout copy) pass the 16-byte rule; ``cusrl_sdpa_bwd`` where not."""
     N, Lq, H, D = q.shape
     Lk = k.shape[1]
     dout, dq, dk, dv, workspace = _backward_operands(q, dout, Lk, _native.lib().cusrl_sdpa_bwd_workspace(N, H, Lq, Lk, D))
-    _checked.cusrl_sdpa_bwd(*_rows_arguments(q, k, v), out.data_ptr(), lse.data_ptr(), *_rows_arguments(dout),
-                            *_mask_arguments(mask, N, H, Lq, Lk), int(is_causal), 1.0 / math.sqrt(D), dq.data_ptr(), dk.data_ptr(),
-                            dv.data_ptr(), workspace.data_ptr(), N, H, Lq, Lk, D, _stream())
+    matrix_core = (bool(matrix_core) and _native.lib().cusrl_sdpa_bwd_mfma_supported(Lq, Lk, D)
+                   and _sixteen_byte_rule(q, k, v, out, dout))
+    launch = _checked.cusrl_sdpa_bwd_mfma if matrix_core else _checked.cusrl_sdpa_bwd
+    launch(*_rows_arguments(q, k, v), out.data_ptr(), lse.data_ptr(), *_rows_arguments(dout), *_mask_arguments(mask, N, H, Lq, Lk),
+           int(is_causal), 1.0 / math.sqrt(D), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), workspace.data_ptr(), N, H, Lq, Lk, D,
+           _stream())
     return dq, dk, dv
 
 
 class Sdpa(torch.autograd.Function):
-    """``apply(q, k, v, mask | None, is_causal[, matrix_core]) -> out`` on ``[N, L, H, D]`` operands :func:`sdpa_supported`
-    accepted: one ``cusrl_sdpa_fwd`` launch forward (``matrix_core``: one ``cusrl_sdpa_fwd_mfma`` launch, on operands
-    :func:`sdpa_mfma_supported` accepted), one ``cusrl_sdpa_bwd`` call backward either way.  Saved: ``q``, ``k``, ``v``, ``out``, the row
-    statistics ``lse [N, H, Lq]`` and the mask as it was given — nothing of size ``Lq x Lk``; the backward recomputes the
-    probabilities."""
+    """``apply(q, k, v, mask | None, is_causal[, matrix_core[, matrix_core_backward]]) -> out`` on ``[N, L, H, D]`` operands
+    :func:`sdpa_supported` accepted: one ``cusrl_sdpa_fwd`` launch forward (``matrix_core``: one ``cusrl_sdpa_fwd_mfma`` launch, on
+    operands :func:`sdpa_mfma_supported` accepted), one ``cusrl_sdpa_bwd`` call backward (``matrix_core_backward``: one
+    ``cusrl_sdpa_bwd_mfma`` call where :func:`sdpa_backward` finds the operands fit, decided per call when ``dout`` arrives).  Saved:
+    ``q``, ``k``, ``v``, ``out``, the row statistics ``lse [N, H, Lq]`` and the mask as it was given — nothing of size ``Lq x Lk``;
+    the backward recomputes the probabilities."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, is_causal, matrix_core=False):
+    def forward(ctx, q, k, v, mask, is_causal, matrix_core=False, matrix_core_backward=False):
         out, lse = _launch_sdpa_fwd(q, k, v, mask, is_causal, matrix_core)
         ctx.save_for_backward(q, k, v, out, lse, *(() if mask is None else (mask,)))
-        ctx.is_causal = is_causal
+        ctx.is_causal, ctx.matrix_core_backward = is_causal, matrix_core_backward
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
         q, k, v, out, lse, *mask = ctx.saved_tensors
-        dq, dk, dv = sdpa_backward(q, k, v, out, lse, dout, mask[0] if mask else None, ctx.is_causal)
-        return dq, dk, dv, None, None, None
+        dq, dk, dv = sdpa_backward(q, k, v, out, lse, dout, mask[0] if mask else None, ctx.is_causal, ctx.matrix_core_backward)
+        return dq, dk, dv, None, None, None, None
 
 
-def sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, matrix_core: bool | None = None) -> torch.Tensor:
+def sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, matrix_core: bool | None = None,
+         matrix_core_backward: bool | None = None) -> torch.Tensor:
     """``softmax(q k^T / sqrt(D) + mask) v`` per head on the ``[N, L, H, D]`` layout, returned in the same layout.  One launch
     where :func:`sdpa_supported` says so (the forward launch alone when no gradient is asked for);
     ``F.scaled_dot_product_attention`` on the transposed views everywhere else: CPU tensors, float64, autocast, dropout,
@@ -196,16 +219,22 @@ def sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = Fals
 
     ``matrix_core``: True takes the fp32-MFMA forward ``cusrl_sdpa_fwd_mfma`` where :func:`sdpa_mfma_supported` says so and goes
     on as above where it does not; None (the default) reads :func:`matrix_core_attention`, which is off outside the context;
-    False never takes it.  Its results agree with the other forward's to rounding, not to the bit (include/cusrl_hip.h)."""
+    False never takes it.  Its results agree with the other forward's to rounding, not to the bit (include/cusrl_hip.h).
+
+    ``matrix_core_backward``: the same three values for the backward, independent of ``matrix_core`` (either backward takes
+    ``out`` / ``lse`` of either forward): True asks for ``cusrl_sdpa_bwd_mfma`` where it is supported and goes on with
+    ``cusrl_sdpa_bwd`` where not; None reads the context's ``backward`` field; False never takes it."""
     if not sdpa_supported(q, k, v, attn_mask, dropout_p, is_causal):
         return _sdpa_expression(q, k, v, attn_mask, dropout_p, is_causal)
     if matrix_core is None:
         matrix_core = getattr(_matrix_core, "enabled", False)
     matrix_core = bool(matrix_core) and sdpa_mfma_supported(q, k, v, attn_mask, dropout_p, is_causal)
+    if matrix_core_backward is None:
+        matrix_core_backward = getattr(_matrix_core, "backward", False)
     shape = q.shape
     q, k, v = (_one_batch_dimension(t) for t in (q, k, v))
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
-        out = Sdpa.apply(q, k, v, attn_mask, bool(is_causal), matrix_core)
+        out = Sdpa.apply(q, k, v, attn_mask, bool(is_causal), matrix_core, bool(matrix_core_backward))
     else:
         out, _ = _launch_sdpa_fwd(q, k, v, attn_mask, bool(is_causal), matrix_core)
     return out.view(shape)

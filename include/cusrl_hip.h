@@ -1059,6 +1059,26 @@ int cusrl_sdpa_fwd_mfma(const float *q, int64_t q_stride_n, int64_t q_stride_l, 
                         int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q, int64_t mask_stride_k, int causal,
                         float scale, float *out, float *lse, int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D, void *stream);
 int cusrl_sdpa_fwd_mfma_supported(int64_t Lq, int64_t Lk, int64_t D);
+/* cusrl_sdpa_bwd_mfma, TWO launches on the stream (csrc/attention_mfma_bwd.hip): the backward of cusrl_sdpa_bwd - its argument
+ * list, layout, masks, formulas, workspace (delta) and exact zeros (a masked pair, a fully masked query row, a key no query sees) -
+ * on v_mfma_f32_16x16x4_f32.  out and lse may come from either forward.  What differs is the ORDER of the sums.  Over d (the scores,
+ * dout . v): blocks of 16, within a block d = 4 kk + j over the four k slots kk of MFMA j = 0 .. 3.  delta_i: d = 16 t + 4 kk + e as
+ * fmaf chains over (t, e) per kk, then (kk ^ 1 added, then kk ^ 2).  dq_i over keys and dk_j / dv_j over queries: tiles of 32 in
+ * index order, two sub-tiles of 16 each, row 4 kk + j of a sub-tile in slot kk of MFMA j.  So the results agree with
+ * cusrl_sdpa_bwd's to rounding, not to the bit; they are the same bits on every call, one owning lane per element, no atomics; a
+ * dq row's bits depend on its own row of q / dout / out / lse / mask, the keys and D, a dk / dv row's on its own key row, the
+ * queries and D - not on lane, wave, workgroup or batch position.
+ * Supported: cusrl_sdpa_bwd_mfma_supported(Lq, Lk, D) (what cusrl_sdpa_fwd_mfma_supported answers) and the 16-byte rule for q, k,
+ * v, dout - every strided base 16-byte aligned, stride_n and stride_l multiples of 4 - and 16-byte aligned out, dq, dk, dv.
+ * CUSRL_E_INVALID for what cusrl_sdpa_bwd calls invalid; CUSRL_E_UNSUPPORTED for a valid call outside the supported set (another D,
+ * a misaligned view, an extent beyond int64); nothing is launched or written in either case.  N == 0 is a successful no-op. */
+int cusrl_sdpa_bwd_mfma(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n, int64_t k_stride_l,
+                        const float *v, int64_t v_stride_n, int64_t v_stride_l, const float *out, const float *lse, const float *dout,
+                        int64_t dout_stride_n, int64_t dout_stride_l, const uint8_t *keep_mask, const float *bias,
+                        int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q, int64_t mask_stride_k, int causal,
+                        float scale, float *dq, float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t Lk,
+                        int64_t D, void *stream);
+int cusrl_sdpa_bwd_mfma_supported(int64_t Lq, int64_t Lk, int64_t D);
 int cusrl_rope_apply(const float *x, int64_t x_stride_n, int64_t x_stride_l, const float *cos_rows, const float *sin_rows,
                      float *out, int64_t N, int64_t L, int64_t H, int64_t D, int transpose, void *stream);
 

@@ -5,8 +5,13 @@ replayed graph of LAUNCHES launches (host clock around replays that end in a syn
 one process; a line gives the median of each in us per call, the spread (max - min) / median over the rounds, the rate over the
 4 N H L^2 D operations of the two products (half of them under the causal mask) and the verdict: a path counts as faster only where
 the ratio of the medians exceeds 1 + the larger of the two spreads.  The outputs of the two paths are compared first.
+``--backward`` times cusrl_sdpa_bwd_mfma next to cusrl_sdpa_bwd instead (a call is both launches), on the same tensors with the
+``out`` / ``lse`` of one cusrl_sdpa_fwd launch; the rate is over 10 N H L^2 D operations: the five distinct products s, dout . v, dq,
+dk and dv at 2 N H L^2 D apiece, counted once each - the key-major pass computes s and dout . v a second time (seven MFMA products
+in all, 14 N H L^2 D executed), and that recomputation is not counted as useful work.  It also prints each shape's causal /
+unmasked time per path.
 
-    python scripts/sdpa_mfma_bench.py [--rounds 3]
+    python scripts/sdpa_mfma_bench.py [--rounds 3] [--backward]
 """
 import argparse
 import statistics
@@ -19,7 +24,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch  # noqa: E402
 
 from cusrl_amd import ops  # noqa: E402
-from cusrl_amd.ops.attention import _launch_sdpa_fwd  # noqa: E402
+from cusrl_amd.ops.attention import _launch_sdpa_fwd, sdpa_backward  # noqa: E402
 
 SHAPES = ((256, 16, 4, 16), (64, 128, 4, 32), (16, 512, 8, 64), (4, 2048, 8, 128))  # [N, L, H, D]
 CASES = [(shape, mask) for shape in SHAPES for mask in ("none", "causal")] + [((16, 512, 8, 64), "bool")]
@@ -56,7 +61,9 @@ def replay_time(graph, seconds=0.2):
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--rounds", type=int, default=3)
-    rounds = parser.parse_args().rounds
+    parser.add_argument("--backward", action="store_true")
+    args = parser.parse_args()
+    rounds, unmasked = args.rounds, {}
     dev = "cuda:0"
     torch.manual_seed(0)
     for (N, L, H, D), kind in CASES:
@@ -65,9 +72,15 @@ def main():
         causal = kind == "causal"
         assert ops.sdpa_mfma_supported(q, k, v, mask, 0.0, causal)
         paths = {"mfma": lambda: _launch_sdpa_fwd(q, k, v, mask, causal, True), "valu": lambda: _launch_sdpa_fwd(q, k, v, mask, causal, False)}
+        if args.backward:
+            dout, (out, lse) = torch.randn(N, L, H, D, device=dev), paths["valu"]()
+            before = ops._native.launch_counts.get("cusrl_sdpa_bwd_mfma", 0)
+            paths = {"mfma": lambda: sdpa_backward(q, k, v, out, lse, dout, mask, causal, matrix_core=True),
+                     "valu": lambda: sdpa_backward(q, k, v, out, lse, dout, mask, causal)}
         with torch.no_grad():
-            (out_m, lse_m), (out_v, lse_v) = paths["mfma"](), paths["valu"]()
-            differ = float((out_m - out_v).abs().max() / out_v.abs().max())
+            got_m, got_v = paths["mfma"](), paths["valu"]()
+            assert not args.backward or ops._native.launch_counts["cusrl_sdpa_bwd_mfma"] == before + 1
+            differ = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(got_m, got_v) if a.dim() == 4)
             graphs = {path: captured(fn) for path, fn in paths.items()}
             times = {path: [] for path in paths}
             for _ in range(rounds):  # the two paths alternate within a round
@@ -77,10 +90,14 @@ def main():
         spread = {path: (max(times[path]) - min(times[path])) / med[path] for path in paths}
         ratio, noise = med["valu"] / med["mfma"], max(spread.values())
         verdict = "mfma faster" if ratio > 1 + noise else "valu faster" if 1 / ratio > 1 + noise else "within spread"
-        flops = 4.0 * N * H * L * L * D * (0.5 if causal else 1.0)
+        flops = (10.0 if args.backward else 4.0) * N * H * L * L * D * (0.5 if causal else 1.0)
         print(f"[{N:3d},{L:5d},{H:2d},{D:4d}] {kind:6s}  mfma {med['mfma']:9.2f} us (spread {spread['mfma']:5.1%}, {flops / med['mfma'] / 1e6:6.2f} TFLOP/s)  "
               f"valu {med['valu']:9.2f} us (spread {spread['valu']:5.1%}, {flops / med['valu'] / 1e6:6.2f} TFLOP/s)  valu / mfma {ratio:5.2f}  {verdict}"
-              f"  max |out difference| {differ:.1e} of the largest entry", flush=True)
+              f"  max |{'gradient' if args.backward else 'out'} difference| {differ:.1e} of the largest entry", flush=True)
+        if kind == "none":
+            unmasked = med
+        elif kind == "causal":
+            print(f"{'':20s} causal / unmasked: mfma {med['mfma'] / unmasked['mfma']:.2f}  valu {med['valu'] / unmasked['valu']:.2f}", flush=True)
         del graphs
 
 
