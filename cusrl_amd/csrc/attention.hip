@@ -25,7 +25,7 @@
 // The region is dynamic and nothing static sits in front of it.
 #include <type_traits>
 
-#include "attention_common.hpp"  // kOwn, kTile, Rows, Shape, Span, Mask, softmax_step, probability and the host's size rules
+#include "attention_common.hpp"  // kOwn, kTile, Rows, Shape, Span, Mask, Band, softmax_step, probability and the host's size rules
 
 namespace cusrl {
 namespace {
@@ -40,28 +40,7 @@ static_assert(kOwn * kGroup == kBlock, "one lane group per owned row");
 // key tiles that can hold a key visible to a query of q0 ... q0 + kOwn - 1; queries(): the query tiles that can hold a query
 // that sees a key of j0 ... j0 + kOwn - 1.  Every (i, j) outside those spans scores -inf.  kSkipsKeys: whether the key-major
 // pass may be told to start behind key 0 (its key_from); where it may not, key_from is the constant 0 in the kernel.
-// (Mask, the dense one: attention_common.hpp.)
-
-struct Band {  // Lk = Lq + W, the first W keys are the cache, and query i sees keys i ... i + W
-    const uint8_t *valid;  // [N, Lq + W] contiguous, nonzero = a key that exists; or NULL
-    const int32_t *seg;    // [N, Lq] contiguous segment id of every query; the cache is segment 0; or NULL
-    const float *slopes;   // [H] ALiBi slopes; or NULL
-    int64_t W;
-    static constexpr bool kSkipsKeys = true;  // (the cache keys' gradients are not always wanted: key_grad_from)
-
-    // scale * (q . k) - slope[h] * (i + W - j)
-    __device__ __forceinline__ float score(float qk, float scale, int64_t n, int64_t h, int64_t i, int64_t j, int64_t Lq) const {
-        if (j < i || j > i + W) return -INFINITY;
-        if (valid && !valid[n * (Lq + W) + j]) return -INFINITY;
-        if (seg && seg[n * Lq + i] != (j < W ? 0 : seg[n * Lq + j - W])) return -INFINITY;
-        const float s = qk * scale;
-        return slopes ? fmaf(-slopes[h], float(i + W - j), s) : s;  // (one rounding, the same in all four kernels)
-    }
-    // (the last query of the tile sees key q0 + kOwn - 1 + W)
-    __device__ __forceinline__ Span keys(int64_t q0, const Shape &s) const { return {q0, min(s.Lk, q0 + kOwn + W)}; }
-    // (key j is seen by queries j - W ... j)
-    __device__ __forceinline__ Span queries(int64_t j0, const Shape &s) const { return {j0 > W ? j0 - W : 0, min(s.Lq, j0 + kOwn)}; }
-};
+// (Mask, the dense one, and Band, the sliding window: attention_common.hpp.)
 
 __device__ __forceinline__ float group_max(float v) {
 #pragma unroll
@@ -369,14 +348,6 @@ void with_width(bool vec, Launch launch) {
 uint32_t grid_for(int64_t items) { return uint32_t(items < kSdpaMaxBlocks ? items : kSdpaMaxBlocks); }
 
 size_t lds_bytes(int rows, int extra, int D) { return (size_t(rows) * (D | 1) + extra) * sizeof(float); }
-
-bool valid_band_sizes(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
-    return N >= 0 && H >= 1 && Lq >= 1 && W >= 1 && D >= 1 && D <= CUSRL_MAX_SDPA_HEAD_DIM;
-}
-
-bool band_sizes_fit(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
-    return W <= INT64_MAX - Lq && sizes_fit(N, H, Lq, Lq + W, D);
-}
 
 // The launchers take validated sizes with N >= 1 and return the entry's status.
 template <typename Visibility>

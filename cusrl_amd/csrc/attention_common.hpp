@@ -1,7 +1,8 @@
 // What the attention translation units share (attention.hip: the VALU bodies; attention_mfma.hip and attention_mfma_bwd.hip: the
-// fp32-MFMA forward and backward): the operand and shape structs, the dense visibility `Mask` with the two tile constants its spans
-// are written in, the online-softmax step, the backward's `probability`, and the host's size and 16-byte rules.  Moved here from
-// attention.hip as they stood; formulas: include/cusrl_hip.h.
+// dense fp32-MFMA forward and backward; attention_mfma_band.hip: the band's fp32-MFMA forward): the operand and shape structs, the
+// two visibilities `Mask` (dense) and `Band` (sliding window) with the two tile constants their spans are written in, the
+// online-softmax step, the backward's `probability`, and the host's size and 16-byte rules.  Moved here from attention.hip as they
+// stood; formulas: include/cusrl_hip.h.
 #pragma once
 
 #include <math.h>
@@ -55,6 +56,27 @@ struct Mask {  // dense: element strides (n, h, q, k) of the keep-mask or of the
     __device__ __forceinline__ Span queries(int64_t j0, const Shape &s) const { return {causal ? j0 / kTile * kTile : 0, s.Lq}; }
 };
 
+struct Band {  // Lk = Lq + W, the first W keys are the cache, and query i sees keys i ... i + W
+    const uint8_t *valid;  // [N, Lq + W] contiguous, nonzero = a key that exists; or NULL
+    const int32_t *seg;    // [N, Lq] contiguous segment id of every query; the cache is segment 0; or NULL
+    const float *slopes;   // [H] ALiBi slopes; or NULL
+    int64_t W;
+    static constexpr bool kSkipsKeys = true;  // (the cache keys' gradients are not always wanted: key_grad_from)
+
+    // scale * (q . k) - slope[h] * (i + W - j)
+    __device__ __forceinline__ float score(float qk, float scale, int64_t n, int64_t h, int64_t i, int64_t j, int64_t Lq) const {
+        if (j < i || j > i + W) return -INFINITY;
+        if (valid && !valid[n * (Lq + W) + j]) return -INFINITY;
+        if (seg && seg[n * Lq + i] != (j < W ? 0 : seg[n * Lq + j - W])) return -INFINITY;
+        const float s = qk * scale;
+        return slopes ? fmaf(-slopes[h], float(i + W - j), s) : s;  // (one rounding, the same in all four kernels)
+    }
+    // (the last query of the tile sees key q0 + kOwn - 1 + W)
+    __device__ __forceinline__ Span keys(int64_t q0, const Shape &s) const { return {q0, min(s.Lk, q0 + kOwn + W)}; }
+    // (key j is seen by queries j - W ... j)
+    __device__ __forceinline__ Span queries(int64_t j0, const Shape &s) const { return {j0 > W ? j0 - W : 0, min(s.Lq, j0 + kOwn)}; }
+};
+
 // One step of a row's online softmax: m becomes max(m, top), where top is the largest of the step's scores over the whole row
 // group; the scores become exp(score - m) in place (0 for -inf) and the factor that rescales what the row has accumulated
 // so far is returned.  A row that has seen no key yet keeps m = -inf, weights of 0 and a factor of 1.
@@ -93,6 +115,14 @@ inline bool sizes_fit(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {
 
 inline bool valid_sizes(int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {
     return N >= 0 && H >= 1 && Lq >= 1 && Lk >= 1 && D >= 1 && D <= CUSRL_MAX_SDPA_HEAD_DIM;
+}
+
+inline bool valid_band_sizes(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
+    return N >= 0 && H >= 1 && Lq >= 1 && W >= 1 && D >= 1 && D <= CUSRL_MAX_SDPA_HEAD_DIM;
+}
+
+inline bool band_sizes_fit(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D) {
+    return W <= INT64_MAX - Lq && sizes_fit(N, H, Lq, Lq + W, D);
 }
 
 }  // namespace

@@ -12,7 +12,7 @@ import torch
 from cusrl_amd import _native
 from cusrl_amd.ops._common import _checked, _ptr, _stream
 from cusrl_amd.ops.attention import (MAX_SDPA_HEAD_DIM, _backward_operands, _differentiated_inside_double_differentiable, _forward_outputs,
-                                     _rows_arguments, _rows_layout, sdpa)
+                                     _matrix_core, _rows_arguments, _rows_layout, _sixteen_byte_rule, sdpa)
 
 
 def _check_shapes(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from) -> None:
@@ -51,6 +51,17 @@ def band_sdpa_supported(q, k, v, window, key_valid=None, q_segment=None, alibi_s
     return not _differentiated_inside_double_differentiable((q, k, v))
 
 
+def band_sdpa_mfma_supported(q, k, v, window, key_valid=None, q_segment=None, alibi_slopes=None, key_grad_from: int = 0) -> bool:
+    """Does ``cusrl_band_sdpa_fwd_mfma`` take this call right now?  :func:`band_sdpa_supported`, the shapes the library accepts
+    (``cusrl_band_sdpa_fwd_mfma_supported``: ``Lq >= 2``, ``window >= 1``, ``D % 4 == 0``, ``4 <= D <= 128``) and the 16-byte rule
+    on ``q``, ``k``, ``v``: every base 16-byte aligned, ``n`` / ``l`` strides multiples of 4."""
+    if not band_sdpa_supported(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from):
+        return False
+    if not _native.lib().cusrl_band_sdpa_fwd_mfma_supported(q.shape[1], window, q.shape[-1]):
+        return False
+    return _sixteen_byte_rule(q, k, v)
+
+
 def band_mask(q, window: int, key_valid=None, q_segment=None, alibi_slopes=None) -> torch.Tensor:
     """The band as a dense mask for ``ops.sdpa``: a bool keep-mask ``[N, 1, Lq, Lk]``, or with ALiBi one mask ``[N, H, Lq, Lk]``
     of ``q``'s dtype holding the bias, ``-inf`` where a key is not visible."""
@@ -74,12 +85,14 @@ def _side_arguments(key_valid, q_segment, alibi_slopes):
     return _ptr(key_valid), _ptr(q_segment), _ptr(alibi_slopes)
 
 
-def _launch_band_fwd(q, k, v, window, key_valid=None, q_segment=None, alibi_slopes=None):
-    """One ``cusrl_band_sdpa_fwd`` launch: ``(out [N, Lq, H, D], lse [N, H, Lq])``."""
+def _launch_band_fwd(q, k, v, window, key_valid=None, q_segment=None, alibi_slopes=None, matrix_core: bool = False):
+    """One ``cusrl_band_sdpa_fwd`` launch (``matrix_core``: one ``cusrl_band_sdpa_fwd_mfma`` launch, on operands
+    :func:`band_sdpa_mfma_supported` accepted): ``(out [N, Lq, H, D], lse [N, H, Lq])``."""
     N, Lq, H, D = q.shape
     out, lse = _forward_outputs(q)
-    _checked.cusrl_band_sdpa_fwd(*_rows_arguments(q, k, v), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D),
-                                 out.data_ptr(), lse.data_ptr(), N, H, Lq, window, D, _stream())
+    launch = _checked.cusrl_band_sdpa_fwd_mfma if matrix_core else _checked.cusrl_band_sdpa_fwd
+    launch(*_rows_arguments(q, k, v), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D),
+           out.data_ptr(), lse.data_ptr(), N, H, Lq, window, D, _stream())
     return out, lse
 
 
@@ -105,14 +118,16 @@ def _full_rows(grad: torch.Tensor, key_grad_from: int) -> torch.Tensor:
 
 
 class BandSdpa(torch.autograd.Function):
-    """``apply(q, k, v, window, key_valid | None, q_segment | None, alibi_slopes | None, key_grad_from) -> out`` on operands
-    :func:`band_sdpa_supported` accepted: one ``cusrl_band_sdpa_fwd`` launch forward, one ``cusrl_band_sdpa_bwd`` call backward.
+    """``apply(q, k, v, window, key_valid | None, q_segment | None, alibi_slopes | None, key_grad_from[, matrix_core]) -> out`` on
+    operands :func:`band_sdpa_supported` accepted: one ``cusrl_band_sdpa_fwd`` launch forward (``matrix_core``: one
+    ``cusrl_band_sdpa_fwd_mfma`` launch, on operands :func:`band_sdpa_mfma_supported` accepted), one ``cusrl_band_sdpa_bwd`` call
+    backward, whichever forward ran.
     Saved: ``q``, ``k``, ``v``, ``out``, ``lse [N, H, Lq]`` and the three small side tensors — nothing of size ``Lq x Lk``.  The
     gradients of ``k`` and ``v`` are zero in front of ``key_grad_from``."""
 
     @staticmethod
-    def forward(ctx, q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from):
-        out, lse = _launch_band_fwd(q, k, v, window, key_valid, q_segment, alibi_slopes)
+    def forward(ctx, q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from, matrix_core=False):
+        out, lse = _launch_band_fwd(q, k, v, window, key_valid, q_segment, alibi_slopes, matrix_core)
         sides = (key_valid, q_segment, alibi_slopes)
         ctx.save_for_backward(q, k, v, out, lse, *(side for side in sides if side is not None))
         ctx.present = tuple(side is not None for side in sides)
@@ -126,22 +141,31 @@ class BandSdpa(torch.autograd.Function):
         given = iter(given)
         sides = [next(given) if present else None for present in ctx.present]
         dq, dk, dv = band_sdpa_backward(q, k, v, out, lse, dout, ctx.window, *sides, key_grad_from=ctx.key_grad_from)
-        return dq, _full_rows(dk, ctx.key_grad_from), _full_rows(dv, ctx.key_grad_from), None, None, None, None, None
+        return dq, _full_rows(dk, ctx.key_grad_from), _full_rows(dv, ctx.key_grad_from), None, None, None, None, None, None
 
 
-def band_sdpa(q, k, v, window: int, key_valid=None, q_segment=None, alibi_slopes=None, key_grad_from: int = 0) -> torch.Tensor:
+def band_sdpa(q, k, v, window: int, key_valid=None, q_segment=None, alibi_slopes=None, key_grad_from: int = 0,
+              matrix_core: bool | None = None) -> torch.Tensor:
     """Causal sliding-window attention of ``q [N, Lq, H, D]`` over ``k``, ``v`` ``[N, Lq + window, H, D]``, returned as
     ``[N, Lq, H, D]``: query ``i`` sees key ``j`` iff ``i <= j <= i + window``, ``key_valid[n, j]`` and the segment of ``i`` is
     that of ``j`` (``q_segment[n, j - window]``, 0 for the cache); ``alibi_slopes[h] * (i + window - j)`` is taken off the
     scaled score.  Keys in front of ``key_grad_from`` get no gradient.  One launch where :func:`band_sdpa_supported` says so
     (the forward launch alone when no gradient is asked for); everywhere else — CPU tensors, float64, other dtypes, autocast,
-    ``D`` beyond the kernel's — the dense mask of :func:`band_mask` through ``ops.sdpa``."""
+    ``D`` beyond the kernel's — the dense mask of :func:`band_mask` through ``ops.sdpa``.
+
+    ``matrix_core``: True takes the fp32-MFMA forward ``cusrl_band_sdpa_fwd_mfma`` where :func:`band_sdpa_mfma_supported` says so
+    and goes on with ``cusrl_band_sdpa_fwd`` where it does not; None (the default) reads the ``enabled`` field of
+    ``ops.matrix_core_attention()``, which is off outside the context; False never takes it.  Its results agree with the other
+    forward's to rounding, not to the bit (include/cusrl_hip.h); the backward is ``cusrl_band_sdpa_bwd`` either way."""
     _check_shapes(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from)
     if not band_sdpa_supported(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from):
         if key_grad_from > 0 and (k.requires_grad or v.requires_grad):
             k = torch.cat([k[:, :key_grad_from].detach(), k[:, key_grad_from:]], dim=1)
             v = torch.cat([v[:, :key_grad_from].detach(), v[:, key_grad_from:]], dim=1)
         return sdpa(q, k, v, attn_mask=band_mask(q, window, key_valid, q_segment, alibi_slopes))
+    if matrix_core is None:
+        matrix_core = getattr(_matrix_core, "enabled", False)
+    matrix_core = bool(matrix_core) and band_sdpa_mfma_supported(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
-        return BandSdpa.apply(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from)
-    return _launch_band_fwd(q, k, v, window, key_valid, q_segment, alibi_slopes)[0]
+        return BandSdpa.apply(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from, matrix_core)
+    return _launch_band_fwd(q, k, v, window, key_valid, q_segment, alibi_slopes, matrix_core)[0]

@@ -1119,6 +1119,24 @@ int cusrl_band_sdpa_bwd(const float *q, int64_t q_stride_n, int64_t q_stride_l, 
                         float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D,
                         void *stream);
 int64_t cusrl_band_sdpa_bwd_workspace(int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D);
+/* cusrl_band_sdpa_fwd_mfma, ONE launch (csrc/attention_mfma_band.hip): the forward of cusrl_band_sdpa_fwd - its argument list,
+ * layout, visibility, formulas for out and lse, and its handling of a query with no visible key - on v_mfma_f32_16x16x4_f32, for
+ * Lq >= 2.  out and lse feed cusrl_band_sdpa_bwd as cusrl_band_sdpa_fwd's do.  One wave owns 16 queries q0 .. q0 + 15 and reads the
+ * 16-key sub-tiles from q0 up to min(Lk, q0 + 16 + W) straight from global memory.  What differs is the ORDER of the two sums: the
+ * score's sum over d runs in blocks of 16, within a block d = 4 kk + j over the four k slots kk of MFMA j = 0 .. 3; the sum over keys
+ * runs in sub-tiles of 16 keys from q0, key 4 kk + j in slot kk of MFMA j.  So the results agree with cusrl_band_sdpa_fwd's to
+ * rounding, not to the bit; they are the same bits on every call, and a query row's bits do not depend on its lane, wave, workgroup,
+ * batch position or Lq.
+ * Supported: cusrl_band_sdpa_fwd_mfma_supported(Lq, W, D) (nonzero for Lq >= 2, W >= 1 and D % 4 == 0, 4 <= D <= 128; Lq == 1 stays
+ * with cusrl_band_sdpa_fwd's step kernel) and the 16-byte rule for q, k, v - every strided base 16-byte aligned, stride_n and
+ * stride_l multiples of 4 - and a 16-byte aligned out.  CUSRL_E_INVALID for what cusrl_band_sdpa_fwd calls invalid;
+ * CUSRL_E_UNSUPPORTED for a valid call outside the supported set (Lq == 1, another D, a misaligned view, an extent beyond int64);
+ * nothing is launched or written in either case.  N == 0 is a successful no-op. */
+int cusrl_band_sdpa_fwd_mfma(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                             int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *key_valid,
+                             const int32_t *q_segment, const float *alibi_slopes, float scale, float *out, float *lse, int64_t N,
+                             int64_t H, int64_t Lq, int64_t W, int64_t D, void *stream);
+int cusrl_band_sdpa_fwd_mfma_supported(int64_t Lq, int64_t W, int64_t D);
 
 /* ---- depthwise 2-D convolution — the spatial half of cusrl/nn/layer/separable_conv.py:52-64, an nn.Conv2d with
  * groups == in_channels == out_channels and zero padding (additive entries of ABI 7; csrc/conv.hip).  fp32, contiguous:

@@ -10,8 +10,11 @@ the ratio of the medians exceeds 1 + the larger of the two spreads.  The outputs
 dk and dv at 2 N H L^2 D apiece, counted once each - the key-major pass computes s and dout . v a second time (seven MFMA products
 in all, 14 N H L^2 D executed), and that recomputation is not counted as useful work.  It also prints each shape's causal /
 unmasked time per path.
+``--band`` times cusrl_band_sdpa_fwd_mfma next to cusrl_band_sdpa_fwd instead, through the ops' launch function on the same tensors:
+``q [N, L, H, D]`` against the two slices of a packed ``[N, L + W, 2, H, D]`` projection, with a key-validity row, segment ids and
+ALiBi slopes; the rate is over the 4 N H L (W + 1) D operations of the pairs inside the band.
 
-    python scripts/sdpa_mfma_bench.py [--rounds 3] [--backward]
+    python scripts/sdpa_mfma_bench.py [--rounds 3] [--backward | --band]
 """
 import argparse
 import statistics
@@ -25,9 +28,12 @@ import torch  # noqa: E402
 
 from cusrl_amd import ops  # noqa: E402
 from cusrl_amd.ops.attention import _launch_sdpa_fwd, sdpa_backward  # noqa: E402
+from cusrl_amd.ops.band_attention import _launch_band_fwd  # noqa: E402
 
 SHAPES = ((256, 16, 4, 16), (64, 128, 4, 32), (16, 512, 8, 64), (4, 2048, 8, 128))  # [N, L, H, D]
 CASES = [(shape, mask) for shape in SHAPES for mask in ("none", "causal")] + [((16, 512, 8, 64), "bool")]
+# the band: the training shape of the causal transformer backbone at two batch sizes, then long sequences against the window
+BAND_CASES = (((256, 24, 4, 16), 16), ((65536, 24, 4, 16), 16), ((64, 512, 8, 64), 64), ((16, 2048, 8, 128), 128))  # ([N, L, H, D], W)
 LAUNCHES = 10
 
 
@@ -58,11 +64,51 @@ def replay_time(graph, seconds=0.2):
     return elapsed / replays / LAUNCHES * 1e6
 
 
+def alternate(paths, rounds):
+    """Median us per call and spread (max - min) / median of each path, the paths alternating within a round."""
+    graphs = {path: captured(fn) for path, fn in paths.items()}
+    times = {path: [] for path in paths}
+    for _ in range(rounds):
+        for path in paths:
+            times[path].append(replay_time(graphs[path]))
+    med = {path: statistics.median(times[path]) for path in paths}
+    return med, {path: (max(times[path]) - min(times[path])) / med[path] for path in paths}
+
+
+def band(rounds, dev="cuda:0"):
+    torch.manual_seed(0)
+    for (N, L, H, D), W in BAND_CASES:
+        q = torch.randn(N, L, H, D, device=dev)
+        k, v = torch.randn(N, L + W, 2, H, D, device=dev).unbind(dim=2)  # the slices of a packed projection, read where they are
+        valid = torch.rand(N, L + W, device=dev) < 0.9
+        valid[:, W:] = True  # (every query keeps its own token)
+        segment = (torch.rand(N, L, device=dev) < 0.05).cumsum(1).int()
+        slopes = torch.tensor([0.5 ** (h + 1) for h in range(H)], device=dev)
+        assert ops.band_sdpa_mfma_supported(q, k, v, W, valid, segment, slopes)
+        paths = {"mfma": lambda: _launch_band_fwd(q, k, v, W, valid, segment, slopes, True),
+                 "valu": lambda: _launch_band_fwd(q, k, v, W, valid, segment, slopes, False)}
+        with torch.no_grad():
+            before = ops._native.launch_counts.get("cusrl_band_sdpa_fwd_mfma", 0)
+            (got_m, _), (got_v, _) = paths["mfma"](), paths["valu"]()
+            assert ops._native.launch_counts["cusrl_band_sdpa_fwd_mfma"] == before + 1
+            differ = float((got_m - got_v).abs().max() / got_v.abs().max())
+            med, spread = alternate(paths, rounds)
+        ratio, noise = med["valu"] / med["mfma"], max(spread.values())
+        verdict = "mfma faster" if ratio > 1 + noise else "valu faster" if 1 / ratio > 1 + noise else "within spread"
+        flops = 4.0 * N * H * L * (W + 1) * D
+        print(f"[{N:5d},{L:5d},{H:2d},{D:4d}] W {W:3d}  mfma {med['mfma']:9.2f} us (spread {spread['mfma']:5.1%}, {flops / med['mfma'] / 1e6:6.2f} TFLOP/s)  "
+              f"valu {med['valu']:9.2f} us (spread {spread['valu']:5.1%}, {flops / med['valu'] / 1e6:6.2f} TFLOP/s)  valu / mfma {ratio:5.2f}  {verdict}"
+              f"  max |out difference| {differ:.1e} of the largest entry", flush=True)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--rounds", type=int, default=3)
     parser.add_argument("--backward", action="store_true")
+    parser.add_argument("--band", action="store_true")
     args = parser.parse_args()
+    if args.band:
+        return band(args.rounds)
     rounds, unmasked = args.rounds, {}
     dev = "cuda:0"
     torch.manual_seed(0)
@@ -81,13 +127,7 @@ def main():
             got_m, got_v = paths["mfma"](), paths["valu"]()
             assert not args.backward or ops._native.launch_counts["cusrl_sdpa_bwd_mfma"] == before + 1
             differ = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(got_m, got_v) if a.dim() == 4)
-            graphs = {path: captured(fn) for path, fn in paths.items()}
-            times = {path: [] for path in paths}
-            for _ in range(rounds):  # the two paths alternate within a round
-                for path in paths:
-                    times[path].append(replay_time(graphs[path]))
-        med = {path: statistics.median(times[path]) for path in paths}
-        spread = {path: (max(times[path]) - min(times[path])) / med[path] for path in paths}
+            med, spread = alternate(paths, rounds)
         ratio, noise = med["valu"] / med["mfma"], max(spread.values())
         verdict = "mfma faster" if ratio > 1 + noise else "valu faster" if 1 / ratio > 1 + noise else "within spread"
         flops = (10.0 if args.backward else 4.0) * N * H * L * L * D * (0.5 if causal else 1.0)
@@ -98,7 +138,6 @@ def main():
             unmasked = med
         elif kind == "causal":
             print(f"{'':20s} causal / unmasked: mfma {med['mfma'] / unmasked['mfma']:.2f}  valu {med['valu'] / unmasked['valu']:.2f}", flush=True)
-        del graphs
 
 
 if __name__ == "__main__":
