@@ -62,6 +62,17 @@ def band_sdpa_mfma_supported(q, k, v, window, key_valid=None, q_segment=None, al
     return _sixteen_byte_rule(q, k, v)
 
 
+def band_sdpa_bwd_mfma_supported(q, k, v, window, key_valid=None, q_segment=None, alibi_slopes=None, key_grad_from: int = 0) -> bool:
+    """Does ``cusrl_band_sdpa_bwd_mfma`` take the backward of this call?  What :func:`band_sdpa_mfma_supported` asks, with the
+    library's ``cusrl_band_sdpa_bwd_mfma_supported``; ``out`` and ``dout`` are held to the 16-byte rule when they arrive
+    (:func:`band_sdpa_backward`)."""
+    if not band_sdpa_supported(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from):
+        return False
+    if not _native.lib().cusrl_band_sdpa_bwd_mfma_supported(q.shape[1], window, q.shape[-1]):
+        return False
+    return _sixteen_byte_rule(q, k, v)
+
+
 def band_mask(q, window: int, key_valid=None, q_segment=None, alibi_slopes=None) -> torch.Tensor:
     """The band as a dense mask for ``ops.sdpa``: a bool keep-mask ``[N, 1, Lq, Lk]``, or with ALiBi one mask ``[N, H, Lq, Lk]``
     of ``q``'s dtype holding the bias, ``-inf`` where a key is not visible."""
@@ -96,15 +107,22 @@ def _launch_band_fwd(q, k, v, window, key_valid=None, q_segment=None, alibi_slop
     return out, lse
 
 
-def band_sdpa_backward(q, k, v, out, lse, dout, window, key_valid=None, q_segment=None, alibi_slopes=None, key_grad_from: int = 0):
+def band_sdpa_backward(q, k, v, out, lse, dout, window, key_valid=None, q_segment=None, alibi_slopes=None, key_grad_from: int = 0,
+                       matrix_core: bool = False):
     """The ``cusrl_band_sdpa_bwd`` call by itself: ``(dq [N, Lq, H, D], dk, dv [N, Lk - key_grad_from, H, D])``, contiguous; row
-    ``j - key_grad_from`` of ``dk`` / ``dv`` is key ``j``'s, and the keys in front of ``key_grad_from`` are not visited."""
+    ``j - key_grad_from`` of ``dk`` / ``dv`` is key ``j``'s, and the keys in front of ``key_grad_from`` are not visited.  ``out``
+    and ``lse`` are the forward's — either forward's.  ``matrix_core``: the ``cusrl_band_sdpa_bwd_mfma`` call in its place where the
+    library takes the shapes and ``q``, ``k``, ``v``, ``out`` and ``dout`` (after the rows-layout copy) pass the 16-byte rule;
+    ``cusrl_band_sdpa_bwd`` where not."""
     N, Lq, H, D = q.shape
     dout, dq, dk, dv, workspace = _backward_operands(q, dout, Lq + window - key_grad_from,
                                                      _native.lib().cusrl_band_sdpa_bwd_workspace(N, H, Lq, window, D))
-    _checked.cusrl_band_sdpa_bwd(*_rows_arguments(q, k, v), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D),
-                                 out.data_ptr(), lse.data_ptr(), *_rows_arguments(dout), key_grad_from, dq.data_ptr(), dk.data_ptr(),
-                                 dv.data_ptr(), workspace.data_ptr(), N, H, Lq, window, D, _stream())
+    matrix_core = (bool(matrix_core) and _native.lib().cusrl_band_sdpa_bwd_mfma_supported(Lq, window, D)
+                   and _sixteen_byte_rule(q, k, v, out, dout))
+    launch = _checked.cusrl_band_sdpa_bwd_mfma if matrix_core else _checked.cusrl_band_sdpa_bwd
+    launch(*_rows_arguments(q, k, v), *_side_arguments(key_valid, q_segment, alibi_slopes), 1.0 / math.sqrt(D), out.data_ptr(),
+           lse.data_ptr(), *_rows_arguments(dout), key_grad_from, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), workspace.data_ptr(),
+           N, H, Lq, window, D, _stream())
     return dq, dk, dv
 
 
@@ -118,20 +136,21 @@ def _full_rows(grad: torch.Tensor, key_grad_from: int) -> torch.Tensor:
 
 
 class BandSdpa(torch.autograd.Function):
-    """``apply(q, k, v, window, key_valid | None, q_segment | None, alibi_slopes | None, key_grad_from[, matrix_core]) -> out`` on
-    operands :func:`band_sdpa_supported` accepted: one ``cusrl_band_sdpa_fwd`` launch forward (``matrix_core``: one
-    ``cusrl_band_sdpa_fwd_mfma`` launch, on operands :func:`band_sdpa_mfma_supported` accepted), one ``cusrl_band_sdpa_bwd`` call
-    backward, whichever forward ran.
+    """``apply(q, k, v, window, key_valid | None, q_segment | None, alibi_slopes | None, key_grad_from[, matrix_core[,
+    matrix_core_backward]]) -> out`` on operands :func:`band_sdpa_supported` accepted: one ``cusrl_band_sdpa_fwd`` launch forward
+    (``matrix_core``: one ``cusrl_band_sdpa_fwd_mfma`` launch, on operands :func:`band_sdpa_mfma_supported` accepted), one
+    ``cusrl_band_sdpa_bwd`` call backward, whichever forward ran (``matrix_core_backward``: one ``cusrl_band_sdpa_bwd_mfma`` call
+    where :func:`band_sdpa_backward` finds the operands fit, decided per call when ``dout`` arrives).
     Saved: ``q``, ``k``, ``v``, ``out``, ``lse [N, H, Lq]`` and the three small side tensors — nothing of size ``Lq x Lk``.  The
     gradients of ``k`` and ``v`` are zero in front of ``key_grad_from``."""
 
     @staticmethod
-    def forward(ctx, q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from, matrix_core=False):
+    def forward(ctx, q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from, matrix_core=False, matrix_core_backward=False):
         out, lse = _launch_band_fwd(q, k, v, window, key_valid, q_segment, alibi_slopes, matrix_core)
         sides = (key_valid, q_segment, alibi_slopes)
         ctx.save_for_backward(q, k, v, out, lse, *(side for side in sides if side is not None))
         ctx.present = tuple(side is not None for side in sides)
-        ctx.window, ctx.key_grad_from = window, key_grad_from
+        ctx.window, ctx.key_grad_from, ctx.matrix_core_backward = window, key_grad_from, matrix_core_backward
         return out
 
     @staticmethod
@@ -140,12 +159,13 @@ class BandSdpa(torch.autograd.Function):
         q, k, v, out, lse, *given = ctx.saved_tensors
         given = iter(given)
         sides = [next(given) if present else None for present in ctx.present]
-        dq, dk, dv = band_sdpa_backward(q, k, v, out, lse, dout, ctx.window, *sides, key_grad_from=ctx.key_grad_from)
-        return dq, _full_rows(dk, ctx.key_grad_from), _full_rows(dv, ctx.key_grad_from), None, None, None, None, None, None
+        dq, dk, dv = band_sdpa_backward(q, k, v, out, lse, dout, ctx.window, *sides, key_grad_from=ctx.key_grad_from,
+                                        matrix_core=ctx.matrix_core_backward)
+        return dq, _full_rows(dk, ctx.key_grad_from), _full_rows(dv, ctx.key_grad_from), None, None, None, None, None, None, None
 
 
 def band_sdpa(q, k, v, window: int, key_valid=None, q_segment=None, alibi_slopes=None, key_grad_from: int = 0,
-              matrix_core: bool | None = None) -> torch.Tensor:
+              matrix_core: bool | None = None, matrix_core_backward: bool | None = None) -> torch.Tensor:
     """Causal sliding-window attention of ``q [N, Lq, H, D]`` over ``k``, ``v`` ``[N, Lq + window, H, D]``, returned as
     ``[N, Lq, H, D]``: query ``i`` sees key ``j`` iff ``i <= j <= i + window``, ``key_valid[n, j]`` and the segment of ``i`` is
     that of ``j`` (``q_segment[n, j - window]``, 0 for the cache); ``alibi_slopes[h] * (i + window - j)`` is taken off the
@@ -156,7 +176,11 @@ def band_sdpa(q, k, v, window: int, key_valid=None, q_segment=None, alibi_slopes
     ``matrix_core``: True takes the fp32-MFMA forward ``cusrl_band_sdpa_fwd_mfma`` where :func:`band_sdpa_mfma_supported` says so
     and goes on with ``cusrl_band_sdpa_fwd`` where it does not; None (the default) reads the ``enabled`` field of
     ``ops.matrix_core_attention()``, which is off outside the context; False never takes it.  Its results agree with the other
-    forward's to rounding, not to the bit (include/cusrl_hip.h); the backward is ``cusrl_band_sdpa_bwd`` either way."""
+    forward's to rounding, not to the bit (include/cusrl_hip.h).
+
+    ``matrix_core_backward``: the same three values for the backward, independent of ``matrix_core`` (either backward takes
+    ``out`` / ``lse`` of either forward): True asks for ``cusrl_band_sdpa_bwd_mfma`` where it is supported and goes on with
+    ``cusrl_band_sdpa_bwd`` where not; None reads the context's ``backward`` field; False never takes it."""
     _check_shapes(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from)
     if not band_sdpa_supported(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from):
         if key_grad_from > 0 and (k.requires_grad or v.requires_grad):
@@ -166,6 +190,8 @@ def band_sdpa(q, k, v, window: int, key_valid=None, q_segment=None, alibi_slopes
     if matrix_core is None:
         matrix_core = getattr(_matrix_core, "enabled", False)
     matrix_core = bool(matrix_core) and band_sdpa_mfma_supported(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from)
+    if matrix_core_backward is None:
+        matrix_core_backward = getattr(_matrix_core, "backward", False)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
-        return BandSdpa.apply(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from, matrix_core)
+        return BandSdpa.apply(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from, matrix_core, bool(matrix_core_backward))
     return _launch_band_fwd(q, k, v, window, key_valid, q_segment, alibi_slopes, matrix_core)[0]

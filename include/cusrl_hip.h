@@ -1137,6 +1137,31 @@ int cusrl_band_sdpa_fwd_mfma(const float *q, int64_t q_stride_n, int64_t q_strid
                              const int32_t *q_segment, const float *alibi_slopes, float scale, float *out, float *lse, int64_t N,
                              int64_t H, int64_t Lq, int64_t W, int64_t D, void *stream);
 int cusrl_band_sdpa_fwd_mfma_supported(int64_t Lq, int64_t W, int64_t D);
+/* cusrl_band_sdpa_bwd_mfma, TWO launches on the stream (csrc/attention_mfma_band_bwd.hip): the backward of cusrl_band_sdpa_bwd - its
+ * argument list, layout, visibility, formulas, workspace (delta, cusrl_band_sdpa_bwd_workspace floats), key_grad_from and exact zeros
+ * (a masked pair, a query with no visible key, a key no query sees) - on v_mfma_f32_16x16x4_f32, for Lq >= 2.  out and lse may come
+ * from either forward.  One wave owns 16 rows and reads only its own span straight from global memory: the query-major launch (dq,
+ * delta) the 16-key sub-tiles from q0 up to min(Lk, q0 + 16 + W), the key-major launch (dk, dv) the 16-query sub-tiles from
+ * max(0, j0 - W) up to min(Lq, j0 + 16) with j0 = key_grad_from + 16 tile.  What differs is the ORDER of the sums.  Over d (the
+ * scores, dout . v): blocks of 16, within a block d = 4 kk + j over the four k slots kk of MFMA j = 0 .. 3.  delta_i:
+ * d = 16 t + 4 kk + e as fmaf chains over (t, e) per kk, then (kk ^ 1 added, then kk ^ 2).  dq_i over keys and dk_j / dv_j over
+ * queries: sub-tiles of 16 from the span's begin, row 4 kk + j of a sub-tile in slot kk of MFMA j.  So the results agree with
+ * cusrl_band_sdpa_bwd's to rounding, not to the bit; they are the same bits on every call, one owning lane per element, no atomics.
+ * A dq row's bits do not depend on its lane, wave, workgroup, batch position or Lq.  A dk / dv row's bits do not depend on lane,
+ * wave, workgroup or batch position, but MAY depend on key_grad_from: it moves the key's place in its 16-key tile and the start of
+ * the query sub-tiles, and with them the order of the sum over queries.
+ * Supported: cusrl_band_sdpa_bwd_mfma_supported(Lq, W, D) (what cusrl_band_sdpa_fwd_mfma_supported answers; Lq == 1 stays with
+ * cusrl_band_sdpa_bwd) and the 16-byte rule for q, k, v, dout - every strided base 16-byte aligned, stride_n and stride_l multiples
+ * of 4 - and 16-byte aligned out, dq, dk, dv.  CUSRL_E_INVALID for what cusrl_band_sdpa_bwd calls invalid (key_grad_from outside
+ * 0 .. W included); CUSRL_E_UNSUPPORTED for a valid call outside the supported set (Lq == 1, another D, a misaligned view, an extent
+ * beyond int64); nothing is launched or written in either case.  N == 0 is a successful no-op. */
+int cusrl_band_sdpa_bwd_mfma(const float *q, int64_t q_stride_n, int64_t q_stride_l, const float *k, int64_t k_stride_n,
+                             int64_t k_stride_l, const float *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *key_valid,
+                             const int32_t *q_segment, const float *alibi_slopes, float scale, const float *out, const float *lse,
+                             const float *dout, int64_t dout_stride_n, int64_t dout_stride_l, int64_t key_grad_from, float *dq,
+                             float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D,
+                             void *stream);
+int cusrl_band_sdpa_bwd_mfma_supported(int64_t Lq, int64_t W, int64_t D);
 
 /* ---- depthwise 2-D convolution — the spatial half of cusrl/nn/layer/separable_conv.py:52-64, an nn.Conv2d with
  * groups == in_channels == out_channels and zero padding (additive entries of ABI 7; csrc/conv.hip).  fp32, contiguous:

@@ -13,8 +13,12 @@ unmasked time per path.
 ``--band`` times cusrl_band_sdpa_fwd_mfma next to cusrl_band_sdpa_fwd instead, through the ops' launch function on the same tensors:
 ``q [N, L, H, D]`` against the two slices of a packed ``[N, L + W, 2, H, D]`` projection, with a key-validity row, segment ids and
 ALiBi slopes; the rate is over the 4 N H L (W + 1) D operations of the pairs inside the band.
+``--band --backward`` times cusrl_band_sdpa_bwd_mfma next to cusrl_band_sdpa_bwd (a call is both launches) on those tensors with the
+``out`` / ``lse`` of one cusrl_band_sdpa_fwd launch and ``key_grad_from = W`` (what nn/causal_attn.py passes with a detached cache),
+plus one line with ``key_grad_from = 0``; the rate is over 10 N H L (W + 1) D operations, the five distinct products inside the band
+counted once each as in ``--backward``.
 
-    python scripts/sdpa_mfma_bench.py [--rounds 3] [--backward | --band]
+    python scripts/sdpa_mfma_bench.py [--rounds 3] [--backward] [--band]
 """
 import argparse
 import statistics
@@ -28,7 +32,7 @@ import torch  # noqa: E402
 
 from cusrl_amd import ops  # noqa: E402
 from cusrl_amd.ops.attention import _launch_sdpa_fwd, sdpa_backward  # noqa: E402
-from cusrl_amd.ops.band_attention import _launch_band_fwd  # noqa: E402
+from cusrl_amd.ops.band_attention import _launch_band_fwd, band_sdpa_backward  # noqa: E402
 
 SHAPES = ((256, 16, 4, 16), (64, 128, 4, 32), (16, 512, 8, 64), (4, 2048, 8, 128))  # [N, L, H, D]
 CASES = [(shape, mask) for shape in SHAPES for mask in ("none", "causal")] + [((16, 512, 8, 64), "bool")]
@@ -75,6 +79,34 @@ def alternate(paths, rounds):
     return med, {path: (max(times[path]) - min(times[path])) / med[path] for path in paths}
 
 
+def band_backward(rounds, dev="cuda:0"):
+    torch.manual_seed(0)
+    for ((N, L, H, D), W), start in [(case, case[1]) for case in BAND_CASES] + [(BAND_CASES[0], 0)]:
+        q, dout = torch.randn(N, L, H, D, device=dev), torch.randn(N, L, H, D, device=dev)
+        k, v = torch.randn(N, L + W, 2, H, D, device=dev).unbind(dim=2)  # the slices of a packed projection, read where they are
+        valid = torch.rand(N, L + W, device=dev) < 0.9
+        valid[:, W:] = True  # (every query keeps its own token)
+        segment = (torch.rand(N, L, device=dev) < 0.05).cumsum(1).int()
+        slopes = torch.tensor([0.5 ** (h + 1) for h in range(H)], device=dev)
+        assert ops.band_sdpa_bwd_mfma_supported(q, k, v, W, valid, segment, slopes, start)
+        with torch.no_grad():
+            out, lse = _launch_band_fwd(q, k, v, W, valid, segment, slopes, False)
+            paths = {"mfma": lambda: band_sdpa_backward(q, k, v, out, lse, dout, W, valid, segment, slopes, start, matrix_core=True),
+                     "valu": lambda: band_sdpa_backward(q, k, v, out, lse, dout, W, valid, segment, slopes, start)}
+            before = ops._native.launch_counts.get("cusrl_band_sdpa_bwd_mfma", 0)
+            got_m, got_v = paths["mfma"](), paths["valu"]()
+            assert ops._native.launch_counts["cusrl_band_sdpa_bwd_mfma"] == before + 1
+            differ = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(got_m, got_v))
+            del got_m, got_v
+            med, spread = alternate(paths, rounds)
+        ratio, noise = med["valu"] / med["mfma"], max(spread.values())
+        verdict = "mfma faster" if ratio > 1 + noise else "valu faster" if 1 / ratio > 1 + noise else "within spread"
+        flops = 10.0 * N * H * L * (W + 1) * D
+        print(f"[{N:5d},{L:5d},{H:2d},{D:4d}] W {W:3d} from {start:3d}  mfma {med['mfma']:9.2f} us (spread {spread['mfma']:5.1%}, {flops / med['mfma'] / 1e6:6.2f} TFLOP/s)  "
+              f"valu {med['valu']:9.2f} us (spread {spread['valu']:5.1%}, {flops / med['valu'] / 1e6:6.2f} TFLOP/s)  valu / mfma {ratio:5.2f}  {verdict}"
+              f"  max |gradient difference| {differ:.1e} of the largest entry", flush=True)
+
+
 def band(rounds, dev="cuda:0"):
     torch.manual_seed(0)
     for (N, L, H, D), W in BAND_CASES:
@@ -108,7 +140,7 @@ def main():
     parser.add_argument("--band", action="store_true")
     args = parser.parse_args()
     if args.band:
-        return band(args.rounds)
+        return band_backward(args.rounds) if args.backward else band(args.rounds)
     rounds, unmasked = args.rounds, {}
     dev = "cuda:0"
     torch.manual_seed(0)
