@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "recurrent_cell.hpp"  // gru_sigmoid, gru_gates, gru_next, lstm_next: shared with recurrent_step.hip
 
 namespace cusrl {
 
@@ -76,22 +77,6 @@ __device__ __forceinline__ bool row_live(const int64_t *__restrict__ lengths, in
     return !lengths || t < lengths[b];
 }
 
-__device__ __forceinline__ float gru_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-struct GruGates {
-    float r, z, q, n;
-};
-
-__device__ __forceinline__ GruGates gru_gates(float gi_r, float gi_z, float gi_n, float gh_r, float gh_z, float gh_n,
-                                              float b_r, float b_z, float b_n) {
-    GruGates g;
-    g.r = gru_sigmoid(gi_r + gh_r + b_r);
-    g.z = gru_sigmoid(gi_z + gh_z + b_z);
-    g.q = gh_n + b_n;
-    g.n = tanhf(gi_n + g.r * g.q);
-    return g;
-}
-
 // b_hh = {b_hr, b_hz, b_hn} at columns [j, j + kW); zeros without a bias
 template <typename V>
 struct GruBias {
@@ -125,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void gru_gates_fwd_kernel(const float *__re
 #pragma unroll
     for (int k = 0; k < L::kW; ++k) {
         const GruGates g = gru_gates(gir[k], giz[k], gin[k], ghr[k], ghz[k], ghn[k], bias.r[k], bias.z[k], bias.n[k]);
-        const float next = (1.0f - g.z) * g.n + g.z * hp[k];
+        const float next = gru_next(g, hp[k]);
         hn[k] = live ? next : hp[k];
         o[k] = live ? next : 0.0f;
     }
@@ -293,11 +278,10 @@ __global__ __launch_bounds__(kBlock) void lstm_gates_fwd_kernel(float *__restric
     L hn, cn, o;
 #pragma unroll
     for (int k = 0; k < L::kW; ++k) {
-        const float c_next = gru_sigmoid(pre[1][k]) * cp[k] + gru_sigmoid(pre[0][k]) * tanhf(pre[2][k]);
-        const float h_next = gru_sigmoid(pre[3][k]) * tanhf(c_next);
-        cn[k] = live ? c_next : cp[k];
-        hn[k] = live ? h_next : hp[k];
-        o[k] = live ? h_next : 0.0f;
+        const LstmState next = lstm_next(pre[0][k], pre[1][k], pre[2][k], pre[3][k], cp[k]);
+        cn[k] = live ? next.c : cp[k];
+        hn[k] = live ? next.h : hp[k];
+        o[k] = live ? next.h : 0.0f;
     }
     hn.store(h + b * H + j);
     cn.store(c + b * H + j);

@@ -26,6 +26,7 @@
 //
 // Activations with the expressions of cusrl_bias_act (act4, mlp_tail.hpp); fp32 MFMA accumulation as in the library's GEMMs.
 #include "mlp_tail.hpp"
+#include "quad_load.hpp"  // quad_load / quad_select: the two read paths
 
 // waves per workgroup (independent of each other; a build with 4 is the alternative DESIGN.md §7 names as not yet timed)
 #ifndef CUSRL_MLP2_WAVE_GROUP
@@ -49,18 +50,6 @@ struct Mlp2WaveArgs {
     float alpha;
     int wide;  // x and w1 are read 16 bytes at a time
 };
-
-// columns k .. k + 3 of row `row` of a [*, K] matrix, UNSELECTED: every address is clamped into the row (column 0 for k >= K),
-// so that the load can stay in flight; quad_select zeroes what lies at k >= K when the value is used
-__device__ __forceinline__ float4 quad_load(const float *base, int64_t row, int K, int k, bool wide) {
-    const float *at = base + row * K;
-    if (wide) return *reinterpret_cast<const float4 *>(at + (k < K ? k : 0));  // (K % 4 == 0: the quad is live or dead as a whole)
-    return make_float4(at[k < K ? k : 0], at[k + 1 < K ? k + 1 : 0], at[k + 2 < K ? k + 2 : 0], at[k + 3 < K ? k + 3 : 0]);
-}
-
-__device__ __forceinline__ float4 quad_select(const float4 &v, int K, int k) {
-    return make_float4(k < K ? v.x : 0.f, k + 1 < K ? v.y : 0.f, k + 2 < K ? v.z : 0.f, k + 3 < K ? v.w : 0.f);
-}
 
 // NT1 / NT2: 16-feature tiles of the first / second hidden layer (H = 16 NT); KB: 16-wide k-blocks of the input (K <= 16 KB).
 template <int ACT, int NT1, int NT2, int KB>

@@ -8,8 +8,10 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Any
 
+import torch
 from torch import Tensor, nn
 
+from cusrl_amd import ops
 from cusrl_amd.nn import recurrent
 from cusrl_amd.nn.gru import gru_forward, gru_supported, lstm_forward, rnn_forward
 from cusrl_amd.nn.module import Module, ModuleFactory
@@ -27,12 +29,51 @@ def _from_layers(state: Tensor) -> Tensor:
     return state.transpose(0, 1).reshape(state.size(1), -1)
 
 
+def _fused_step(module: nn.RNNBase, input: Tensor, memories: tuple[Tensor, ...] | None, states: int):
+    """Inside ``ops.fused_recurrent_step()``: a no-grad single time step (``input`` [1, N, I]) as ONE launch per layer
+    (``ops.gru_step_forward`` / ``ops.lstm_step_forward``, ``states`` = 1 | 2 memories).  Layer ``l`` reads its column slice of the
+    ``[N, layers * H]`` memories in place and writes its slice of ONE new memory per state; the last layer's ``h'`` slice is the
+    output.  An upper layer's input is a contiguous copy of the slice below it (the kernel's ``x`` has no row stride).  Returns
+    ``(output [1, N, H], new memories)``, or None when the call is not the kernel's: the caller goes on as outside the context."""
+    if not ops.fused_recurrent_step_enabled() or input.shape[0] != 1:
+        return None
+    x, H, layers = input[0], module.hidden_size, module.num_layers
+    N = x.shape[0]
+    names = ("weight_ih_l{}", "weight_hh_l{}", "bias_ih_l{}", "bias_hh_l{}") if module.bias else ("weight_ih_l{}", "weight_hh_l{}")
+    params = [tuple(getattr(module, name.format(layer)) for name in names) + (None,) * (4 - len(names)) for layer in range(layers)]
+    if memories is None:
+        memories = (x.new_zeros((N, layers * H)),) * states
+    if any(m.shape != (N, layers * H) for m in memories):
+        return None
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, *memories, *(p for layer in params for p in layer if p is not None))):
+        return None
+    step = ops.gru_step_forward if states == 1 else ops.lstm_step_forward
+    supported = ops.gru_step_forward_supported if states == 1 else ops.lstm_step_forward_supported
+    new = tuple(torch.empty((N, layers * H), dtype=x.dtype, device=x.device) for _ in range(states))
+    below = torch.empty((N, H), dtype=x.dtype, device=x.device) if layers > 1 else None  # an upper layer's input
+    calls = []
+    for layer in range(layers):
+        columns = slice(layer * H, (layer + 1) * H)
+        out = tuple(n[:, columns] for n in new)
+        calls.append((x.contiguous() if layer == 0 else below, *(m[:, columns] for m in memories), *params[layer], out[0] if states == 1 else out))
+        if not supported(*calls[-1]):
+            return None  # (nothing has been launched)
+    for layer, call in enumerate(calls):
+        step(*call)
+        if layer + 1 < layers:
+            below.copy_(new[0][:, layer * H:(layer + 1) * H])
+    return new[0][:, (layers - 1) * H:].unsqueeze(0), new
+
+
 class _Gru(nn.GRU):
     """``nn.GRU`` parameters; fp32 device batches run as GEMMs + one HIP gate pass per step (nn/gru.py) instead of MIOpen's
     RNN.  ``lengths`` (extension): per-sequence valid lengths on the device — the result of the packed form of the batch."""
 
     def forward(self, input, memory=None, lengths=None):
         if gru_supported(self, input):
+            fused = None if lengths is not None else _fused_step(self, input, None if memory is None else (memory,), 1)
+            if fused is not None:
+                return fused[0], fused[1][0]
             h0 = None if memory is None else _to_layers(memory, self.num_layers, self.hidden_size)
             output, hn = gru_forward(self, input, h0, lengths)
             return output, _from_layers(hn)
@@ -65,6 +106,9 @@ class _Lstm(nn.LSTM):
 
     def forward(self, input, memory=None, lengths=None):
         if gru_supported(self, input):
+            fused = None if lengths is not None else _fused_step(self, input, None if memory is None else (memory["hidden"], memory["cell"]), 2)
+            if fused is not None:
+                return fused[0], {"hidden": fused[1][0], "cell": fused[1][1]}
             state = None if memory is None else (_to_layers(memory["hidden"], self.num_layers, self.hidden_size),
                                                  _to_layers(memory["cell"], self.num_layers, self.hidden_size))
             output, (hn, cn) = lstm_forward(self, input, state, lengths)

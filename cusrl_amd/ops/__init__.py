@@ -70,8 +70,9 @@ from cusrl_amd.ops.mlp import (
     relu_backward_bias,
 )
 from cusrl_amd.ops.recurrent import (
-    gru_bias_partial_rows, gru_bias_partials_supported, gru_gates_backward, gru_gates_forward, lstm_gates_backward,
-    lstm_gates_forward, rnn_cell_backward, rnn_cell_forward,
+    fused_recurrent_step, fused_recurrent_step_enabled, gru_bias_partial_rows, gru_bias_partials_supported, gru_gates_backward,
+    gru_gates_forward, gru_step_forward, gru_step_forward_supported, lstm_gates_backward, lstm_gates_forward, lstm_step_forward,
+    lstm_step_forward_supported, rnn_cell_backward, rnn_cell_forward,
 )
 from cusrl_amd.ops.reward import reward_normalize_, reward_normalize_cpu_
 from cusrl_amd.ops.rollout import (

@@ -1,11 +1,107 @@
-"""Gate passes of one GRU / LSTM / RNN time step (``csrc/gru.hip``, ``recurrent.hip``)."""
+"""Gate passes of one GRU / LSTM / RNN time step (``csrc/gru.hip``, ``recurrent.hip``) and the one-launch no-grad GRU / LSTM time
+step on the matrix cores (``csrc/recurrent_step.hip``)."""
 
 from __future__ import annotations
+
+import threading
+from contextlib import contextmanager
 
 import torch
 
 from cusrl_amd import _native
 from cusrl_amd.ops._common import _checked, _ptr, _stream
+
+# ``fused_recurrent_step()``: per thread, whether ``nn.Gru`` / ``nn.Lstm`` take ``cusrl_gru_step_forward`` /
+# ``cusrl_lstm_step_forward`` for a no-grad single time step
+_fused_step = threading.local()
+
+
+@contextmanager
+def fused_recurrent_step(enabled: bool = True):
+    """Inside the context a no-grad ``L == 1`` call of ``nn.Gru`` / ``nn.Lstm`` (no ``lengths``) runs as one
+    ``cusrl_gru_step_forward`` / ``cusrl_lstm_step_forward`` launch per layer where every layer is supported, and as it does
+    outside the context where not.  Thread-local, nestable, restored on exit."""
+    previous = fused_recurrent_step_enabled()
+    _fused_step.enabled = bool(enabled)
+    try:
+        yield
+    finally:
+        _fused_step.enabled = previous
+
+
+def fused_recurrent_step_enabled() -> bool:
+    return getattr(_fused_step, "enabled", False)
+
+
+def _step_operands(x, states, w_ih, w_hh, b_ih, b_hh, outs):
+    """``(arguments of the C entry without the stream, outs)`` of a step call, or None when the tensors are not what the entry
+    describes (fp32 device tensors, ``x`` / weights contiguous, states and outputs ``[B, H]`` views with unit column stride and
+    one row stride).  ``outs`` None: fresh ``[B, H]`` allocations (for the ``*_supported`` question: a placeholder address)."""
+    tensors = [x, *states, w_ih, w_hh, *(t for t in (b_ih, b_hh) if t is not None), *(outs or ())]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return None
+    if x.dim() != 2 or not all(t.is_contiguous() for t in (x, w_ih, w_hh, *(t for t in (b_ih, b_hh) if t is not None))):
+        return None
+    (B, I), H, G = x.shape, w_hh.shape[-1], 3 if len(states) == 1 else 4  # gates: GRU (h) | LSTM (h, c)
+    if w_ih.shape != (G * H, I) or w_hh.shape != (G * H, H) or any(b is not None and b.shape != (G * H,) for b in (b_ih, b_hh)):
+        return None
+
+    def rows(views):
+        if any(v.shape != (B, H) or v.stride(1) != 1 for v in views):
+            return None
+        strides = {v.stride(0) if B > 1 else H for v in views}
+        return strides.pop() if len(strides) == 1 else None
+
+    ld_h = rows(states)
+    ld_out = H if outs is None else rows(outs)
+    if ld_h is None or ld_out is None:
+        return None
+    return [x.data_ptr(), B, I, *(s.data_ptr() for s in states), ld_h, w_ih.data_ptr(), w_hh.data_ptr(), _ptr(b_ih), _ptr(b_hh), H], ld_out
+
+
+def _step_supported(entry, x, states, w_ih, w_hh, b_ih, b_hh, outs) -> bool:
+    prepared = _step_operands(x, states, w_ih, w_hh, b_ih, b_hh, outs)
+    if prepared is None:
+        return False
+    arguments, ld_out = prepared
+    # (no output given: a fresh allocation — 256-byte aligned and apart from every operand, as the placeholder address is)
+    out_ptrs = [256] * len(states) if outs is None else [o.data_ptr() for o in outs]
+    return bool(getattr(_native.lib(), entry)(*arguments, *out_ptrs, ld_out))
+
+
+def _step_forward(entry, x, states, w_ih, w_hh, b_ih, b_hh, outs):
+    if outs is None:
+        outs = tuple(torch.empty((x.shape[0], w_hh.shape[-1]), dtype=torch.float32, device=x.device) for _ in states)
+    prepared = _step_operands(x, states, w_ih, w_hh, b_ih, b_hh, outs)
+    if prepared is None:
+        raise ValueError(f"{entry}: fp32 device tensors, contiguous x [B, I] and torch.nn.GRU / LSTM parameters, states and outputs "
+                         "[B, H] with unit column stride and one row stride")
+    arguments, ld_out = prepared
+    getattr(_checked, entry)(*arguments, *(o.data_ptr() for o in outs), ld_out, _stream())
+    return outs
+
+
+def gru_step_forward(x, h, w_ih, w_hh, b_ih, b_hh, out=None) -> torch.Tensor:
+    """One no-grad GRU time step of one layer as ONE launch (``cusrl_gru_step_forward``): ``h'`` [B, H] for ``x`` [B, I] and
+    ``h`` [B, H] under ``torch.nn.GRU`` parameters.  ``h`` and ``out`` may be column-slice views of wider matrices (a layer's
+    slice of a ``[B, layers * H]`` memory); ``out`` None: a fresh tensor.  No autograd.  What the kernel does not take raises."""
+    return _step_forward("cusrl_gru_step_forward", x, (h,), w_ih, w_hh, b_ih, b_hh, None if out is None else (out,))[0]
+
+
+def gru_step_forward_supported(x, h, w_ih, w_hh, b_ih, b_hh, out=None) -> bool:
+    """Does :func:`gru_step_forward` take these tensors?  Asked of the library (``cusrl_gru_step_forward_supported``)."""
+    return _step_supported("cusrl_gru_step_forward_supported", x, (h,), w_ih, w_hh, b_ih, b_hh, None if out is None else (out,))
+
+
+def lstm_step_forward(x, h, c, w_ih, w_hh, b_ih, b_hh, out=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """One no-grad LSTM time step of one layer as ONE launch (``cusrl_lstm_step_forward``): ``(h', c')``; ``out`` = ``(h_out,
+    c_out)`` or None.  ``h`` / ``c`` share a row stride, ``h_out`` / ``c_out`` too.  Otherwise as :func:`gru_step_forward`."""
+    return _step_forward("cusrl_lstm_step_forward", x, (h, c), w_ih, w_hh, b_ih, b_hh, out)
+
+
+def lstm_step_forward_supported(x, h, c, w_ih, w_hh, b_ih, b_hh, out=None) -> bool:
+    """Does :func:`lstm_step_forward` take these tensors?  Asked of the library (``cusrl_lstm_step_forward_supported``)."""
+    return _step_supported("cusrl_lstm_step_forward_supported", x, (h, c), w_ih, w_hh, b_ih, b_hh, out)
 
 
 def gru_gates_forward(gi: torch.Tensor, gh: torch.Tensor, b_hh: torch.Tensor | None, h: torch.Tensor, out: torch.Tensor,

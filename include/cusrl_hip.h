@@ -554,6 +554,31 @@ int cusrl_mlp2_wave_forward(const float *input, int64_t rows, int64_t in_feature
                             float *action, float *logp, float *std_out, void *stream);
 int cusrl_mlp2_wave_forward_supported(int64_t in_features, int64_t hidden1, int64_t hidden2, int64_t out_features);
 
+/* ---- one no-grad time step of one GRU / LSTM layer, one launch (csrc/recurrent_step.hip) ----
+ * torch.nn.GRU (gates r, z, n) / torch.nn.LSTM (i, f, g, o) parameters: w_ih [G H, I], w_hh [G H, H], b_ih / b_hh [G H] (both or
+ * neither), G = 3 | 4, row-major.  h_out[b, :] (and c_out[b, :]) = the cell's next state for x[b, :], h[b, :] (and c[b, :]); both
+ * projections run on the matrix cores (fp32 MFMA) and the gate pass on their accumulators with the element expressions of
+ * cusrl_gru_gates_fwd / cusrl_lstm_gates_fwd; no pre-activation is written.  WITHOUT autograd: the acting step of a recurrent
+ * agent.  Replaces the addmm, the recurrent mm and the gate launch of the per-step chain (and its state copies).
+ * x: contiguous [B, I], any float address (I % 4 == 0 and x / w_ih 16-byte aligned: read 16 bytes at a time, else 4 — into the
+ * same sums).  h / c: [B, H] with row stride ld_h floats; h_out / c_out: [B, H] with row stride ld_out — so a layer's column slice
+ * of a [B, layers * H] memory matrix is read and written in place.  A row's result depends on nothing but that row.
+ * Supported (cusrl_*_step_forward_supported, same pointers and sizes): B >= 1; 1 <= I <= 256; 16 <= H <= 256, H % 16 == 0; ld_h,
+ * ld_out >= H and multiples of 4; h, c, h_out, c_out, w_hh, b_ih, b_hh 16-byte aligned; h_out / c_out share no float with x, h,
+ * c or each other (column slices of one row stride may interleave).  Anything else: CUSRL_E_UNSUPPORTED, nothing launched,
+ * nothing written. */
+int cusrl_gru_step_forward(const float *x, int64_t B, int64_t I, const float *h, int64_t ld_h, const float *w_ih, const float *w_hh,
+                           const float *b_ih, const float *b_hh, int64_t H, float *h_out, int64_t ld_out, void *stream);
+int cusrl_gru_step_forward_supported(const float *x, int64_t B, int64_t I, const float *h, int64_t ld_h, const float *w_ih,
+                                     const float *w_hh, const float *b_ih, const float *b_hh, int64_t H, const float *h_out,
+                                     int64_t ld_out);
+int cusrl_lstm_step_forward(const float *x, int64_t B, int64_t I, const float *h, const float *c, int64_t ld_h, const float *w_ih,
+                            const float *w_hh, const float *b_ih, const float *b_hh, int64_t H, float *h_out, float *c_out,
+                            int64_t ld_out, void *stream);
+int cusrl_lstm_step_forward_supported(const float *x, int64_t B, int64_t I, const float *h, const float *c, int64_t ld_h,
+                                      const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int64_t H,
+                                      const float *h_out, const float *c_out, int64_t ld_out);
+
 /* ---- gradient-norm clipping (hook/on_policy/gradient_clipping.py:67-83 -> torch.nn.utils.clip_grad_norm_) ----
  * norm_out[0] = ||grad||_2 (pre-clip, the `grad_norm/default` metric); grad *= min(max_norm / (norm + 1e-6), 1).
  * max_norm < 0: measure only.  grad: float[n], 16-byte aligned (the flat gradient buffer every .grad aliases);
