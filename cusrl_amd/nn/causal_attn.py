@@ -121,6 +121,7 @@ class CausalMultiheadSelfAttention(Module):
         from cusrl_amd import ops
 
         W = self.window_size
+        one_step = input.dim() == 2 or (sequential and input.size(0) == 1)
         if seq_missing := (input.dim() == 2 or not sequential):
             input = input.unsqueeze(0)
         if sequential and input.dim() >= 3:
@@ -128,6 +129,12 @@ class CausalMultiheadSelfAttention(Module):
         batch_dims = input.shape[1:-1]
         input = input.flatten(1, -2).transpose(0, 1)  # [N, L, C]
         batch_size, seq_len, _ = input.shape
+
+        # (done changes nothing at one step: one segment, and the whole cache survives)
+        if one_step and ops.fused_attention_step_enabled() and not torch.is_grad_enabled():
+            step = self._step(input[:, 0], memory, batch_dims, seq_missing)
+            if step is not None:
+                return step
 
         q = self.q_proj(input).view(batch_size, seq_len, self.num_heads, self.head_dim)
         if memory is None:
@@ -169,6 +176,53 @@ class CausalMultiheadSelfAttention(Module):
             output = output.squeeze(0)
         return output, {"input_cache": new_input_cache.reshape(*batch_dims, W * self.input_dim),
                         "cache_mask": new_cache_mask.reshape(*batch_dims, W)}
+
+    def _folded(self) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+        """The parameters of the one-launch step (DESIGN.md "Attention step on the matrix cores"): ``(Aq [C, H * C], aq [H * C],
+        Ao [H * C, O], ao [O])`` with ``qf = x Aq + aq`` the folded queries ``(Wk_h^T Wq_h) x + Wk_h^T bq_h`` and ``output = ctx Ao
+        + ao`` with ``Ao`` the stacked ``(Wo_h Wv_h)^T`` and ``ao = Wo bv + bo``.  Products in float64, rounded once.  Kept on the
+        module (a plain attribute: no buffer, not in the state dict) under the versions and addresses of the six parameters, so an
+        optimizer step, a ``load_state_dict`` or a move to another device refolds."""
+        params = (self.q_proj.weight, self.q_proj.bias, self.kv_proj.weight, self.kv_proj.bias, self.out_proj.weight, self.out_proj.bias)
+        key = tuple((p._version, p.data_ptr()) for p in params)
+        cached = getattr(self, "_step_fold", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        with torch.no_grad():
+            H, D, E = self.num_heads, self.head_dim, self.embed_dim
+            wq, bq, wkv, bkv, wo, bo = (p.detach().double() for p in params)
+            wq, bq, wk = wq.view(H, D, -1), bq.view(H, D), wkv[:E].view(H, D, -1)  # [H, D, C]
+            wv, bv, wo_h = wkv[E:].view(H, D, -1), bkv[E:], wo.view(-1, H, D)      # [H, D, C], [E], [O, H, D]
+            folded = (torch.einsum("hdc,hde->ehc", wk, wq).flatten(1), torch.einsum("hdc,hd->hc", wk, bq).flatten(),
+                      torch.einsum("ohd,hdc->hco", wo_h, wv).flatten(0, 1), wo @ bv + bo)
+            folded = tuple(t.float().contiguous() for t in folded)
+        self._step_fold = (key, folded)
+        return folded
+
+    def _step(self, x: Tensor, memory, batch_dims, seq_missing: bool):
+        """One no-grad time step ``x [N, C]`` inside ``ops.fused_attention_step()``: one ``addmm`` to the folded queries, one
+        ``cusrl_attn_step_forward`` launch (attention over the raw window, and the window rolled), one ``addmm`` from its context.
+        None where the step kernel does not apply — RoPE, another dtype, operands it refuses — and the caller goes on as outside
+        the context."""
+        from cusrl_amd import ops
+
+        if self.rope is not None or self.dtype != torch.float32 or x.dtype != torch.float32 or not x.is_cuda:
+            return None
+        N, W, H, C = x.size(0), self.window_size, self.num_heads, self.input_dim
+        x = x.contiguous()
+        cache = cache_mask = None
+        if memory is not None:
+            cache, cache_mask = memory["input_cache"].reshape(N, W, C), memory["cache_mask"].reshape(N, W)
+        qf = x.new_empty((N, H, C))
+        if not ops.attention_step_supported(qf, x, cache, cache_mask, self.alibi_slopes, window=W):
+            return None
+        aq_weight, aq_bias, ao_weight, ao_bias = self._folded()
+        torch.addmm(aq_bias, x, aq_weight, out=qf.view(N, H * C))
+        ctx, new_cache, new_mask = ops.attention_step_forward(qf, x, cache, cache_mask, self.alibi_slopes, scale=1.0 / math.sqrt(self.head_dim),
+                                                              window=W)
+        output = torch.addmm(ao_bias, ctx.view(N, H * C), ao_weight).unflatten(0, batch_dims)
+        return (output if seq_missing else output.unsqueeze(0),
+                {"input_cache": new_cache.reshape(*batch_dims, W * C), "cache_mask": new_mask.reshape(*batch_dims, W)})
 
     def reset_memory(self, memory, done=None):
         """Empty the cache in place: all of it, or the entries ``done`` (a slice, or a bool ``[N, 1]``) selects."""

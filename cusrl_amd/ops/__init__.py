@@ -28,8 +28,9 @@ from cusrl_amd.ops.advantage import (
 from cusrl_amd.ops.affine import ColumnAffine, column_affine, column_affine_supported
 from cusrl_amd.ops.attention import (Rope, Sdpa, matrix_core_attention, rope, rope_supported, sdpa, sdpa_backward,
                                      sdpa_bwd_mfma_supported, sdpa_mfma_supported, sdpa_supported)
-from cusrl_amd.ops.band_attention import (BandSdpa, band_mask, band_sdpa, band_sdpa_backward, band_sdpa_bwd_mfma_supported,
-                                          band_sdpa_mfma_supported, band_sdpa_supported)
+from cusrl_amd.ops.band_attention import (BandSdpa, attention_step_forward, attention_step_supported, band_mask, band_sdpa,
+                                          band_sdpa_backward, band_sdpa_bwd_mfma_supported, band_sdpa_mfma_supported, band_sdpa_supported,
+                                          fused_attention_step, fused_attention_step_enabled)
 from cusrl_amd.ops.bias_act import bias_act, bias_act_supported
 from cusrl_amd.ops.bijector import BijectorFunction, bijector_supported, sigmoid_bijector, softplus_bijector
 from cusrl_amd.ops.auxiliary import (

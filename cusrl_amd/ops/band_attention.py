@@ -1,16 +1,19 @@
 """Causal sliding-window attention as HIP launches (the band kernels of ``csrc/attention.hip``): query ``i`` of ``Lq`` sees keys
 ``i ... i + W`` of ``Lk = Lq + W`` (the first ``W`` are a cache), cut by a key-validity row, by segment ids and biased by ALiBi
 slopes — the attention core of the recurrent transformer modules (``nn/causal_attn.py``), on the ``[N, L, H, D]`` layout their
-projections leave.  Formulas: include/cusrl_hip.h."""
+projections leave; and the one-launch no-grad time step of those modules in input space (``csrc/attention_step.hip``).  Formulas:
+include/cusrl_hip.h."""
 
 from __future__ import annotations
 
 import math
+import threading
+from contextlib import contextmanager
 
 import torch
 
 from cusrl_amd import _native
-from cusrl_amd.ops._common import _checked, _ptr, _stream
+from cusrl_amd.ops._common import _checked, _ptr, _stream, require_device
 from cusrl_amd.ops.attention import (MAX_SDPA_HEAD_DIM, _backward_operands, _differentiated_inside_double_differentiable, _forward_outputs,
                                      _matrix_core, _rows_arguments, _rows_layout, _sixteen_byte_rule, sdpa)
 
@@ -195,3 +198,89 @@ def band_sdpa(q, k, v, window: int, key_valid=None, q_segment=None, alibi_slopes
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         return BandSdpa.apply(q, k, v, window, key_valid, q_segment, alibi_slopes, key_grad_from, matrix_core, bool(matrix_core_backward))
     return _launch_band_fwd(q, k, v, window, key_valid, q_segment, alibi_slopes, matrix_core)[0]
+
+
+# ------------------------------------------------------------------------------------------- the one-launch acting step
+# ``fused_attention_step()``: per thread, whether ``nn.CausalMultiheadSelfAttention`` takes ``cusrl_attn_step_forward`` for a
+# no-grad single time step
+_fused_step = threading.local()
+
+
+@contextmanager
+def fused_attention_step(enabled: bool = True):
+    """Inside the context a no-grad single time step of ``nn.CausalMultiheadSelfAttention`` without RoPE (and of the encoder layer
+    built on it) runs as one ``addmm``, one ``cusrl_attn_step_forward`` launch and one ``addmm`` where
+    :func:`attention_step_supported` says so, and as it does outside the context where not.  Thread-local, nestable, restored on
+    exit."""
+    previous = fused_attention_step_enabled()
+    _fused_step.enabled = bool(enabled)
+    try:
+        yield
+    finally:
+        _fused_step.enabled = previous
+
+
+def fused_attention_step_enabled() -> bool:
+    return getattr(_fused_step, "enabled", False)
+
+
+def _step_operands(qf, x, cache, cache_mask, alibi_slopes, window, out):
+    """``(input pointers, output pointers, (N, H, W, C))`` of a step call, or None when the tensors are not what
+    ``cusrl_attn_step_forward`` describes: contiguous fp32 ``qf [N, H, C]``, ``x [N, C]``, ``cache [N, W, C]`` with a bool / uint8
+    ``cache_mask [N, W]`` (both None: an empty cache of ``window`` steps), ``alibi_slopes [H]`` or None, all on one device;
+    ``out`` = ``(ctx, cache_out, mask_out)`` of the inputs' shapes (``cache_out`` / ``mask_out`` may be None), or None: fresh
+    allocations (for the ``_supported`` question a placeholder address, and no roll)."""
+    floats = [qf, x, *(t for t in (cache, alibi_slopes) if t is not None), *(t for t in (out or ())[:2] if t is not None)]
+    flags = [t for t in (cache_mask, out[2] if out else None) if t is not None]
+    if not all(isinstance(t, torch.Tensor) and t.device == x.device and t.is_contiguous() for t in (*floats, *flags)):
+        return None
+    if any(t.dtype != torch.float32 for t in floats) or any(t.dtype not in (torch.bool, torch.uint8) for t in flags):
+        return None
+    if qf.dim() != 3 or (cache is None) != (cache_mask is None) or (cache is None and window is None):
+        return None
+    N, H, C = qf.shape
+    W = int(window) if cache is None else cache.shape[1]
+    if x.shape != (N, C) or (cache is not None and (cache.shape != (N, W, C) or cache_mask.shape != (N, W) or window not in (None, W))):
+        return None
+    if alibi_slopes is not None and alibi_slopes.shape != (H,):
+        return None
+    if out is None:
+        outputs = (256, None, None)
+    else:
+        if len(out) != 3 or any(o is not None and o.shape != s for o, s in zip(out, ((N, H, C), (N, W, C), (N, W)))) or out[0] is None:
+            return None
+        outputs = tuple(_ptr(o) for o in out)
+    return (qf.data_ptr(), x.data_ptr(), _ptr(cache), _ptr(cache_mask)), outputs, (N, H, W, C)
+
+
+def attention_step_supported(qf, x, cache, cache_mask, alibi_slopes=None, window: int | None = None, out=None) -> bool:
+    """Does ``cusrl_attn_step_forward`` take these tensors?  The layout of :func:`attention_step_forward`, then asked of the library
+    (``cusrl_attn_step_forward_supported``: ``1 <= H <= 16``, ``W >= 1``, ``C % 4 == 0``, ``4 <= C <= 128``, 16-byte aligned
+    pointers, no output overlapping an input or another output).  Looks at addresses and sizes only: usable without a GPU."""
+    prepared = _step_operands(qf, x, cache, cache_mask, alibi_slopes, window, out)
+    if prepared is None:
+        return False
+    inputs, outputs, sizes = prepared
+    return bool(_native.lib().cusrl_attn_step_forward_supported(*inputs, *outputs, *sizes))
+
+
+def attention_step_forward(qf, x, cache, cache_mask, alibi_slopes=None, scale: float = 1.0, window: int | None = None, out=None):
+    """One no-grad time step of causal sliding-window attention in input space as ONE launch (``cusrl_attn_step_forward``;
+    formulas: include/cusrl_hip.h): ``(ctx [N, H, C], cache_out [N, W, C], mask_out [N, W])`` for the folded queries
+    ``qf [N, H, C]``, the new input ``x [N, C]`` and the window ``cache [N, W, C]`` / ``cache_mask [N, W]`` (both None: an empty
+    cache of ``window`` steps).  Head ``h`` attends over the ``W + 1`` raw inputs with score ``(qf[n, h] . X_j) * scale -
+    alibi_slopes[h] * (W - j)``; the outputs are the probability-weighted inputs and the window rolled by one step (``mask_out`` in
+    ``cache_mask``'s dtype, bool for an empty cache).  ``out``: the three outputs to write (the last two may be None: not
+    written), None: fresh tensors.  No autograd.  What the kernel does not take raises."""
+    require_device(x, "x")
+    if out is None and _step_operands(qf, x, cache, cache_mask, alibi_slopes, window, None) is not None:
+        (N, H, C), W = qf.shape, window if cache is None else cache.shape[1]
+        out = (torch.empty_like(qf), x.new_empty((N, W, C)),
+               torch.empty((N, W), dtype=torch.bool if cache_mask is None else cache_mask.dtype, device=x.device))
+    prepared = None if out is None else _step_operands(qf, x, cache, cache_mask, alibi_slopes, window, out)
+    if prepared is None:
+        raise ValueError("cusrl_attn_step_forward: contiguous fp32 device tensors qf [N, H, C], x [N, C], cache [N, W, C] with a bool / "
+                         "uint8 cache_mask [N, W] (or neither, with 'window'), alibi_slopes [H] or None, and outputs of the same shapes")
+    inputs, outputs, sizes = prepared
+    _checked.cusrl_attn_step_forward(*inputs, _ptr(alibi_slopes), float(scale), *outputs, *sizes, _stream())
+    return tuple(out)

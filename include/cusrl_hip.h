@@ -1187,6 +1187,35 @@ int cusrl_band_sdpa_bwd_mfma(const float *q, int64_t q_stride_n, int64_t q_strid
                              float *dk, float *dv, float *workspace, int64_t N, int64_t H, int64_t Lq, int64_t W, int64_t D,
                              void *stream);
 int cusrl_band_sdpa_bwd_mfma_supported(int64_t Lq, int64_t W, int64_t D);
+/* cusrl_attn_step_forward, ONE launch (csrc/attention_step.hip): ONE no-grad time step (Lq == 1) of causal sliding-window attention
+ * without RoPE, in INPUT space, on v_mfma_f32_16x16x4_f32 - the acting step of cusrl/nn/module/causal_attn.py.  With Wq_h, Wk_h, Wv_h
+ * the head_dim rows of head h in the three projections, q_h . k_hj = (Wk_h^T q_h) . X_j + q_h . bk_h, whose second term is the same
+ * for every key and drops out of the softmax, and sum_j p_j v_hj = Wv_h (sum_j p_j X_j) + bv_h since the p_j sum to one.  So every
+ * head attends over the sequence's raw window with the folded query the caller built, and the caller projects ctx afterwards.
+ * fp32, contiguous:  qf [N, H, C] folded queries;  x [N, C] the new input;  cache [N, W, C] the cached inputs and cache_mask uint8
+ * [N, W], nonzero = the cached step exists (both NULL: an empty cache - zeros, every step hidden);  alibi_slopes [H] or NULL;
+ * ctx [N, H, C];  cache_out [N, W, C] and mask_out uint8 [N, W], the window rolled by one step (either may be NULL: not written).
+ * For sequence n, head h, key j = 0 .. W:
+ *   X_j = cache[n, j] for j < W, X_W = x[n];   key j is visible iff j == W or cache_mask[n, j] != 0;
+ *   s_j = fmaf(-alibi_slopes[h], (float)(W - j), (qf[n, h] . X_j) * scale)   (the band's score at i = 0, the same single rounding;
+ *         without slopes (qf[n, h] . X_j) * scale);   p = softmax of s over the visible keys;   ctx[n, h] = sum_j p_j X_j;
+ *   a hidden key contributes exactly nothing - its row is selected away, not multiplied by zero - whatever the row holds;
+ *   cache_out[n, j] = X_{j + 1} (the loaded bits);   mask_out[n, j] = cache_mask[n, j + 1] (the loaded byte; 0 for an empty cache)
+ *   for j < W - 1, mask_out[n, W - 1] = 1.
+ * One wave per sequence, its H heads the rows of the MFMA tile over one shared key / value operand; the sum over d runs in blocks
+ * of 16 (d = 4 kk + j over the four k slots kk of MFMA j), the sum over keys in sub-tiles of 16 from key 0.  One owning lane per
+ * element, no atomics: the same bits on every call, and a row's bits do not depend on N or on its place in the grid.
+ * Supported (cusrl_attn_step_forward_supported, same pointers and sizes): 1 <= H <= 16, W >= 1, C % 4 == 0, 4 <= C <=
+ * CUSRL_MAX_SDPA_HEAD_DIM; qf, x, cache, ctx, cache_out 16-byte aligned; cache and cache_mask both given or both NULL; no output
+ * sharing a byte with an input or with another output (the roll is never done in place).  Anything else: CUSRL_E_UNSUPPORTED;
+ * CUSRL_E_INVALID for a negative N, H, W or C < 1, C beyond CUSRL_MAX_SDPA_HEAD_DIM, or a NULL qf, x or ctx; nothing is launched or
+ * written in either case.  N == 0 is a successful no-op. */
+int cusrl_attn_step_forward(const float *qf, const float *x, const float *cache, const uint8_t *cache_mask,
+                            const float *alibi_slopes, float scale, float *ctx, float *cache_out, uint8_t *mask_out,
+                            int64_t N, int64_t H, int64_t W, int64_t C, void *stream);
+int cusrl_attn_step_forward_supported(const float *qf, const float *x, const float *cache, const uint8_t *cache_mask,
+                                      const float *ctx, const float *cache_out, const uint8_t *mask_out,
+                                      int64_t N, int64_t H, int64_t W, int64_t C);
 
 /* ---- depthwise 2-D convolution — the spatial half of cusrl/nn/layer/separable_conv.py:52-64, an nn.Conv2d with
  * groups == in_channels == out_channels and zero padding (additive entries of ABI 7; csrc/conv.hip).  fp32, contiguous:
