@@ -1,5 +1,6 @@
 // What the attention translation units share (attention.hip: the VALU bodies; attention_mfma.hip and attention_mfma_bwd.hip: the
-// dense fp32-MFMA forward and backward; attention_mfma_band.hip: the band's fp32-MFMA forward): the operand and shape structs, the
+// dense fp32-MFMA forward and backward; attention_bf16.hip: the dense forward on bf16 operands, with a `Rows` of its own;
+// attention_mfma_band.hip: the band's fp32-MFMA forward): the operand and shape structs, the
 // two visibilities `Mask` (dense) and `Band` (sliding window) with the two tile constants their spans are written in, the
 // online-softmax step, the backward's `probability`, and the host's size and 16-byte rules.  Moved here from attention.hip as they
 // stood; formulas: include/cusrl_hip.h.

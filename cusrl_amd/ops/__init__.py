@@ -26,8 +26,8 @@ from cusrl_amd.ops.advantage import (
     packed_mean_var,
 )
 from cusrl_amd.ops.affine import ColumnAffine, column_affine, column_affine_supported
-from cusrl_amd.ops.attention import (Rope, Sdpa, matrix_core_attention, rope, rope_supported, sdpa, sdpa_backward,
-                                     sdpa_bwd_mfma_supported, sdpa_mfma_supported, sdpa_supported)
+from cusrl_amd.ops.attention import (Rope, Sdpa, SdpaBf16, matrix_core_attention, rope, rope_supported, sdpa, sdpa_backward,
+                                     sdpa_bf16_supported, sdpa_bwd_mfma_supported, sdpa_mfma_supported, sdpa_supported)
 from cusrl_amd.ops.band_attention import (BandSdpa, attention_step_forward, attention_step_supported, band_mask, band_sdpa,
                                           band_sdpa_backward, band_sdpa_bwd_mfma_supported, band_sdpa_mfma_supported, band_sdpa_supported,
                                           fused_attention_step, fused_attention_step_enabled)

@@ -50,11 +50,16 @@ def sdpa_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: b
     a mask and ``is_causal`` together, a bool or fp32 mask that does not require grad and broadcasts to ``(N, H, Lq, Lk)``, and
     — when a gradient is asked for — a forward that is not being built inside ``double_differentiable()``.  Other leading
     dimensions are accepted where folding them into one is a view and no mask is given."""
+    return not torch.is_autocast_enabled("cuda") and _operands_supported(torch.float32, q, k, v, attn_mask, dropout_p, is_causal)
+
+
+def _operands_supported(dtype, q, k, v, attn_mask, dropout_p, is_causal) -> bool:
+    """What :func:`sdpa_supported` asks of the operands of element type ``dtype``, autocast aside."""
     if not all(isinstance(t, torch.Tensor) for t in (q, k, v)) or not q.is_cuda or q.dim() < 3:
         return False
-    if any(t.dtype != torch.float32 or t.device != q.device or t.dim() != q.dim() for t in (q, k, v)):
+    if any(t.dtype != dtype or t.device != q.device or t.dim() != q.dim() for t in (q, k, v)):
         return False
-    if dropout_p != 0.0 or (attn_mask is not None and is_causal) or torch.is_autocast_enabled("cuda"):
+    if dropout_p != 0.0 or (attn_mask is not None and is_causal):
         return False
     if q.dim() != 4 and attn_mask is not None:
         return False
@@ -99,8 +104,9 @@ def matrix_core_attention(enabled: bool = True, backward: bool = False):
 
 
 def _sixteen_byte_rule(*tensors) -> bool:
-    """Every ``[N, L, H, D]`` view's base 16-byte aligned, its ``n`` / ``l`` strides multiples of 4."""
-    return all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 for t in tensors)
+    """Every ``[N, L, H, D]`` view's base 16-byte aligned, its ``n`` / ``l`` strides multiples of 4 (fp32) or 8 (bf16) elements."""
+    return all(t.data_ptr() % 16 == 0 and t.stride(0) * t.element_size() % 16 == 0 and t.stride(1) * t.element_size() % 16 == 0
+               for t in tensors)
 
 
 def _mfma_supported(entry: str, q, k, v, attn_mask, dropout_p, is_causal) -> bool:
@@ -122,6 +128,20 @@ def sdpa_bwd_mfma_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_
     """Does ``cusrl_sdpa_bwd_mfma`` take the backward of this call?  What :func:`sdpa_mfma_supported` asks, with the library's
     ``cusrl_sdpa_bwd_mfma_supported``; ``dout`` is held to the 16-byte rule when it arrives (:func:`sdpa_backward`)."""
     return _mfma_supported("cusrl_sdpa_bwd_mfma_supported", q, k, v, attn_mask, dropout_p, is_causal)
+
+
+def sdpa_bf16_supported(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False) -> bool:
+    """Does ``cusrl_sdpa_fwd_bf16`` take this call right now?  What :func:`sdpa_supported` asks, of ``torch.bfloat16`` tensors (the
+    mask stays bool or fp32), with autocast either off or on with bf16 as its GPU type; the shapes the library accepts
+    (``cusrl_sdpa_fwd_bf16_supported``: ``D % 8 == 0``, ``8 <= D <= 128``) and the 16-byte rule on the ``[N, L, H, D]`` views: every
+    base 16-byte aligned, ``n`` / ``l`` strides multiples of 8."""
+    if not _operands_supported(torch.bfloat16, q, k, v, attn_mask, dropout_p, is_causal):
+        return False
+    if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") != torch.bfloat16:
+        return False
+    if not _native.lib().cusrl_sdpa_fwd_bf16_supported(q.shape[-3], k.shape[-3], q.shape[-1]):
+        return False
+    return _sixteen_byte_rule(*(_one_batch_dimension(t) for t in (q, k, v)))
 
 
 def _sdpa_expression(q, k, v, attn_mask, dropout_p, is_causal):
@@ -210,6 +230,41 @@ class Sdpa(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None
 
 
+def _launch_sdpa_fwd_bf16(q, k, v, mask=None, is_causal: bool = False):
+    """One ``cusrl_sdpa_fwd_bf16`` launch on bf16 ``[N, L, H, D]`` operands :func:`sdpa_bf16_supported` accepted:
+    ``(out [N, Lq, H, D] bf16, lse [N, H, Lq] fp32)``."""
+    N, Lq, H, D = q.shape
+    Lk = k.shape[1]
+    out = torch.empty((N, Lq, H, D), dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty((N, H, Lq), dtype=torch.float32, device=q.device)
+    _checked.cusrl_sdpa_fwd_bf16(*_rows_arguments(q, k, v), *_mask_arguments(mask, N, H, Lq, Lk), int(is_causal), 1.0 / math.sqrt(D),
+                                 out.data_ptr(), lse.data_ptr(), N, H, Lq, Lk, D, _stream())
+    return out, lse
+
+
+class SdpaBf16(torch.autograd.Function):
+    """``apply(q, k, v, mask | None, is_causal[, matrix_core_backward]) -> out`` on bf16 ``[N, L, H, D]`` operands
+    :func:`sdpa_bf16_supported` accepted: one ``cusrl_sdpa_fwd_bf16`` launch forward.  Saved: ``q``, ``k``, ``v``, ``out``, ``lse`` and
+    the mask.  There is no bf16 backward kernel: the backward is :func:`sdpa_backward` on fp32 copies of ``q``, ``k``, ``v``, ``out``
+    and ``dout`` (``matrix_core_backward`` as in :class:`Sdpa`), its three gradients rounded to bf16 once."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, is_causal, matrix_core_backward=False):
+        out, lse = _launch_sdpa_fwd_bf16(q, k, v, mask, is_causal)
+        ctx.save_for_backward(q, k, v, out, lse, *(() if mask is None else (mask,)))
+        ctx.is_causal, ctx.matrix_core_backward = is_causal, matrix_core_backward
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse, *mask = ctx.saved_tensors
+        with torch.autocast("cuda", enabled=False):
+            q, k, v, out, dout = (t.float() for t in (q, k, v, out, dout))
+            grads = sdpa_backward(q, k, v, out, lse, dout, mask[0] if mask else None, ctx.is_causal, ctx.matrix_core_backward)
+        return (*(g.to(torch.bfloat16) for g in grads), None, None, None)
+
+
 def sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, matrix_core: bool | None = None,
          matrix_core_backward: bool | None = None) -> torch.Tensor:
     """``softmax(q k^T / sqrt(D) + mask) v`` per head on the ``[N, L, H, D]`` layout, returned in the same layout.  One launch
@@ -219,18 +274,27 @@ def sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = Fals
 
     ``matrix_core``: True takes the fp32-MFMA forward ``cusrl_sdpa_fwd_mfma`` where :func:`sdpa_mfma_supported` says so and goes
     on as above where it does not; None (the default) reads :func:`matrix_core_attention`, which is off outside the context;
-    False never takes it.  Its results agree with the other forward's to rounding, not to the bit (include/cusrl_hip.h).
+    False never takes it.  Its results agree with the other forward's to rounding, not to the bit (include/cusrl_hip.h).  On
+    ``torch.bfloat16`` tensors - what the attention layers hold under bf16 autocast - True takes ``cusrl_sdpa_fwd_bf16`` where
+    :func:`sdpa_bf16_supported` says so (its backward: ``cusrl_sdpa_bwd`` on fp32 copies, the gradients rounded to bf16); without
+    it they go to ``F.scaled_dot_product_attention`` as every other non-fp32 call does.
 
     ``matrix_core_backward``: the same three values for the backward, independent of ``matrix_core`` (either backward takes
     ``out`` / ``lse`` of either forward): True asks for ``cusrl_sdpa_bwd_mfma`` where it is supported and goes on with
     ``cusrl_sdpa_bwd`` where not; None reads the context's ``backward`` field; False never takes it."""
-    if not sdpa_supported(q, k, v, attn_mask, dropout_p, is_causal):
-        return _sdpa_expression(q, k, v, attn_mask, dropout_p, is_causal)
     if matrix_core is None:
         matrix_core = getattr(_matrix_core, "enabled", False)
-    matrix_core = bool(matrix_core) and sdpa_mfma_supported(q, k, v, attn_mask, dropout_p, is_causal)
     if matrix_core_backward is None:
         matrix_core_backward = getattr(_matrix_core, "backward", False)
+    if matrix_core and sdpa_bf16_supported(q, k, v, attn_mask, dropout_p, is_causal):
+        shape = q.shape
+        q, k, v = (_one_batch_dimension(t) for t in (q, k, v))
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+            return SdpaBf16.apply(q, k, v, attn_mask, bool(is_causal), bool(matrix_core_backward)).view(shape)
+        return _launch_sdpa_fwd_bf16(q, k, v, attn_mask, bool(is_causal))[0].view(shape)
+    if not sdpa_supported(q, k, v, attn_mask, dropout_p, is_causal):
+        return _sdpa_expression(q, k, v, attn_mask, dropout_p, is_causal)
+    matrix_core = bool(matrix_core) and sdpa_mfma_supported(q, k, v, attn_mask, dropout_p, is_causal)
     shape = q.shape
     q, k, v = (_one_batch_dimension(t) for t in (q, k, v))
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):

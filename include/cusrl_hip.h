@@ -1024,7 +1024,7 @@ int cusrl_glu_bwd(int kind, const float *input, const float *dout, float *dinput
 
 /* ---- scaled dot-product attention and the rotary embedding — what cusrl/nn/layer/mha.py:133-140 hands to
  * F.scaled_dot_product_attention, and cusrl/nn/layer/encoding.py:107-125 (additive entries of ABI 7; csrc/attention.hip).
- * fp32 throughout; the [N, H, Lq, Lk] scores are never written to memory.
+ * fp32 throughout (cusrl_sdpa_fwd_bf16 aside); the [N, H, Lq, Lk] scores are never written to memory.
  *
  * Layout: q [N, Lq, H, D], k and v [N, Lk, H, D] with element (n, l, h, d) at base + n * stride_n + l * stride_l + h * D + d
  * (strides in elements, per tensor): the slices of a packed [N, L, 3, H, D] or [N, L, 2, H, D] projection and a
@@ -1084,6 +1084,24 @@ int cusrl_sdpa_fwd_mfma(const float *q, int64_t q_stride_n, int64_t q_stride_l, 
                         int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q, int64_t mask_stride_k, int causal,
                         float scale, float *out, float *lse, int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D, void *stream);
 int cusrl_sdpa_fwd_mfma_supported(int64_t Lq, int64_t Lk, int64_t D);
+/* cusrl_sdpa_fwd_bf16, ONE launch (csrc/attention_bf16.hip): cusrl_sdpa_fwd_mfma's argument list, layout, masks, formulas and
+ * handling of a fully masked row (out = 0, lse = -inf, nothing NaN) with q, k, v and out in bf16 (passed as void pointers; strides in
+ * bf16 elements), on v_mfma_f32_16x16x32_bf16.  keep_mask, bias and lse [N, H, Lq] stay uint8 / fp32 / fp32; out is bf16
+ * [N, Lq, H, D] contiguous.  Numerics: the scores are bf16 x bf16 products accumulated in fp32; scale, bias, the running maximum,
+ * the row sum l (of the UNROUNDED fp32 probabilities) and lse are fp32; the probabilities that multiply v are rounded to bf16
+ * (nearest even); out is accumulated in fp32, scaled by 1 / l and rounded to bf16 once.  ORDER of the sums: over d in blocks of 32
+ * (one MFMA each); over keys in tiles of 32 from the first key, inside a tile l adds ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7))
+ * per lane over keys 4 kk + j and 16 + 4 kk + j, then the lanes kk ^ 1 and kk ^ 2, and out adds the tile's 32 products in one MFMA.
+ * The same bits on every call; a query row's bits do not depend on its lane, wave, workgroup, batch position or Lq.
+ * Supported: cusrl_sdpa_fwd_bf16_supported(Lq, Lk, D) (nonzero for Lq, Lk >= 1 and D % 8 == 0, 8 <= D <= 128) and the 16-byte rule
+ * in bf16 elements for q, k, v - every strided base 16-byte aligned, stride_n and stride_l multiples of 8 - and a 16-byte aligned
+ * out.  CUSRL_E_INVALID / CUSRL_E_UNSUPPORTED as cusrl_sdpa_fwd_mfma returns them; nothing is launched or written in either case.
+ * N == 0 is a successful no-op.  There is no bf16 backward: ops.sdpa differentiates through cusrl_sdpa_bwd on fp32 copies. */
+int cusrl_sdpa_fwd_bf16(const void *q, int64_t q_stride_n, int64_t q_stride_l, const void *k, int64_t k_stride_n, int64_t k_stride_l,
+                        const void *v, int64_t v_stride_n, int64_t v_stride_l, const uint8_t *keep_mask, const float *bias,
+                        int64_t mask_stride_n, int64_t mask_stride_h, int64_t mask_stride_q, int64_t mask_stride_k, int causal,
+                        float scale, void *out, float *lse, int64_t N, int64_t H, int64_t Lq, int64_t Lk, int64_t D, void *stream);
+int cusrl_sdpa_fwd_bf16_supported(int64_t Lq, int64_t Lk, int64_t D);
 /* cusrl_sdpa_bwd_mfma, TWO launches on the stream (csrc/attention_mfma_bwd.hip): the backward of cusrl_sdpa_bwd - its argument
  * list, layout, masks, formulas, workspace (delta) and exact zeros (a masked pair, a fully masked query row, a key no query sees) -
  * on v_mfma_f32_16x16x4_f32.  out and lse may come from either forward.  What differs is the ORDER of the sums.  Over d (the scores,
